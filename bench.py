@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- query Gbp/s of the sketch + L1/L2 hot path on N MI355X (one process per GPU).
 
-  python bench.py --gpus N --steps K --warmup W [--workload configs1|configs2|configs3|configs4|northstar] [--batches B]
+  python bench.py --gpus N --steps K --warmup W [--workload configs1|configs2|configs3|configs4|northstar] [--batches B] [--full]
+                  [--dump-outputs DIR]
 
 With N > 1 and no torch.distributed environment the script starts its own N ranks (torch.distributed.run, 127.0.0.1); started by
 a launcher it checks that WORLD_SIZE == N.  It never prints an `n_gpus` other than the N it was asked for.
@@ -27,13 +28,19 @@ Workloads (BASELINE.json `configs`; the default is configs[1], the configuration
             space, winSketch.hpp:174-214), --dense --pi 80 => sketchSize 498
 --reads / --ref-contigs / --ref-contig-len scale a workload down; the JSON line names what actually ran.
 
-The default run (configs1, nothing scaled, one GPU) carries three more measurements behind the headline one, as extra keys; `value` /
-`config` / `roofline` stay the configs[1] figures:
+A plain run sets up, warms up, times the K steps and prints the line (`roofline` from the HIP events of the timed region and the
+committed PMC passes).  Every other measurement runs only with --full: `cpu_baseline` (the stock binary on a sample of the reads),
+`host_path`, `roofline.int` (the hash-only kernel), configs2's FASTA -> PAF, and -- the default workload (configs1, nothing scaled, one
+GPU) -- three more measurements behind the headline one, as extra keys; `value` / `config` / `roofline` stay the configs[1] figures:
   e2e                 the `mashmap_hip` command line FASTA -> PAF on configs[1] (10 GB of FASTA written to a temporary directory), per stage
   north_star_target   the north_star sentence -- 1 M x 10 kbp reads at pi 85 against the human-scale (3 Gbp) index --, stock segLength 5000
                       and the "10 kbp segments" variant, the stock binary beside it; and `repeat_rich`: the same workload on a reference
                       with human-like repeat structure (make_repeat_rich_reference: ~45 % interspersed repeat families, satellites, N gaps)
 --no-e2e / --no-north-star / --no-configs2 skip them.
+
+--dump-outputs DIR: after the timed steps, what the last one computed -- candidate mappings, L2 loci, L1 candidates, per-fragment stats
+of the resident batch -- goes to DIR/<name>.npy as float64 columns, rows in a canonical order, a fixed seeded sample of them past
+DUMP_LIMIT in all (dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 What rank 0 prints LAST is one JSON object of about 4 KB (compact_line: the contract's keys, `roofline`, `cpu_baseline`, one small numeric
 object per side measurement); the full record of the run goes to profiles/bench_last_full.json.  The synthetic inputs live in
@@ -129,12 +136,13 @@ VALU_PEAK_GINST = SIMDS * CLOCK_HZ / 2.0 / 1e9   # wave64 VALU instructions per 
 VALU_MIX_CYCLES = 3.35                           # cycles per wave-instruction of the sketch kernel's VOP3/VOP2 mix (profiles/r02_valu_rate.txt, r02_sketch_instruction_mix.txt)
 
 
-def roofline_block(ctx, capi, W, workload_key, nF, prof, step_ms, pmc_ok, mean_points=0.0):
+def roofline_block(ctx, capi, W, workload_key, nF, prof, step_ms, pmc_ok, mean_points=0.0, hash_only=True):
     """roofline of the dominant kernel (k_sketch_fast).  What binds it is VALU issue (2 x MurmurHash3_x64_128 per base, 0.25 B/bp in): `bound`
     is "valu", `achieved` = wave64 VALU instructions per launch (PMC SQ_INSTS_VALU of the committed passes of this workload) / the kernel's
     average HIP-event duration in THIS run, `peak` = 1024 SIMDs x 2.4 GHz / 2 cycles (MI355X_MICROARCH.md).  `hbm` is the secondary entry:
     algorithmic bytes per fragment = L/4 packed bases in + 24 B per sketch entry out over the same duration against 8 TB/s,
-    and the PMC traffic.  `int` is the hash-only yardstick of SURVEY 8d(ii), measured in this run."""
+    and the PMC traffic.  `int` is the hash-only yardstick of SURVEY 8d(ii), measured in this run by kernel runs of its own (hash_only=False
+    leaves it out: a plain bench run)."""
     SEG, SKETCH = W["seg"], W["sketch"]
     sk_ms, sk_n = prof["sketch"]
     sk_avg = sk_ms / max(1, sk_n)
@@ -143,11 +151,12 @@ def roofline_block(ctx, capi, W, workload_key, nF, prof, step_ms, pmc_ok, mean_p
     # integer roofline: the same fragments through a kernel that only hashes (2 x MurmurHash3_x64_128 per base)
     integer = None
     try:
-        hms = ctx.bench_hash_only(3)
-        integer = {"hash_only_ms": round(hms, 3), "hash_only_gbps": round(nF * SEG / hms / 1e6, 2),
-                   "sketch_kernel_frac": round(hms / sk_avg, 4) if sk_avg > 0 else None, "step_frac": round(hms / step_ms, 4),
-                   "note": "k_hash_only: the sketch kernel's own geometry (positions per thread, threads per workgroup, LDS claim), staging and tables, "
-                           "nothing but the two hashes per position; frac = its time / the kernel's (step's) time = share of the integer floor reached"}
+        if hash_only:
+            hms = ctx.bench_hash_only(3)
+            integer = {"hash_only_ms": round(hms, 3), "hash_only_gbps": round(nF * SEG / hms / 1e6, 2),
+                       "sketch_kernel_frac": round(hms / sk_avg, 4) if sk_avg > 0 else None, "step_frac": round(hms / step_ms, 4),
+                       "note": "k_hash_only: the sketch kernel's own geometry (positions per thread, threads per workgroup, LDS claim), staging and tables, "
+                               "nothing but the two hashes per position; frac = its time / the kernel's (step's) time = share of the integer floor reached"}
     except capi.MashmapError as e:
         log("[bench] hash-only microbenchmark unavailable:", e)
     # HBM bytes / VALU instructions per launch of that kernel from the committed PMC passes of the same workload
@@ -577,6 +586,44 @@ def compact_line(full, full_path=None):
     return line
 
 
+DUMP_LIMIT = 56 << 20   # --dump-outputs: bytes of .npy data in all (a seeded sample of the rows beyond it)
+
+
+def _columns(rec):
+    """a structured array of the library's records as float64 columns: padding dropped, u64 fields split into exact 32-bit halves"""
+    cols, names = [], []
+    for n in rec.dtype.names:
+        if n.startswith("pad"):
+            continue
+        v = rec[n]
+        if v.dtype == np.uint64:
+            cols += [(v >> np.uint64(32)).astype(np.float64), (v & np.uint64(0xFFFFFFFF)).astype(np.float64)]
+            names += [n + "_hi", n + "_lo"]
+        else:
+            cols.append(v.astype(np.float64)); names.append(n)
+    return np.stack(cols, axis=1) if len(rec) else np.zeros((0, len(names))), names
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """what the last timed step handed its caller, as outdir/<name>.npy (float64, one column per record field): rows in a canonical order
+    (sorted on every column unless `ordered`: the library's output order is not part of its contract), and past an equal share of
+    DUMP_LIMIT a fixed seeded sample of them.  totals.npy holds, per array, the full row count and the column sums over ALL rows."""
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_LIMIT // max(1, len(arrays))
+    totals = []
+    for name, rec, ordered in arrays:
+        m, cols = _columns(rec)
+        if not ordered and len(m):
+            m = m[np.lexsort(m.T[::-1])]
+        totals.append([len(m)] + [float(x) for x in m.sum(axis=0)] + [0.0] * (16 - m.shape[1]))
+        cap = max(1, budget // (8 * max(1, m.shape[1])))
+        if len(m) > cap:
+            m = m[np.sort(np.random.default_rng(seed).choice(len(m), cap, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(m))
+        log("[bench] %s/%s.npy: %d of %d rows, columns %s" % (outdir, name, len(m), int(totals[-1][0]), ",".join(cols)))
+    np.save(os.path.join(outdir, "totals.npy"), np.array(totals, dtype=np.float64))
+
+
 def emit(full):
     """stdout of rank 0: the full record goes to profiles/bench_last_full.json (and gpurun_out/, which travels back from a GPU box), the side
     measurements one small object per line, and LAST the line the driver parses."""
@@ -633,6 +680,10 @@ def main():
     ap.add_argument("--sync-exchange", action="store_true", help="N>1: all-gatherv on the compute stream instead of overlapped with the next batch")
     ap.add_argument("--repeat-rich-reference", action="store_true", help="draw reference and reads from make_repeat_rich_reference instead of uniform ACGT (not a BASELINE configuration)")
     ap.add_argument("--stock", action="store_true", help="configs2: also run the stock binary on the same FASTA files (index ~30 s + mapping) and compare the PAF bytes")
+    ap.add_argument("--full", action="store_true", help="also take the side measurements behind the headline one (cpu_baseline, host_path, e2e, north_star_target, "
+                                                        "configs2, roofline.int); a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (candidate mappings, L2 loci, L1 "
+                                                          "candidates, per-fragment stats) as DIR/<name>.npy, float64")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--north-star-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -725,9 +776,9 @@ def main():
     ctx.set_tables_default(PI)
     log("[rank %d] index build: %.1f s; integer tables: %.2f s" % (rank, index_s, time.time() - t0))
     # the CPU leg indexes the reference with the stock binary: minutes beyond a few hundred Mbp, so it rides on the default workload only
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and sum(len(a) for a in ref_np) <= 400e6
-    want_e2e = is_default and rank == 0 and world == 1 and not args.no_e2e
-    want_e2e2 = bool(W.get("assembly")) and rank == 0 and world == 1 and not args.no_e2e
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and sum(len(a) for a in ref_np) <= 400e6
+    want_e2e = args.full and is_default and rank == 0 and world == 1 and not args.no_e2e
+    want_e2e2 = args.full and bool(W.get("assembly")) and rank == 0 and world == 1 and not args.no_e2e
     e2e2 = None
     if want_e2e2:                                       # before the reads take the room: needs the reference on the device once more
         try:
@@ -760,14 +811,18 @@ def main():
     n1, n2 = ctx.result_counts()
 
     if rank == 0:
-        stats, _, _ = ctx.results()
-        nmap = len(ctx.mappings())
+        stats, l1, l2 = ctx.results()
+        maps = ctx.mappings()
+        nmap = len(maps)
         cnts = ctx.pass_counts()
         bases_step = nreads * READ_LEN * world
         value = bases_step * args.steps / dt / 1e9
         step_ms = dt / args.steps * 1e3
         P = float(stats["nPoints"].mean())
-        roofline = roofline_block(ctx, capi, W, wl_key, nF, prof, step_ms, not scaled, P)
+        if args.dump_outputs:                           # the last timed pass's results, as this rank's caller receives them
+            dump_outputs(args.dump_outputs, [("mappings", maps, False), ("l2_loci", l2, False), ("l1_candidates", l1, False), ("fragment_stats", stats, True)])
+        del l1, l2, maps
+        roofline = roofline_block(ctx, capi, W, wl_key, nF, prof, step_ms, not scaled, P, hash_only=args.full)
         kernels = {k: {"ms_per_step": v[0] / args.steps, "launches_per_step": v[1] / args.steps} for k, v in prof.items() if v[1]}
         ref_mbp = sum(ref_lens) / 1e6
         out = {
@@ -796,7 +851,7 @@ def main():
         # the side measurements never take the headline with them
         if e2e2 is not None:
             out["e2e"] = e2e2
-        if world == 1 and not args.no_host_path and not W.get("assembly"):
+        if args.full and world == 1 and not args.no_host_path and not W.get("assembly"):
             try:
                 out["host_path"] = host_path(ctx, W, nreads, ref_lens, step_ms)
             except Exception as e:
@@ -815,7 +870,7 @@ def main():
                 log("[bench] e2e FASTA -> PAF: %s (%.0f s)" % ({k: out["e2e"].get(k) for k in ("value", "map_s", "device_stage", "error")}, time.time() - t0))
             except Exception as e:
                 log("[bench] e2e failed:", repr(e)); out["e2e"] = {"error": repr(e)}
-        if is_default and world == 1 and not args.no_north_star:
+        if args.full and is_default and world == 1 and not args.no_north_star:
             # in a process of its own, after this one has let go of its index and reads: whatever happens there, the headline line is printed
             reads_np = ref_np = None
             torch.cuda.empty_cache()

@@ -38,29 +38,29 @@ smoke)
   timeout 300 python __graft_entry__.py smoke 2>&1 | tail -3 | tee -a $OUT/log.txt ;;
 bench)
   say "== bench (default line)"
-  MM_E2E_LOG=$OUT/e2e_stage_log.txt timeout 1500 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+  MM_E2E_LOG=$OUT/e2e_stage_log.txt timeout 1500 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
   grep -v "^\[mm\]" $OUT/bench.err | tail -25 | tee -a $OUT/log.txt; full bench ;;
 bench:*)
   WL=${S#bench:}
   say "== bench --workload $WL"
-  timeout 1500 python bench.py --steps 5 --warmup 3 --workload $WL --no-cpu-baseline --no-host-path > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err
+  timeout 1500 python bench.py --full --steps 5 --warmup 3 --workload $WL --no-cpu-baseline --no-host-path > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err
   tail -5 $OUT/bench_$WL.err | tee -a $OUT/log.txt; full bench_$WL ;;
 c2)
   say "== bench --workload configs2 (resident passes + FASTA -> PAF through the command line; C2_EXTRA=--stock adds the stock binary)"
-  MM_E2E2_LOG=$OUT/e2e_configs2_stage_log.txt timeout 1700 python bench.py --steps 5 --warmup 3 --workload configs2 --no-cpu-baseline $C2_EXTRA > $OUT/bench_configs2.json 2> $OUT/bench_configs2.err
+  MM_E2E2_LOG=$OUT/e2e_configs2_stage_log.txt timeout 1700 python bench.py --full --steps 5 --warmup 3 --workload configs2 --no-cpu-baseline $C2_EXTRA > $OUT/bench_configs2.json 2> $OUT/bench_configs2.err
   grep -v "^\[mm\]" $OUT/bench_configs2.err | tail -8 | cut -c1-1200 | tee -a $OUT/log.txt; cat $OUT/e2e_configs2_stage_log.txt | tee -a $OUT/log.txt; full bench_configs2 ;;
 quick)
   say "== configs[1] headline only"
-  timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-e2e --no-north-star > $OUT/quick.json 2> $OUT/quick.err
+  timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-e2e --no-north-star > $OUT/quick.json 2> $OUT/quick.err
   tail -4 $OUT/quick.err | tee -a $OUT/log.txt; full quick ;;
 rr)
   say "== repeat-rich north_star workload"
-  MM_DEBUG=${MM_DEBUG:-} timeout 1500 python bench.py --steps 5 --warmup 3 --workload northstar --repeat-rich-reference --no-cpu-baseline --no-host-path > $OUT/rr.json 2> $OUT/rr.err
+  MM_DEBUG=${MM_DEBUG:-} timeout 1500 python bench.py --full --steps 5 --warmup 3 --workload northstar --repeat-rich-reference --no-cpu-baseline --no-host-path > $OUT/rr.json 2> $OUT/rr.err
   grep -v "^\[mm\] sketch" $OUT/rr.err | tail -12 | tee -a $OUT/log.txt; full rr ;;
 trace:*)
   WL=${S#trace:}
   say "== $WL: rocprofv3 --kernel-trace --stats"
-  timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$WL -o trace -- python bench.py --steps 3 --warmup 3 $(wl_args $WL) $MM_BENCH_EXTRA --no-cpu-baseline --no-host-path --no-e2e --no-north-star > $OUT/trace_$WL.json 2> $OUT/trace_$WL.err
+  timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$WL -o trace -- python bench.py --full --steps 3 --warmup 3 $(wl_args $WL) $MM_BENCH_EXTRA --no-cpu-baseline --no-host-path --no-e2e --no-north-star > $OUT/trace_$WL.json 2> $OUT/trace_$WL.err
   find $OUT/trace_$WL -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} $OUT/kernel_stats_$WL.csv
   rm -rf $OUT/trace_$WL
   grep -E '^"(void )?k_' $OUT/kernel_stats_$WL.csv | head -12 | cut -c1-160 | tee -a $OUT/log.txt ;;
@@ -68,7 +68,7 @@ pmc:*)
   WL=${S#pmc:}
   for C in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU; do
     say "== $WL: rocprofv3 --pmc $C"
-    timeout 1500 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_${WL}_$C -o pmc -- python bench.py --steps 1 --warmup 3 --batches 1 $(wl_args $WL) $MM_BENCH_EXTRA --no-cpu-baseline --no-host-path --no-e2e --no-north-star > /dev/null 2> $OUT/pmc_${WL}_$C.err
+    timeout 1500 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_${WL}_$C -o pmc -- python bench.py --full --steps 1 --warmup 3 --batches 1 $(wl_args $WL) $MM_BENCH_EXTRA --no-cpu-baseline --no-host-path --no-e2e --no-north-star > /dev/null 2> $OUT/pmc_${WL}_$C.err
     python scripts/pmc_summary.py $OUT/pmc_${WL}_$C $C > $OUT/pmc_${WL}_$C.csv 2>> $OUT/log.txt; rm -rf $OUT/pmc_${WL}_$C
     head -8 $OUT/pmc_${WL}_$C.csv | cut -c1-160 | tee -a $OUT/log.txt
   done ;;
