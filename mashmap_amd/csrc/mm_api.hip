@@ -13,6 +13,22 @@ static const char* kKernelNames[MM_K_COUNT] = {
   "k_pack2bit", "k_sketch_fast", "k_sketch_hard", "k_seed_lookup", "k_sort_points",
   "k_l1_sweep", "k_l2_sweep", "k_ref_hash", "k_l2_locate", "k_winnow_tiles", "k_l2_select"};
 
+mm_env mm_read_env() {
+  mm_env v;
+  v.debug = getenv("MM_DEBUG") != nullptr;
+  v.timing = getenv("MASHMAP_HIP_TIMING") != nullptr;
+  v.sketchStats = getenv("MM_SKETCH_STATS") != nullptr;
+  v.l1Literal = getenv("MM_L1_LITERAL") != nullptr;
+  if (const char* e = getenv("MM_L2_PRE_LIMIT")) { const int x = atoi(e); if (x >= 0 && x < 4000) v.l2PreLimit = x; }
+  if (const char* e = getenv("MM_L2_STREAM_MIB")) { const double x = atof(e); if (x > 0) v.l2StreamMiB = x; }
+  v.winnowGsk = getenv("MM_WINNOW_GSK") != nullptr;
+  if (const char* e = getenv("MM_SEED_TAGS")) v.seedTags = atoi(e) != 0;
+  if (const char* e = getenv("MASHMAP_HIP_RCCL")) v.rcclPath = e;
+  v.noRccl = getenv("MASHMAP_HIP_NO_RCCL") != nullptr;
+  v.requireRccl = getenv("MASHMAP_HIP_REQUIRE_RCCL") != nullptr;
+  return v;
+}
+
 std::vector<DevBuf*> mm_ctx::allBufs() {
   DeviceIndex& I = idx;
   return {&I.evKey, &I.evAux, &I.evHash, &I.contigOff, &I.opKey, &I.opAux, &I.opHash, &I.blockOff, &I.evBlock, &I.contigBlock, &I.contigLen, &I.refGroup,
@@ -51,7 +67,7 @@ int mm_create(mm_ctx** out, int device, const mm_params* p) {
     return MM_ERR_DEVICE;
   }
   mm_ctx* c = new mm_ctx();
-  c->device = device; c->P = *p;
+  c->device = device; c->P = *p; c->env = mm_read_env();
   if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreate(&c->evA)) != hipSuccess || (e = hipEventCreate(&c->evB)) != hipSuccess) {
     g_createErr = hipGetErrorString(e); delete c; return MM_ERR_DEVICE;
@@ -541,7 +557,6 @@ int mm_map_fragments(mm_ctx* c) {
   if (!c->idx.ready) { c->err = "mm_map_fragments: no index resident (mm_index_upload / mm_index_build first)"; return MM_ERR_STATE; }
   if (!c->nMinHits) { c->err = "mm_map_fragments: mm_set_tables first"; return MM_ERR_STATE; }
   MM_HIP(c, hipSetDevice(c->device));
-  static const bool timing = getenv("MASHMAP_HIP_TIMING") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   const double a0 = g_mmAllocSeconds;
   int rc = mm_launch_sketch(c);
@@ -551,7 +566,7 @@ int mm_map_fragments(mm_ctx* c) {
   rc = mm_launch_map(c);
   if (rc != MM_OK) return rc;
   if (!c->lastSteady) { MM_HIP(c, hipStreamSynchronize(c->stream)); c->nSyncs++; }   // a steady-state pass ends with its one synchronisation
-  if (timing && !c->lastSteady) {
+  if (c->env.timing && !c->lastSteady) {
     auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     fprintf(stderr, "[mashmap_hip::timing] sized pass (%zu fragments, %llu host waits): sketch launch %.4f s, lookup .. selection %.4f s, of both in hipMalloc / hipFree %.4f s\n",
             c->nFrags, (unsigned long long)c->nSyncs, sec(t0, t1), sec(t1, std::chrono::steady_clock::now()), g_mmAllocSeconds - a0);

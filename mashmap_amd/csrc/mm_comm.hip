@@ -44,14 +44,14 @@ struct Rccl {
 Rccl g_rccl;
 std::mutex g_rcclMu;
 
-Rccl* rccl_open(std::string& err) {
+Rccl* rccl_open(const mm_env& env, std::string& err) {
   std::lock_guard<std::mutex> lk(g_rcclMu);
   if (g_rccl.h) return &g_rccl;
   if (!g_rccl.err.empty()) { err = g_rccl.err; return nullptr; }
   // A process that already has an RCCL mapped (torch ships its own librccl.so: bench.py's ranks run dist.init_process_group("nccl") beside
   // this library's communicator) must not get a second copy of the library with its own global state: take the mapped one first
   // (RTLD_NOLOAD), load one only if there is none.  MASHMAP_HIP_RCCL=path pins a file; MM_DEBUG / MASHMAP_HIP_TIMING log what was bound.
-  const char* names[] = {getenv("MASHMAP_HIP_RCCL"), "librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so.1"};
+  const char* names[] = {env.rcclPath.c_str(), "librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so.1"};
   void* h = nullptr; const char* how = "already mapped";
   for (const char* n : names) { if (n && *n && (h = dlopen(n, RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD))) break; }
   if (!h) { how = "loaded"; for (const char* n : names) { if (n && *n && (h = dlopen(n, RTLD_NOW | RTLD_LOCAL))) break; } }
@@ -59,7 +59,7 @@ Rccl* rccl_open(std::string& err) {
   {
     Dl_info di; void* f = dlsym(h, "ncclGetUniqueId");
     g_rccl.path = (f && dladdr(f, &di) && di.dli_fname) ? di.dli_fname : "?";
-    if (getenv("MM_DEBUG") || getenv("MASHMAP_HIP_TIMING")) fprintf(stderr, "[mm] RCCL bound to %s (%s)\n", g_rccl.path.c_str(), how);
+    if (env.debug || env.timing) fprintf(stderr, "[mm] RCCL bound to %s (%s)\n", g_rccl.path.c_str(), how);
   }
   bool ok = true;
   auto sym = [&](const char* n) { void* p = dlsym(h, n); if (!p) ok = false; return p; };
@@ -142,7 +142,7 @@ extern "C" {
 
 int mm_comm_unique_id(void* id) {
   std::string err;
-  Rccl* R = rccl_open(err);
+  Rccl* R = rccl_open(mm_read_env(), err);
   if (!R || !id) return MM_ERR_DEVICE;
   ncclUniqueId u;
   if (R->GetUniqueId(&u) != ncclSuccess) return MM_ERR_DEVICE;
@@ -153,7 +153,7 @@ int mm_comm_unique_id(void* id) {
 
 int mm_comm_init_rank(mm_ctx* c, const void* id, int rank, int world) {
   if (!id || world < 1 || rank < 0 || rank >= world) { c->err = "mm_comm_init_rank: bad argument"; return MM_ERR_ARG; }
-  Rccl* R = rccl_open(c->err);
+  Rccl* R = rccl_open(c->env, c->err);
   if (!R) return MM_ERR_DEVICE;
   MM_HIP(c, hipSetDevice(c->device));
   mm_comm_release(c);
@@ -175,15 +175,15 @@ int mm_comm_init_local(mm_ctx** ctxs, int n) {
   // every context starts on the copy path (device / peer copies: always available inside one process); distinct GPUs move to RCCL
   // broadcasts when a communicator can be had.  No RCCL, or a failing ncclCommInitAll, is not an error here -- the group stays on
   // peer copies, with a warning -- unless MASHMAP_HIP_REQUIRE_RCCL is set.
-  if (distinct && n > 1 && !getenv("MASHMAP_HIP_NO_RCCL")) {
+  if (distinct && n > 1 && !c0->env.noRccl) {
     std::string why;
-    Rccl* R = rccl_open(why);
+    Rccl* R = rccl_open(c0->env, why);
     std::vector<ncclComm_t> comms(n, nullptr);
     bool ok = R != nullptr;
     if (ok) { const ncclResult_t r = R->CommInitAll(comms.data(), n, devs.data()); if (r != ncclSuccess) { ok = false; why = std::string("ncclCommInitAll: ") + R->GetErrorString(r); } }
     if (ok) for (int i = 0; i < n; i++) { ctxs[i]->comm = comms[i]; ctxs[i]->commCopy = false; }
     else {
-      if (getenv("MASHMAP_HIP_REQUIRE_RCCL")) { c0->err = why; return MM_ERR_DEVICE; }
+      if (c0->env.requireRccl) { c0->err = why; return MM_ERR_DEVICE; }
       fprintf(stderr, "[mm] warning: no RCCL communicator for the local group (%s); candidate mappings are exchanged by peer copies\n", why.c_str());
     }
   }
@@ -209,7 +209,7 @@ int mm_allgatherv_mappings(mm_ctx* c) {
   if (!c->comm || c->commCopy) { c->err = "mm_allgatherv_mappings: mm_comm_init_rank first"; return MM_ERR_STATE; }
   if (!c->mapped || !c->haveReplayTables) { c->err = "mm_allgatherv_mappings: no candidate mappings resident"; return MM_ERR_STATE; }
   if (c->gatherThread.joinable()) { c->err = "mm_allgatherv_mappings: an overlapped exchange is in flight (mm_allgatherv_mappings_end first)"; return MM_ERR_STATE; }
-  Rccl* R = rccl_open(c->err);
+  Rccl* R = rccl_open(c->env, c->err);
   if (!R) return MM_ERR_DEVICE;
   c->gathered = false;
   const int rc = exchange(c, c, R, c->dMappings.p, c->nMappings, c->stream);
@@ -222,7 +222,7 @@ int mm_allgatherv_mappings_begin(mm_ctx* c) {
   if (!c->comm || c->commCopy) { c->err = "mm_allgatherv_mappings_begin: mm_comm_init_rank first"; return MM_ERR_STATE; }
   if (!c->mapped || !c->haveReplayTables) { c->err = "mm_allgatherv_mappings_begin: no candidate mappings resident"; return MM_ERR_STATE; }
   if (c->gatherThread.joinable()) { c->err = "mm_allgatherv_mappings_begin: the previous exchange has not been ended"; return MM_ERR_STATE; }
-  Rccl* R = rccl_open(c->err);
+  Rccl* R = rccl_open(c->env, c->err);
   if (!R) return MM_ERR_DEVICE;
   MM_HIP(c, hipSetDevice(c->device));
   if (!c->commStream) MM_HIP(c, hipStreamCreateWithFlags(&c->commStream, hipStreamNonBlocking));
@@ -266,7 +266,7 @@ int mm_allgatherv_mappings_local(mm_ctx** ctxs, int n) {
     MM_HIP(c, c->dGathered.ensure(c->nGathered * sizeof(mm_mapping) + 64));
   }
   if (!c0->commCopy) {
-    Rccl* R = rccl_open(c0->err);
+    Rccl* R = rccl_open(c0->env, c0->err);
     if (!R) return MM_ERR_DEVICE;
     MM_NCCL(c0, R, R->GroupStart());
     int rc = MM_OK;

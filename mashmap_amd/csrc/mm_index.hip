@@ -264,7 +264,7 @@ extern "C" int mm_index_build(mm_ctx* c, const char* bases, const int64_t* conti
   const int k = c->P.kmerSize, w = c->P.segLength, s = c->P.sketchSize;
   HashContigFn hasher = pick_hasher(k);
   if (!hasher) { c->err = "mm_index_build: kmerSize not compiled in"; return MM_ERR_ARG; }
-  const bool dbg = getenv("MM_DEBUG") != nullptr;
+  const bool dbg = c->env.debug;
   const auto tStart = std::chrono::steady_clock::now();
   auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count(); };
   std::vector<int32_t> clen(nContigs);

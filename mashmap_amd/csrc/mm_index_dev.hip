@@ -381,21 +381,16 @@ int mm_flatten_device_index(mm_ctx* c, const mm_minmer* dRec, size_t n, size_t n
   size_t cap = 16; while (cap < 2 * nk + 2) cap <<= 1;
   // presence filter in front of the table (mm_filter_bits: 3 bits per key inside one 64-bit word): 4..8 bits per key, i.e. 2 MB for the
   // ~3 M keys of a 100 Mbp index -- resident in an XCD's L2, ~7 % false positives.  Most query seeds are absent from the index
-  // (sequencing errors): they cost one cached 8-byte load instead of a table slot fetched over the fabric.  Beyond MM_FILTER_MAX_MIB
-  // (default 64) the filter is off: against a 3 Gbp index no size of it paid (profiles/r02c_log_occupancy_filter.txt).
-  uint64_t bitsPerKey = 4;
-  if (const char* e = getenv("MM_FILTER_BITS_PER_KEY")) bitsPerKey = strtoull(e, nullptr, 10);
-  uint64_t fbits = 4096; while (bitsPerKey && fbits < bitsPerKey * (uint64_t)nk) fbits <<= 1;
-  if (!bitsPerKey) fbits = 0;
-  uint64_t maxMiB = 64;
-  if (const char* e = getenv("MM_FILTER_MAX_MIB")) maxMiB = strtoull(e, nullptr, 10);
+  // (sequencing errors): they cost one cached 8-byte load instead of a table slot fetched over the fabric.  Beyond 64 MiB the filter
+  // is off: against a 3 Gbp index no size of it paid (profiles/r02c_log_occupancy_filter.txt).
+  const uint64_t bitsPerKey = 4, maxMiB = 64;
+  uint64_t fbits = 4096; while (fbits < bitsPerKey * (uint64_t)nk) fbits <<= 1;
   if (fbits / 8 > (maxMiB << 20)) fbits = 0;
-  // Tag layer instead of the filter for tables beyond MM_SEED_TAGS_MIN_MIB (default 1024 MiB of slots: indexes of more than ~30 M keys,
-  // where neither the table nor a filter of any useful size stays cached): one tag byte per slot, buckets of 16 slots.  MM_SEED_TAGS=1 / 0
-  // forces it on / off (tests run the small parity cases both ways).
+  // Tag layer instead of the filter for tables beyond 1024 MiB of slots (indexes of more than ~30 M keys, where neither the table nor a
+  // filter of any useful size stays cached): one tag byte per slot, buckets of 16 slots.  MM_SEED_TAGS=1 / 0 forces it on / off (tests
+  // run the small parity cases both ways).
   bool tagged = cap * 16 > ((size_t)1024 << 20);
-  if (const char* e = getenv("MM_SEED_TAGS_MIN_MIB")) tagged = cap * 16 > ((size_t)strtoull(e, nullptr, 10) << 20);
-  if (const char* e = getenv("MM_SEED_TAGS")) tagged = atoi(e) != 0;
+  if (c->env.seedTags >= 0) tagged = c->env.seedTags != 0;
   if (cap < 4 * MM_TAG_BUCKET) tagged = false;
   if (tagged) fbits = 0;
   MM_HIP(c, I.htSlots.ensure(cap * 16)); MM_HIP(c, I.filter.ensure((fbits ? fbits / 8 : 4) + 64));

@@ -82,10 +82,28 @@ struct DeviceIndex {
   bool ready = false;
 };
 
+// The device library's environment switches ("Environment switches"), read once per context by mm_create: a switch
+// set after a context was created does not reach it
+struct mm_env {
+  bool debug = false;             // MM_DEBUG: what every stage of a pass did, on stderr
+  bool timing = false;            // MASHMAP_HIP_TIMING: wall time of the sized passes (and the RCCL library bound), on stderr
+  bool sketchStats = false;       // MM_SKETCH_STATS: phase cycles of the fast sketch kernel, on stderr
+  bool l1Literal = false;         // MM_L1_LITERAL: every queued fragment through the literal L1 kernel instead of k_l1_stream
+  int l2PreLimit = 4000;          // MM_L2_PRE_LIMIT (0 .. 3999): pre-loads of this many records or more go to the exact L2 kernel
+  double l2StreamMiB = 0;         // MM_L2_STREAM_MIB: budget of one chunk of L2 streams; 0 = sized by the free device memory
+  bool winnowGsk = false;         // MM_WINNOW_GSK: the HBM form of the window sketch of k_winnow_tiles at any sketch size
+  int seedTags = -1;              // MM_SEED_TAGS: 1 / 0 forces the tag layer of the seed table on / off; -1 = by the table's size
+  std::string rcclPath;           // MASHMAP_HIP_RCCL: the RCCL library to bind first
+  bool noRccl = false;            // MASHMAP_HIP_NO_RCCL: a local group exchanges by peer copies even across distinct GPUs
+  bool requireRccl = false;       // MASHMAP_HIP_REQUIRE_RCCL: a local group without a communicator is an error, not a warning
+};
+mm_env mm_read_env();
+
 struct mm_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   mm_params P{};
+  mm_env env;
   std::string err;
 
   // host mirrors needed for downloads in reference layout

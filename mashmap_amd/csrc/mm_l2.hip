@@ -1144,7 +1144,7 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
         budget = std::max<int64_t>(budget, (int64_t)(std::min<size_t>(half, (size_t)128 << 30) / 4));
       }
     }
-    if (const char* e = getenv("MM_L2_STREAM_MIB")) { const double v = atof(e); if (v > 0) budget = (int64_t)(v * 262144.0); }
+    if (c->env.l2StreamMiB > 0) budget = (int64_t)(c->env.l2StreamMiB * 262144.0);
     if (totalOps <= budget || nC <= 1) chunks.push_back(Chunk{0, nC, 0});
     else {
       const int64_t* dOff = c->dL2Off.as<int64_t>();
@@ -1167,7 +1167,7 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
         if (end - base > maxChunkOps) maxChunkOps = end - base;
         c0 = lo; base = end;
       }
-      if (getenv("MM_DEBUG")) fprintf(stderr, "[mm] L2: %lld stream entries of %d candidates in %zu chunks of at most %lld\n", (long long)totalOps, nC, chunks.size(), (long long)maxChunkOps);
+      if (c->env.debug) fprintf(stderr, "[mm] L2: %lld stream entries of %d candidates in %zu chunks of at most %lld\n", (long long)totalOps, nC, chunks.size(), (long long)maxChunkOps);
     }
   }
   if (!steady) {
@@ -1188,21 +1188,19 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
   // buckets of the query-sketch search: at least one per sketch entry (more buckets cost more to fill per candidate than the shorter
   // walks save: profiles/r02z_locate_buckets.txt)
   int NB = 256; while (NB < s) NB <<= 1;
-  if (const char* e = getenv("MM_L2_BUCKETS")) { const int v = atoi(e); if (v >= 64 && v <= 16384 && (v & (v - 1)) == 0) NB = v; }
   // waves per workgroup: 4, fewer when four sketches + bucket tables would not fit a CU's LDS
   int wpb = 4; while (wpb > 1 && mm_locate_lds_per_wave(s, NB) * wpb > 160 * 1024) wpb >>= 1;
   const size_t ldsLoc = mm_locate_lds_per_wave(s, NB) * wpb;
   if (ldsLoc > 160 * 1024) { c->err = "sketchSize too large for the LDS-resident query sketch of k_l2_locate"; return MM_ERR_ARG; }
   // total events of the index -> a shift that leaves 16 bits of key (two radix passes)
   int posShift = 0; { const int64_t nEv = (int64_t)(I.evKey.bytes / 4); while ((nEv >> posShift) > 0xFFFF) posShift++; }
-  static const bool sortLocate = getenv("MM_L2_LOCATE_NO_SORT") == nullptr;
   // pre-loads of this many records or more go to the exact kernel (12-bit cell counts); MM_L2_PRE_LIMIT lowers it so that tests can send
   // every candidate there
-  int preLimit = 4000; if (const char* e = getenv("MM_L2_PRE_LIMIT")) { const int v = atoi(e); if (v >= 0 && v < 4000) preLimit = v; }
+  const int preLimit = c->env.l2PreLimit;
   auto locate = [&](const Chunk& ch) -> int {
     KernelTimer t(c, MM_K_L2_LOCATE);
     const int32_t* order = nullptr;
-    if (sortLocate && ch.n > 4096) {
+    if (ch.n > 4096) {
       MM_HIP(c, c->dL2OrderPos.ensure((size_t)nCbuf * 4 + 64));
       MM_HIP(c, c->dL2Sort[0].ensure((size_t)nCbuf * 4 + 64)); MM_HIP(c, c->dL2Sort[2].ensure((size_t)nCbuf * 4 + 64));
       hipLaunchKernelGGL(k_l2_pos_keys, dim3((unsigned)((ch.n + 255) / 256)), dim3(256), 0, c->stream, ch.c0, ch.n, posShift, c->dL2Info.as<L2Info>(),
@@ -1263,7 +1261,6 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
   if (c->l2Cap < (size_t)nCbuf * 2 + 1024) c->l2Cap = (size_t)nCbuf * 2 + 1024;
   unsigned long long hc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int locap = steady && c->prevLocap ? c->prevLocap : MM_LOCAP0;
-  const bool sortSweep = getenv("MM_L2_NO_SORT") == nullptr;
   for (int attempt = 0; attempt < 24; attempt++) {
     MM_HIP(c, c->dL2.ensure(c->l2Cap * sizeof(mm_l2_locus) + 64));
     MM_HIP(c, c->dL2Tmp.ensure((size_t)nCbuf * locap * sizeof(L2Tmp) + 64));
@@ -1277,7 +1274,7 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
         // lane-per-candidate sweep: candidates in order of descending stream length, so that the 64 streams of a wave end together
         // (a wave runs as long as its longest; lengths spread ~ +-10 % around 45 steps: max of 64 is ~15 % above the mean)
         const int32_t* order = nullptr;
-        if (sortSweep && ch.n > 64) {
+        if (ch.n > 64) {
           MM_HIP(c, c->dL2Order.ensure((size_t)nCbuf * 4 + 64));
           const int rc = mm_order_desc(c, c->dL2Cnt.as<int32_t>(), ch.c0, ch.n, 4, c->dL2Order.as<int32_t>());
           if (rc != MM_OK) return rc;
@@ -1306,7 +1303,7 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
       MM_SYNC(c);
       if (hc[7] && !(hc[6] & 1ull) && !hc[5]) {                            // the few candidates whose 5-bit counters overflowed
         const int nWide = (int)hc[7];
-        if (getenv("MM_DEBUG")) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone with 16-bit cells\n", nWide, ch.n);
+        if (c->env.debug) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone with 16-bit cells\n", nWide, ch.n);
         KernelTimer t(c, MM_K_L2);
         sweep(true, 0, nWide, ch.base, c->dL2Wide.as<int32_t>(), locap, nullptr, 0, ch.c0);
         MM_HIP(c, hipGetLastError());
@@ -1315,7 +1312,7 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
       }
       if (hc[0] && !(hc[6] & 1ull) && !hc[5]) {                            // candidates with a doubly open query hash: the literal sweep
         const int nExact = (int)hc[0];
-        if (getenv("MM_DEBUG")) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone by the exact kernel (overlapping windows of one hash)\n", nExact, ch.n);
+        if (c->env.debug) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone by the exact kernel (overlapping windows of one hash)\n", nExact, ch.n);
         MM_HIP(c, c->dL2Cells.ensure((size_t)nExact * (size_t)(s + 1) * sizeof(ExactCell) + 64));
         KernelTimer t(c, MM_K_L2);
         hipLaunchKernelGGL(k_l2_sweep_exact, dim3((unsigned)((nExact + 63) / 64)), dim3(64), 0, c->stream, JB, nExact, ch.base, c->dL2Exact.as<int32_t>(), c->P.segLength,

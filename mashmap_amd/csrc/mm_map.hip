@@ -1467,9 +1467,8 @@ static int map_pass(mm_ctx* c, const bool steady) {
   if (c->l1Cap < cF * 2 + 1024) c->l1Cap = cF * 2 + 1024;
   DevBuf& listB = c->dListB; DevBuf& listC = c->dListC;
   MM_HIP(c, listB.ensure(cF * 4 + 16)); MM_HIP(c, listC.ensure(cF * 4 + 16)); MM_HIP(c, c->dBigList.ensure(cF * 4 + 16));
-  // fragments with more interval points than k_lookup_l1 sorts go through k_lookup_mid first (MM_NO_MID=1: straight to the HBM path, the A/B switch)
-  static const bool noMid = getenv("MM_NO_MID") != nullptr;
-  const bool useMid = !allSlow && !noMid && s <= MM_MID_MAXSKETCH;
+  // fragments with more interval points than k_lookup_l1 sorts go through k_lookup_mid first
+  const bool useMid = !allSlow && s <= MM_MID_MAXSKETCH;
   if (useMid) MM_HIP(c, c->dMidList.ensure(cF * 4 + 16));
   unsigned long long hMid = 0;
   MM_HIP(c, c->dL1Regions.ensure(sizeof(L1Regions)));
@@ -1497,8 +1496,7 @@ static int map_pass(mm_ctx* c, const bool steady) {
       KernelTimer t(c, MM_K_LOOKUP);
       // the fused path holds a fragment's interval points in LDS + registers: up to 128 of them for the default sketch, 256 / 512 for
       // larger ones (points come in proportion to the sketch: s = 310 averages ~176 per fragment with a long tail)
-      int fuse = s > 256 ? 512 : s > 160 ? 256 : 128;
-      if (const char* e = getenv("MM_FUSE_MAXPTS")) { const int v = atoi(e); fuse = v >= 512 ? 512 : v >= 256 ? 256 : 128; }
+      const int fuse = s > 256 ? 512 : s > 160 ? 256 : 128;
       auto kern = I.tagged ? (fuse == 512 ? k_lookup_l1<512, true> : fuse == 256 ? k_lookup_l1<256, true> : k_lookup_l1<128, true>)
                            : (fuse == 512 ? k_lookup_l1<512, false> : fuse == 256 ? k_lookup_l1<256, false> : k_lookup_l1<128, false>);
       hipLaunchKernelGGL(kern, dim3((nF + MM_LOOKUP_WPB - 1) / MM_LOOKUP_WPB), dim3(MM_LOOKUP_WPB * 64), 0, c->stream, nF, s, c->dFrags.as<DFrag>(),
@@ -1559,7 +1557,7 @@ static int map_pass(mm_ctx* c, const bool steady) {
   }
   size_t denseCap = c->dL1.bytes / sizeof(mm_l1_candidate) - 4;   // room behind the fused candidates for the sweep path's
   const int nBig = (int)hc[7];
-  if (getenv("MM_DEBUG")) {
+  if (c->env.debug) {
     if (steady) fprintf(stderr, "[mm] lookup+L1: %d fragments, steady-state pass (the counts stay on the device)\n", nF);
     else fprintf(stderr, "[mm] lookup+L1: %d fragments, %llu through k_lookup_mid, %d to the sort+sweep path, %llu fused candidates\n", nF, hMid, nBig, hc[2]);
   }
@@ -1579,9 +1577,8 @@ static int map_pass(mm_ctx* c, const bool steady) {
                            c->dReadGroup.as<int32_t>(), c->dReadSelf.as<int32_t>(), c->seqCounterBase, fl, c->dStats.as<mm_frag_stats>(), c->dPtOff.as<int64_t>(),
                            c->dPts.as<uint64_t>(), sortIds, c->dPtKept.as<int32_t>(), nBigDev);
         MM_HIP(c, hipGetLastError());
-        // split mode, plain L1: the points that cannot reach minimumHits go before the sort (k_filter_points; MM_NO_POINT_FILTER=1 is the A/B switch)
-        static const bool noFilter = getenv("MM_NO_POINT_FILTER") != nullptr;
-        if (!windowed && (!c->keepPoints || c->keepFiltered) && !fl.skipPrefix && !noFilter) {
+        // split mode, plain L1: the points that cannot reach minimumHits go before the sort (k_filter_points)
+        if (!windowed && (!c->keepPoints || c->keepFiltered) && !fl.skipPrefix) {
           hipLaunchKernelGGL(k_filter_points, dim3(gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(),
                              c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), c->dPtKept.as<int32_t>(), nBigDev);
           MM_HIP(c, hipGetLastError());
@@ -1595,7 +1592,7 @@ static int map_pass(mm_ctx* c, const bool steady) {
       if (!steady) {
         MM_HIP(c, hipMemcpyAsync(hcls, cls, 8, hipMemcpyDeviceToHost, c->stream));
         MM_SYNC(c);
-        if (getenv("MM_DEBUG")) fprintf(stderr, "[mm] point path: %d queued fragments, after the filter %u lists of more than %d points (LDS sorter), %u beyond the LDS sorter\n", nBig, hcls[0], MM_SORT_WAVECAP, hcls[1]);
+        if (c->env.debug) fprintf(stderr, "[mm] point path: %d queued fragments, after the filter %u lists of more than %d points (LDS sorter), %u beyond the LDS sorter\n", nBig, hcls[0], MM_SORT_WAVECAP, hcls[1]);
       }
       if (hcls[0]) hipLaunchKernelGGL(k_sort_points_block, dim3(hcls[0]), dim3(256), 0, c->stream, cls, c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), listB.as<int32_t>(), sortIds);
       if (hcls[1]) hipLaunchKernelGGL(k_sort_points_global, dim3(hcls[1]), dim3(1024), 0, c->stream, cls + 1, c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), listC.as<int32_t>(), sortIds);
@@ -1612,7 +1609,7 @@ static int map_pass(mm_ctx* c, const bool steady) {
         KernelTimer t(c, MM_K_L1);
         // a wave per fragment streams the sorted points; what it cannot take (a position group across two contigs, minimumHits 0) and
         // every fragment under -Y reference groups goes to the literal one-thread-per-fragment kernel
-        const bool stream = !fl.skipPrefix && !getenv("MM_L1_LITERAL") && !windowed;
+        const bool stream = !fl.skipPrefix && !c->env.l1Literal && !windowed;
         const int32_t* sweepList = c->dBigList.as<int32_t>(); const unsigned int* sweepCount = nullptr;
         if (windowed) {
           const int nFreq = s > 256 ? s : 256;                                     // seeds are numbered by their index in the raw sketch
@@ -1701,9 +1698,8 @@ int mm_launch_map(mm_ctx* c) {
   c->nL1 = c->nL2 = 0; c->nMappings = 0; c->nSyncs = 0; c->lastSteady = false;
   if (nF == 0) return MM_OK;
   const bool allSlow = c->keepPoints || (c->P.flags & MM_FLAG_SKIP_PREFIX) || c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH;
-  static const bool noSteady = getenv("MM_NO_STEADY") != nullptr;
   // (a batch with a tenth more fragments than the one the buffers were sized for would only fail and be redone: it is sized right away)
-  if (c->steadyOk && c->steadyFails < 3 && !allSlow && !noSteady && (size_t)nF <= c->sizedFrags + c->sizedFrags / 10) {
+  if (c->steadyOk && c->steadyFails < 3 && !allSlow && (size_t)nF <= c->sizedFrags + c->sizedFrags / 10) {
     const int rc = map_pass(c, true);
     if (rc == MM_OK) { c->lastSteady = true; c->steadyFails = 0; return MM_OK; }
     if (rc != MM_PASS_REDO) return rc;

@@ -694,9 +694,8 @@ static FastGeom sketch_fast_geom(int K, int s, int maxLen, size_t tabBytes, bool
   FastGeom g;
   // survivors the fast kernel aims for: s + 4.2 sqrt(s) (their count is ~Poisson, so s stays about 4 sigma away): fewer = less queue /
   // table work and less LDS, more fragments redone by k_sketch_hard (measured, profiles/r02v_sketch_geometry.txt: 0.007 % of random
-  // fragments at s = 130, 0.008 % at 310, 0.02 % at 498, at 44 ns each).  MM_SKETCH_CUT = wanted survivors / s.
+  // fragments at s = 130, 0.008 % at 310, 0.02 % at 498, at 44 ns each).
   g.wantFast = (int)(s + 4.2 * sqrt((double)s) + 0.999);
-  if (const char* e = getenv("MM_SKETCH_CUT")) { double cut = atof(e); if (cut < 1.05) cut = 1.05; if (cut > 2.5) cut = 2.5; g.wantFast = (int)(s * cut + 0.999); }
   int n = maxLen - K + 1; if (n < 1) n = 1;
   // positions per thread: 16, or 20 where that fills whole waves better (the workgroup's critical path is ceil(waves / 4 SIMDs) strips)
   auto wavesFor = [&](int SL) { int st = (n + SL - 1) / SL; int w = (st + 63) / 64; return w < 1 ? 1 : (w > 16 ? 16 : w); };
@@ -706,15 +705,13 @@ static FastGeom sketch_fast_geom(int K, int s, int maxLen, size_t tabBytes, bool
     const int c16 = ((w16 + 3) / 4) * 16, c20 = ((w20 + 3) / 4) * 20;
     if (c20 < c16 || (c20 == c16 && w20 < w16)) g.SL = 20;
   }
-  if (const char* e = getenv("MM_SKETCH_SL")) { const int v = atoi(e); if (v == 16 || (v == 20 && sl20Built && 20 + K - 1 <= 48)) g.SL = v; }
   g.threads = wavesFor(g.SL) * 64;
-  if (const char* e = getenv("MM_SKETCH_THREADS")) { const int t = atoi(e); if (t >= 64 && t <= 1024 && t % 64 == 0) g.threads = t; }
   const int nWaves = g.threads / 64;
   // a wave queues the survivors of its 64 threads' strips: their expectation + qsig standard deviations; the table has htf slots per
   // wanted survivor (load limit = 5/8 of them).  The kernel's table phases wait on LDS latency and are hidden by the other workgroups
   // of the CU, whose number the LDS footprint decides (allocated in 1280-byte units out of 160 KB): the roomy geometry is kept unless a
   // tighter one lets one more workgroup in (s = 130: 7 instead of 6, s = 310: 5 instead of 4, s = 498: 4 instead of 3 -- 49 -> 42 ms per
-  // 1.6 M fragments there).  MM_SKETCH_HTF / MM_SKETCH_QSIG pin the two numbers.
+  // 1.6 M fragments there).
   int nStrips = (n + g.SL - 1) / g.SL; if (nStrips < 1) nStrips = 1;
   const int passes = (nStrips + g.threads - 1) / g.threads;
   double ex = 64.0 * passes * g.SL * (double)g.wantFast / (double)n; if (ex > g.wantFast) ex = g.wantFast;
@@ -726,17 +723,10 @@ static FastGeom sketch_fast_geom(int K, int s, int maxLen, size_t tabBytes, bool
     const size_t unit = 1280, alloc = (g.lds + unit - 1) / unit * unit;
     return (int)((size_t)160 * 1024 / alloc);      // workgroups a CU holds
   };
-  const char* eh = getenv("MM_SKETCH_HTF"); const char* eq = getenv("MM_SKETCH_QSIG");
-  if (eh || eq) {
-    double htf = eh ? atof(eh) : 2.4, qsig = eq ? atof(eq) : 6.0;
-    if (htf < 1.8) htf = 1.8; if (htf > 4.0) htf = 4.0; if (qsig < 3.0) qsig = 3.0; if (qsig > 8.0) qsig = 8.0;
-    (void)shape(htf, qsig);
-  } else {
-    const double cand[3][2] = {{2.4, 6.0}, {2.2, 6.0}, {2.2, 5.0}};
-    int best = 0, bestWg = shape(cand[0][0], cand[0][1]);
-    for (int i = 1; i < 3; i++) { const int wg = shape(cand[i][0], cand[i][1]); if (wg > bestWg) { bestWg = wg; best = i; } }
-    (void)shape(cand[best][0], cand[best][1]);
-  }
+  const double cand[3][2] = {{2.4, 6.0}, {2.2, 6.0}, {2.2, 5.0}};
+  int best = 0, bestWg = shape(cand[0][0], cand[0][1]);
+  for (int i = 1; i < 3; i++) { const int wg = shape(cand[i][0], cand[i][1]); if (wg > bestWg) { bestWg = wg; best = i; } }
+  (void)shape(cand[best][0], cand[best][1]);
   return g;
 }
 // hard kernel's table: the load limit, 5/8 of it, stays >= 2 s (the window [s, limit] the cut must hit is an octave wide); no larger
@@ -758,12 +748,11 @@ static SketchPlan sketch_plan(int K, int s, int maxLen, size_t tabBytes, bool sl
   SketchPlan P;
   P.g = sketch_fast_geom(K, s, maxLen, tabBytes, sl20Built);
   P.ldsFast = P.g.lds;
-  P.useFast = P.ldsFast <= lim && P.g.HT + MM_SK_PAD <= 8192 && maxLen < (1 << 18) && !getenv("MM_SKETCH_ALL_HARD");
+  P.useFast = P.ldsFast <= lim && P.g.HT + MM_SK_PAD <= 8192 && maxLen < (1 << 18);
   P.HTH = sketch_ht_hard(s);
-  P.spill = getenv("MM_SKETCH_SPILL") != nullptr;
   P.ldsHard = sketch_hard_lds(tabBytes, maxLen, P.HTH, MM_SK_PADH);
-  if (P.ldsHard > lim || P.spill) {
-    P.spill = true;
+  P.spill = P.ldsHard > lim;
+  if (P.spill) {
     P.ldsHard = sketch_hard_lds_spill(tabBytes, maxLen, P.HTH, MM_SK_PADH);
     if (P.ldsHard > lim) {                          // not a power of two then: load limit 5/8 HT >= 2 s
       P.HTH = (((s * 16 + 4) / 5) + 63) / 64 * 64;
@@ -837,8 +826,7 @@ static int launch_sketch_k(mm_ctx* c) {
   }
   MM_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 64, c->stream));
   unsigned long long* phaseStats = nullptr;
-  if (getenv("MM_SKETCH_STATS")) { phaseStats = c->dCounters.as<unsigned long long>() + 24; MM_HIP(c, hipMemsetAsync(phaseStats, 0, 64, c->stream)); }
-  // MM_SKETCH_PROBE=1: the fast kernel probes the seed table for the sketch it emits (needs the queue memory to hold s values)
+  if (c->env.sketchStats) { phaseStats = c->dCounters.as<unsigned long long>() + 24; MM_HIP(c, hipMemsetAsync(phaseStats, 0, 64, c->stream)); }
   if (plan.useFast) {
     KernelTimer t(c, MM_K_SKETCH);
     auto launch = [&](auto kern) {
@@ -864,7 +852,7 @@ static int launch_sketch_k(mm_ctx* c) {
     fprintf(stderr, "[mm] sketch phases, shader-clock cycles per workgroup (thread 0), %d fragments, %d threads x %d positions, HT %d, queue %d/wave, lds %zu: stage+init %.0f | hash %.0f | wait %.0f | drain %.0f | occupancy+list %.0f | rank+emit %.0f\n",
             nF, g.threads, g.SL, g.HT, g.QC, ldsFast, (double)h[0] / nF, (double)h[1] / nF, (double)h[2] / nF, (double)h[3] / nF, (double)h[4] / nF, (double)h[5] / nF);
   }
-  if (getenv("MM_DEBUG")) {
+  if (c->env.debug) {
     uint32_t nHard = 0;
     MM_HIP(c, hipMemcpyAsync(&nHard, c->dCounters.p, 4, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipStreamSynchronize(c->stream));
@@ -899,10 +887,7 @@ static int launch_hash_only_k(mm_ctx* c, int reps, double* msAvg) {
   // the sketch kernel's geometry for these fragments: positions per thread, threads per workgroup, LDS per workgroup
   const FastGeom g = sketch_fast_geom(K, c->P.sketchSize, maxLen, sizeof(Tabs), MMHasSL20<K>::value);
   const size_t need = sizeof(Tabs) + (((size_t)(maxLen + 15) / 16 + 4) * 4 + 15) / 16 * 16;
-  size_t lds = (g.lds > need && g.lds <= 160 * 1024) ? g.lds : need;
-  // MM_HASH_ONLY_LDS=bytes: claim that much LDS per workgroup instead (occupancy experiment); MM_HASH_ONLY_BARE=1: only what the kernel needs
-  if (getenv("MM_HASH_ONLY_BARE")) lds = need;
-  if (const char* e = getenv("MM_HASH_ONLY_LDS")) { const size_t want = (size_t)atol(e); if (want > need && want <= 160 * 1024) lds = want; }
+  const size_t lds = (g.lds > need && g.lds <= 160 * 1024) ? g.lds : need;
   if (c->sketchTabsK != K) {
     MM_HIP(c, c->dSketchTabs.ensure(sizeof(Tabs)));
     hipLaunchKernelGGL((k_sketch_tables<K>), dim3(1), dim3(256), 0, c->stream, c->dSketchTabs.as<Tabs>());

@@ -570,7 +570,7 @@ int mm_winnow_contig_device(mm_ctx* c, WinnowBuffers& B, const uint64_t* dH, con
   // windows per tile: a segment length's worth -- except with the sketch in HBM (sketchSize > MM_WINNOW_LDS_SKETCH), where a window step costs scans
   // of tens of thousands of candidates and a cold start is one streamed pass: there the tiles shrink (down to w / 16) until there are
   // about four per CU, so that a small reference still fills the GPU
-  const bool gskTiles = s > MM_WINNOW_LDS_SKETCH || getenv("MM_WINNOW_GSK") != nullptr;
+  const bool gskTiles = s > MM_WINNOW_LDS_SKETCH || c->env.winnowGsk;
   const int TW = !gskTiles ? w : (int)std::max<int64_t>((int64_t)std::max(1, w / 16), std::min<int64_t>((int64_t)w, ((int64_t)nW + 1023) / 1024));
   const int nTiles = nW - 1 <= 0 ? 1 : (int)(((int64_t)nW - 1 + TW - 1) / TW);
   // cut: the s-th smallest of wk canonical hashes (min of two uniforms) is ~ s / (2 wk) * 2^64; keep 2.5x that
@@ -598,7 +598,7 @@ int mm_winnow_contig_device(mm_ctx* c, WinnowBuffers& B, const uint64_t* dH, con
   MM_HIP(c, B.status.ensure((size_t)nTiles * 4 + 64)); MM_HIP(c, B.open.ensure((size_t)nTiles * s * sizeof(WnOpenRun) + 64));
   MM_HIP(c, B.outOff.ensure((size_t)nTiles * 8 + 64));
   // the window's sketch in LDS while it fits next to at least 64 staged candidates (sketchSize <= MM_WINNOW_LDS_SKETCH), in HBM beyond
-  const bool gsk = s > MM_WINNOW_LDS_SKETCH || getenv("MM_WINNOW_GSK") != nullptr;   // (MM_WINNOW_GSK=1: the HBM form at any size, for the tests)
+  const bool gsk = s > MM_WINNOW_LDS_SKETCH || c->env.winnowGsk;   // (MM_WINNOW_GSK=1: the HBM form at any size, for the tests)
   const size_t ldsSketch = gsk ? WnBlockSketch::ldsBytes(WnBlockSketch::capFor(s)) : (size_t)(s + 1) * 16;
   int ldsCand = 1024; while ((size_t)ldsCand * 13 + ldsSketch > 60 * 1024 && ldsCand > 64) ldsCand >>= 1;
   const size_t ldsSparse = ldsSketch + (size_t)ldsCand * 13 + 16;

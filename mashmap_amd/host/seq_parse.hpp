@@ -733,7 +733,7 @@ class BatchReader {
 
   void parseWindow(const char* p, size_t n, ParsedBatch& out) {
     using detail::Rec;
-    if (packOutput_ && out.names.empty() && !getenv("MASHMAP_HIP_TWO_PASS_PACK") && parseWindowPackedOnePass(p, n, out)) return;
+    if (packOutput_ && out.names.empty() && parseWindowPackedOnePass(p, n, out)) return;
     const char* b = p; const char* e = p + n;
     const unsigned T = (unsigned)std::min<size_t>(threads_, std::max<size_t>(1, n >> 16));
     // piece t = records that start in [cut[t], cut[t+1])

@@ -18,8 +18,7 @@
 // A device PASS covers as many parsed batches as it takes to fill the GPU (MASHMAP_HIP_COALESCE_MBP, default 3072 Mbp; the kernels of a
 // 512 Mbp pass run at ~120 Gbp/s, those of a 2 Gbp pass at ~150): the batches of a pass are laid end to end in HBM by
 // mm_reads_upload_packed_parts, each from its own page-locked buffer, so the reader's unit (and the memory it locks) stays small.  A
-// pass takes what is queued when the GPU falls free and never waits for more (greedy; MASHMAP_HIP_PASS_POLICY=ramp: the round-4 plan that
-// grew passes 1, 1, 2, 4 ... to the coalescing limit and shrank them towards a known end).
+// pass takes what is queued when the GPU falls free and never waits for more.
 //
 // Device stage.  The kernels report, per fragment, the candidate mappings doL2Mapping would have pushed (mm_mapping, k_l2_select);
 // with several contexts (MASHMAP_HIP_DEVICES, one per GPU, index replicated by Sketch) a batch -- 512 Mbp PER CONTEXT -- is cut into
@@ -28,7 +27,6 @@
 // MASHMAP_HIP_EXCHANGE=allgather puts the device-side all-gatherv (mm_allgatherv_mappings_local, RCCL over xGMI) in front instead.
 #pragma once
 #include <malloc.h>
-#include <sys/mman.h>
 
 #include <algorithm>
 #include <atomic>
@@ -86,7 +84,7 @@ class Map {
   // order (mm_reads_prefetch_packed_append), up to twice a pass's worth.  Whoever sees room sends the next block -- the reader the moment
   // it has parsed a batch, the device stage right after an upload has emptied part of the area -- so the copies of the batches behind a
   // pass always run under that pass's kernels.  stagedBases[i]: bases of queued batches already sent to context i (guarded by pfMu).
-  std::mutex pfMu; std::vector<size_t> stagedBases; size_t stageCapBases = 0, stageReserveBases = 0; bool earlyPrefetch = true;
+  std::mutex pfMu; std::vector<size_t> stagedBases; size_t stageCapBases = 0, stageReserveBases = 0;
   bool exchangeFellBack = false;                 // a default RCCL all-gatherv failed once: per-context downloads for the rest of the run
   skch::Time::time_point tStart = skch::Time::now();   // MASHMAP_HIP_TIMING lines carry the time since the Map was constructed
   // one write per diagnostic line: three stages log at once, and `std::cerr << a << b` from two threads interleaves inside a line
@@ -159,6 +157,8 @@ class Map {
     // single-GPU run (tens of milliseconds of kernels), instead of an n-th of it
     const QueryBatchPlan plan = queryBatchPlan(param.querySequences, ctxs.size());
     const size_t batchBases = plan.batchBases;
+    // the reader's workers normalise and pack the bases (2 bit + N mask, pack2bit.hpp) while they drop the line breaks, so that PCIe
+    // carries 0.375 bytes per base instead of 1 (mm_reads_upload_packed); MASHMAP_HIP_ASCII_UPLOAD=1 ships ASCII to k_pack2bit instead
     packedUpload = getenv("MASHMAP_HIP_ASCII_UPLOAD") == nullptr;
     // batches per device pass: only with one context (the blocks of a sharded batch are not consecutive reads across batches) and packed
     // uploads; MASHMAP_HIP_COALESCE_MBP=0 maps every batch by itself
@@ -171,38 +171,14 @@ class Map {
       const int reserve = (int)std::min<uint64_t>(0x7fffffffu, frags + frags / 4 + 1024);
       for (mm_ctx* c : ctxs) if (mm_set_option(c, MM_OPT_RESERVE_FRAGMENTS, reserve) != MM_OK) die("mm_set_option", c);
     }
-    if (!getenv("MASHMAP_HIP_NO_MALLOPT") && (!plan.inputKnown || plan.inputBytes > (256u << 20))) {
+    if (!plan.inputKnown || plan.inputBytes > (256u << 20)) {
       // every batch allocates and frees a few megabyte-sized vectors (records, per-read results, PAF text) from three stages at once:
       // keep them on the heap instead of mmap/munmap per batch (each unmap interrupts every thread of the process), and keep the heap
       mallopt(M_MMAP_THRESHOLD, 32 << 20); mallopt(M_TRIM_THRESHOLD, 1 << 30); mallopt(M_TOP_PAD, 256 << 20);
     }
-    // the reader's workers normalise and pack the bases (2 bit + N mask, pack2bit.hpp) while they drop the line breaks, so that PCIe
-    // carries 0.375 bytes per base instead of 1 (mm_reads_upload_packed); MASHMAP_HIP_ASCII_UPLOAD=1 ships ASCII to k_pack2bit instead
-    earlyPrefetch = getenv("MASHMAP_HIP_NO_EARLY_PREFETCH") == nullptr;
     stagedBases.assign(ctxs.size(), 0);
     stageCapBases = stagingCapBases(plan, ctxs.size());                               // per context: the pass being assembled and the one behind it (skch_types.hpp)
     stageReserveBases = stagingReserveBases(plan, ctxs.size());
-    // diagnostic (MASHMAP_HIP_STALL_TRACE=1): a thread that sleeps 0.5 ms at a time and reports when the sleep, a one-page mmap/munmap
-    // (address-space lock) or a first touch of a fresh page took more than 3 ms -- tells a process-wide stall (scheduler, CPU quota)
-    // from a lock inside the process when the stage timings show all three stages pausing at once
-    std::atomic<bool> stallStop{false};
-    std::thread stallTrace;
-    if (getenv("MASHMAP_HIP_STALL_TRACE")) stallTrace = std::thread([&]() {
-      while (!stallStop) {
-        const auto a = skch::Time::now();
-        std::this_thread::sleep_for(std::chrono::microseconds(500));
-        const auto b = skch::Time::now();
-        void* q = mmap(nullptr, 4096, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        const auto c = skch::Time::now();
-        if (q != MAP_FAILED) { *(volatile char*)q = 1; }
-        const auto d = skch::Time::now();
-        if (q != MAP_FAILED) munmap(q, 4096);
-        const auto e = skch::Time::now();
-        auto sec = [](skch::Time::time_point x, skch::Time::time_point y) { return std::chrono::duration<double>(y - x).count(); };
-        if (sec(a, e) > 0.0035)
-          LogLine() << "[mashmap_hip::stall] sleep " << sec(a, b) << " mmap " << sec(b, c) << " touch " << sec(c, d) << " munmap " << sec(d, e) << at();
-      }
-    });
     std::thread reader([&]() {
       // multi-threaded ingest (seq_parse.hpp): a window of the file per batch, parsed straight into a page-locked buffer.  8 workers:
       // memchr + memcpy at that width keep up with the device stage, and more of them page-faulting through the same file mapping next
@@ -253,7 +229,7 @@ class Map {
           // while holding it would never be served.
           parsed.waitSpace();
           std::lock_guard<std::mutex> lk(pfMu);
-          if (earlyPrefetch && packedUpload) {
+          if (packedUpload) {
             const std::vector<size_t> cut = blocksOf(batch);
             for (size_t i = 0; i < ctxs.size(); i++) issuePrefetch(batch, i, cut);
           }
@@ -271,29 +247,20 @@ class Map {
       }
     });
     {
-      // pass size: ramps up from one batch (so the post stage has work after one batch's worth of time), levels at the coalescing limit,
-      // and comes down again towards the end of an input whose size is known (the last pass is followed by nothing that could hide it)
-      // Default: greedy -- a pass takes whatever the reader has queued when the GPU falls free (at least one batch, at most maxGroup) and
+      // pass size, greedy: a pass takes whatever the reader has queued when the GPU falls free (at least one batch, at most maxGroup) and
       // never waits for more.  A one-batch pass costs more per base than the reader needs for a batch, so the queue grows and the next pass
       // takes two or three: the sizes balance themselves where the device keeps up with the reader, the post stage gets its work in a
       // steady trickle instead of six batches at a time, and what is left when the input ends is one small pass.
-      // MASHMAP_HIP_PASS_POLICY=ramp is the previous plan (1, 1, 2, 4 ... up to the coalescing limit, down again towards a known end).
-      const char* ppe = getenv("MASHMAP_HIP_PASS_POLICY");
-      const bool greedy = !(ppe && std::string(ppe) == "ramp");
       std::vector<Batch> grp;
-      uint64_t doneBases = 0;
-      while (true) {
-        const size_t want = maxGroup == 1 ? 0 : greedy ? 1 : mmhost::passWant(batchBases, plan.passBases, plan.inputKnown, plan.inputBytes, doneBases);
-        if (!parsed.getGroup(grp, want, maxGroup, greedy && maxGroup > 1)) break;
+      while (parsed.getGroup(grp, maxGroup)) {
         deviceStage(grp, parsed);
-        for (auto& b : grp) { doneBases += b.bases(); mapped.put(std::move(b)); }
+        for (auto& b : grp) mapped.put(std::move(b));
         grp.clear();
       }
       mapped.close();
     }
     reader.join();
     poster.join();
-    stallStop = true; if (stallTrace.joinable()) stallTrace.join();
     HostBufferPool::instance().stop();                      // nobody asks for page-locked buffers any more
 
     if (param.filterMode == filter::ONETOONE) {            // :358-406
@@ -420,7 +387,7 @@ class Map {
         // order, while the pass is mapped; what the reader parses from now on it sends itself
         std::lock_guard<std::mutex> lk(pfMu);
         for (const auto& bt : grp) if (bt.prefetched.size() == nCtx && bt.prefetched[i]) { const auto ct = blocksOf(bt); stagedBases[i] -= (size_t)(bt.in.offs[ct[i + 1]] - bt.in.offs[ct[i]]); }
-        if (earlyPrefetch && packedUpload) parsed.forEach([&](Batch& q) { issuePrefetch(q, i, blocksOf(q)); });
+        if (packedUpload) parsed.forEach([&](Batch& q) { issuePrefetch(q, i, blocksOf(q)); });
       }
       const auto p1 = skch::Time::now();
       if (mm_map_fragments(c) != MM_OK) die("mm_map_fragments", c);
@@ -511,8 +478,7 @@ class Map {
     std::vector<int32_t> chunkMapped(nChunks, 0);
     // no wider than the CPUs the process may use (a container's quota: seq_parse.hpp availableCpus) -- more threads than that do not
     // finish the batch sooner, they get the whole process throttled
-    const char* pte = getenv("MASHMAP_HIP_POST_THREADS");
-    const unsigned nThreads = pte ? (unsigned)std::max(1, atoi(pte)) : std::min((unsigned)std::max(1, param.threads), mmhost::availableCpus());
+    const unsigned nThreads = std::min((unsigned)std::max(1, param.threads), mmhost::availableCpus());
     std::atomic<size_t> next(0);
     auto work = [&]() {
       std::string text;                                    // the chunk's PAF lines (MapPost::appendReadMappings: std::to_chars, no stream)

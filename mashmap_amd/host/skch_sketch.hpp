@@ -106,7 +106,7 @@ class Sketch {
     if (!p.saveIndexFilename.empty()) this->saveIndex();
     for (size_t i = 1; i < ctxs_.size(); i++)        // replicas of the resident index, GPU to GPU
       if (mm_index_replicate(ctxs_[i], ctx_) != MM_OK) { std::cerr << "[mashmap_hip::skch::Sketch] ERROR: mm_index_replicate: " << mm_last_error(ctxs_[i]) << std::endl; exit(1); }
-    if (!getenv("MASHMAP_HIP_ASCII_UPLOAD") && !getenv("MASHMAP_HIP_NO_EARLY_PREFETCH")) {
+    if (!getenv("MASHMAP_HIP_ASCII_UPLOAD")) {
       // the staging area skch::Map's reader sends its packed batches ahead into (skch_map.hpp: issuePrefetch reserves the same size): allocated
       // here, behind the index build, so that the reader's second batch does not wait ~10 ms for a multi-gigabyte hipMalloc
       const QueryBatchPlan plan = queryBatchPlan(p.querySequences, ctxs_.size());

@@ -266,7 +266,7 @@ inline QueryBatchPlan queryBatchPlan(const std::vector<std::string>& queryFiles,
     q.inputBytes += (uint64_t)st.st_size * (gz ? 5u : 1u);           // DNA text deflates to between a fifth and a third
   }
   const size_t ascii = q.batchBases + q.batchBases / 8 + (1u << 20);
-  const size_t full = (packed && !getenv("MASHMAP_HIP_BIG_BUFFERS")) ? (ascii + (2u << 20)) / 8 * 3 + (1u << 20) : ascii;      // locking pages costs ~0.2 s per GB: no more than needed
+  const size_t full = packed ? (ascii + (2u << 20)) / 8 * 3 + (1u << 20) : ascii;      // locking pages costs ~0.2 s per GB: no more than needed
   const size_t inFlight = std::min<size_t>(24, 2 * perPass + 2) + (perPass == 1 ? 4 : 0);   // one batch per pass: as before (reader 1 + two queues of 2 + device 1 + post 1 + one spare)
   if (!q.inputKnown) { q.bufferBytes = full; q.buffers = inFlight; return q; }
   const uint64_t batches = q.inputBytes / q.batchBases + 1;

@@ -15,7 +15,7 @@
 #   fuzz:N           N random command lines through mashmap_hip and the stock binary, PAF bytes compared (MM_FUZZ_SEED)
 #   nosplit          --noSplit on 30 kbp reads through both command lines: same PAF, both times
 #   large            --dense -s 100000 (sketchSize 9 998) and k = 40 / 57 through mashmap_hip and the stock binary, with the stage log
-# Environment variables given on the command line reach every step (A/B switches: MM_*, MASHMAP_HIP_*); MM_BENCH_EXTRA: extra bench.py
+# Environment variables given on the command line reach every step (the switches: INTEGRATION.md, "Environment switches"); MM_BENCH_EXTRA: extra bench.py
 # arguments of the trace steps (e.g. --repeat-rich-reference).
 TAG=${1:-visit}; shift
 OUT=gpurun_out/$TAG
