@@ -31,6 +31,18 @@
 
 namespace skch {
 
+// The device path holds sequence positions as int32 in both builds: a reference or query record longer than this is refused with a
+// message, not truncated (the LARGE_CONTIG build has 64-bit offset_t on the host, and only there)
+constexpr int64_t kDeviceMaxLen = std::numeric_limits<int32_t>::max();
+inline const char* tooLongAdvice() {
+#ifdef LARGE_CONTIG
+  return " bp are not supported: this LARGE_CONTIG build keeps 64-bit positions on the host and in its index files, but the device path"
+         " maps records of at most 2147483647 bp";
+#else
+  return " bp need the reference's LARGE_CONTIG build (64-bit offset_t), which mashmap_hip does not provide";
+#endif
+}
+
 class Sketch {
   const skch::Parameters& param;
   int freqThreshold = std::numeric_limits<int>::max();
@@ -46,6 +58,42 @@ class Sketch {
   [[noreturn]] void die(const char* what) const {
     std::cerr << "[mashmap_hip::skch::Sketch] ERROR: " << what << ": " << mm_last_error(ctx_) << std::endl;
     exit(1);
+  }
+
+  // Host records <-> device records.  In the default build MinmerInfo IS mm_minmer (the library writes and reads the host vectors
+  // directly).  In the LARGE_CONTIG build (offset_t = int64 as in the reference's build of that name) the host holds 32- / 24-byte
+  // records and the device still holds 32-bit positions: records are widened on the way back and narrowed
+  // on the way in, where a position beyond INT32_MAX is refused (it can only come from an index file; FASTA contigs are checked in build)
+  static constexpr bool kWide = sizeof(offset_t) != sizeof(int32_t);
+  template <class Fetch> static void fetchMinmers(std::vector<MinmerInfo>& out, size_t n, Fetch fetch) {
+    out.resize(n);
+    if constexpr (!kWide) fetch(reinterpret_cast<mm_minmer*>(out.data()));
+    else {
+      std::vector<mm_minmer> d(n);
+      fetch(d.data());
+      for (size_t i = 0; i < n; i++) out[i] = MinmerInfo{d[i].hash, d[i].wpos, d[i].wpos_end, d[i].seqId, (strand_t)d[i].strand};
+    }
+  }
+  static int32_t narrowPos(int64_t v, const char* what) {
+    if (v < std::numeric_limits<int32_t>::min() || v > std::numeric_limits<int32_t>::max()) {
+      std::cerr << "[mashmap_hip::skch::Sketch] ERROR: " << what << " holds position " << v << "; the device index holds positions up to "
+                << std::numeric_limits<int32_t>::max() << " only" << std::endl;
+      exit(1);
+    }
+    return (int32_t)v;
+  }
+  // `all` as device records: the same memory in the default build, a narrowed copy in `tmp` with LARGE_CONTIG
+  static const mm_minmer* deviceMinmers(const std::vector<MinmerInfo>& all, std::vector<mm_minmer>& tmp, const char* what) {
+    if constexpr (!kWide) { (void)tmp; (void)what; return reinterpret_cast<const mm_minmer*>(all.data()); }
+    else {
+      tmp.resize(all.size());
+      for (size_t i = 0; i < all.size(); i++) {
+        mm_minmer q; std::memset(&q, 0, sizeof q);
+        q.hash = all[i].hash; q.wpos = narrowPos(all[i].wpos, what); q.wpos_end = narrowPos(all[i].wpos_end, what); q.seqId = all[i].seqId; q.strand = all[i].strand;
+        tmp[i] = q;
+      }
+      return tmp.data();
+    }
   }
 
  public:
@@ -71,8 +119,9 @@ class Sketch {
   }
 
   explicit Sketch(const skch::Parameters& p) : param(p) {
-    static_assert(sizeof(MinmerInfo) == sizeof(mm_minmer), "MinmerInfo layout");
-    static_assert(sizeof(IntervalPoint) == sizeof(mm_interval_point), "IntervalPoint layout");
+    // with LARGE_CONTIG: the 32 / 24 bytes of the reference's records of that build, the layout of its --saveIndex files
+    static_assert(sizeof(MinmerInfo) == (kWide ? 32 : sizeof(mm_minmer)), "MinmerInfo layout");
+    static_assert(sizeof(IntervalPoint) == (kWide ? 24 : sizeof(mm_interval_point)), "IntervalPoint layout");
     mm_params mp;
     mp.kmerSize = p.kmerSize; mp.segLength = p.segLength; mp.sketchSize = p.sketchSize;
     mp.flags = (p.stage1_topANI_filter ? MM_FLAG_HG_FILTER : 0) | (p.skip_self ? MM_FLAG_SKIP_SELF : 0) |
@@ -156,8 +205,9 @@ class Sketch {
   void materializeMinmerIndex() const {
     std::lock_guard<std::mutex> lk(materializeMu_);
     if (minmerIndexReady_) return;
-    minmerIndex.resize(nMinmers_);
-    if (nMinmers_ && mm_index_download(ctx_, reinterpret_cast<mm_minmer*>(minmerIndex.data()), nullptr, nullptr, nullptr, nullptr) != MM_OK) die("mm_index_download");
+    fetchMinmers(minmerIndex, nMinmers_, [this](mm_minmer* p) {
+      if (nMinmers_ && mm_index_download(ctx_, p, nullptr, nullptr, nullptr, nullptr) != MM_OK) die("mm_index_download");
+    });
     minmerIndexReady_ = true;
   }
   size_t minmerIndexSize() const { return nMinmers_; }
@@ -189,8 +239,8 @@ class Sketch {
   void saveIndex() {
     size_t nAll = 0;
     if (mm_index_download_full(ctx_, nullptr, &nAll) != MM_OK) die("mm_index_download_full");
-    std::vector<MinmerInfo> all(nAll);
-    if (mm_index_download_full(ctx_, reinterpret_cast<mm_minmer*>(all.data()), &nAll) != MM_OK) die("mm_index_download_full");
+    std::vector<MinmerInfo> all;
+    fetchMinmers(all, nAll, [this, &nAll](mm_minmer* p) { if (mm_index_download_full(ctx_, p, &nAll) != MM_OK) die("mm_index_download_full"); });
     if (param.saveIndexFilename.extension() == ".tsv") {
       std::ofstream out(param.saveIndexFilename);
       out << "seqId" << "\t" << "strand" << "\t" << "start" << "\t" << "end" << "\t" << "hash\n";
@@ -268,12 +318,13 @@ class Sketch {
       tmp.resize(n);
       in.read((char*)tmp.data(), (std::streamsize)(n * sizeof(IntervalPoint)));
       keys[i] = key; offs[i] = pts.size();
-      for (const auto& ip : tmp) { mm_interval_point q; std::memset(&q, 0, sizeof q); q.pos = ip.pos; q.hash = ip.hash; q.seqId = ip.seqId; q.side = ip.side; pts.push_back(q); }
+      for (const auto& ip : tmp) { mm_interval_point q; std::memset(&q, 0, sizeof q); q.pos = kWide ? narrowPos(ip.pos, fn.c_str()) : (int32_t)ip.pos; q.hash = ip.hash; q.seqId = ip.seqId; q.side = ip.side; pts.push_back(q); }
     }
     offs[nKeys] = pts.size();
     std::vector<int32_t> clen(metadata.size());
-    for (size_t i = 0; i < metadata.size(); i++) clen[i] = metadata[i].len;
-    if (mm_index_upload_full(ctx_, reinterpret_cast<const mm_minmer*>(all.data()), all.size(), keys.data(), offs.data(), nKeys, pts.data(), pts.size(),
+    for (size_t i = 0; i < metadata.size(); i++) clen[i] = (int32_t)metadata[i].len;          // build() refused longer contigs
+    std::vector<mm_minmer> narrow;
+    if (mm_index_upload_full(ctx_, deviceMinmers(all, narrow, param.loadIndexFilename.c_str()), all.size(), keys.data(), offs.data(), nKeys, pts.data(), pts.size(),
                              clen.data(), param.skip_prefix ? groups.data() : nullptr, metadata.size(), param.kmer_pct_threshold) != MM_OK)
       die("mm_index_upload_full");
   }
@@ -297,12 +348,12 @@ class Sketch {
       mmhost::ParsedBatch b;
       while (rd.next(b)) {
         for (size_t r = 0; r < b.size(); r++) {
-          // offset_t is int32 here as in the reference's default build (base_types.hpp:17-22); its -DLARGE_CONTIG variant (int64
-          // coordinates, CMakeLists.txt:23) has no counterpart in the device layouts, so such a contig is refused, not truncated
-          if (b.offs[r + 1] - b.offs[r] > (int64_t)std::numeric_limits<offset_t>::max()) {
+          // offset_t is int32 here as in the reference's default build (base_types.hpp:17-22); with -DLARGE_CONTIG (int64 coordinates,
+          // CMakeLists.txt:23) it is int64 on the host, but the device path holds int32 positions in both builds, so such a contig is
+          // refused, not truncated
+          if (b.offs[r + 1] - b.offs[r] > kDeviceMaxLen) {
             std::cerr << "[mashmap::skch::Sketch::build] ERROR: reference sequence " << b.names[r] << " has " << (b.offs[r + 1] - b.offs[r])
-                      << " bp; contigs of more than " << std::numeric_limits<offset_t>::max()
-                      << " bp need the reference's LARGE_CONTIG build (64-bit offset_t), which mashmap_hip does not provide" << std::endl;
+                      << " bp; contigs of more than " << kDeviceMaxLen << tooLongAdvice() << std::endl;
             exit(1);
           }
           metadata.push_back(ContigInfo{b.names[r], (offset_t)(b.offs[r + 1] - b.offs[r])});

@@ -24,17 +24,21 @@
 namespace skch {
 
 typedef uint64_t hash_t;
-typedef int32_t offset_t;      // base_types.hpp:21 (the LARGE_CONTIG variant is not supported by the device layouts)
+#ifdef LARGE_CONTIG
+typedef int64_t offset_t;      // base_types.hpp:18-19 (the device still holds positions as int32, see skch_sketch.hpp)
+#else
+typedef int32_t offset_t;      // base_types.hpp:21
+#endif
 typedef int32_t seqno_t;
 typedef int16_t strand_t;
 typedef int8_t side_t;
 typedef std::chrono::high_resolution_clock Time;
 
-struct MinmerInfo {            // base_types.hpp:31 (24 bytes, same layout as mm_minmer)
+struct MinmerInfo {            // base_types.hpp:31 (24 bytes, same layout as mm_minmer; 32 bytes with LARGE_CONTIG)
   hash_t hash; offset_t wpos; offset_t wpos_end; seqno_t seqId; strand_t strand;
   bool operator<(const MinmerInfo& x) const { return seqId != x.seqId ? seqId < x.seqId : wpos < x.wpos; }
 };
-struct IntervalPoint {         // base_types.hpp:66 (24 bytes, same layout as mm_interval_point)
+struct IntervalPoint {         // base_types.hpp:66 (24 bytes, same layout as mm_interval_point; pos int64 with LARGE_CONTIG)
   offset_t pos; hash_t hash; seqno_t seqId; side_t side;
   bool operator<(const IntervalPoint& x) const {
     if (seqId != x.seqId) return seqId < x.seqId;
