@@ -40,13 +40,13 @@ k_idx_keys(size_t n, const mm_minmer* __restrict__ rec, uint64_t* __restrict__ h
 // per sorted position j: bit 0 = first record of a run of merged records, bit 32 = first record of its hash
 __global__ void __launch_bounds__(256)
 k_idx_flags(size_t n, const mm_minmer* __restrict__ rec, const uint64_t* __restrict__ sh, const uint32_t* __restrict__ sidx, uint64_t* __restrict__ flags,
-            unsigned long long* __restrict__ diag /* [0] |= 1: sort not stable */) {
+            unsigned long long* __restrict__ diag /* dCounters + MM_CW_INDEX_BUILD */) {
   const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
   bool keyStart = j == 0 || sh[j] != sh[j - 1];
   bool runStart = keyStart;
   if (!keyStart) {
-    if (sidx[j] < sidx[j - 1]) atomicOr(&diag[0], 1ull);                       // records of a hash must stay in minmerIndex order
+    if (sidx[j] < sidx[j - 1]) atomicOr(&diag[MM_IX_BUILD_UNSTABLE], 1ull);                       // records of a hash must stay in minmerIndex order
     runStart = rec[sidx[j - 1]].wpos_end != rec[sidx[j]].wpos;                 // winSketch.hpp:388: back().pos != mi.wpos -> a new OPEN/CLOSE pair
   }
   flags[j] = (runStart ? 1ull : 0ull) | (keyStart ? (1ull << 32) : 0ull);
@@ -134,13 +134,13 @@ k_compact_records(size_t n, const mm_minmer* __restrict__ rec, const int32_t* __
 // flat device index
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
-k_check_records(size_t n, const mm_minmer* __restrict__ rec, int nContigs, unsigned long long* __restrict__ diag /* [1] bad order/position, [2] max length */) {
+k_check_records(size_t n, const mm_minmer* __restrict__ rec, int nContigs, unsigned long long* __restrict__ diag /* dCounters + MM_CW_INDEX_FLATTEN */) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const mm_minmer m = rec[i];
-  if (m.wpos < 0 || m.wpos_end < 0 || m.seqId < 0 || m.seqId >= nContigs || (i && rec[i - 1].seqId > m.seqId)) atomicOr(&diag[1], 1ull);
+  if (m.wpos < 0 || m.wpos_end < 0 || m.seqId < 0 || m.seqId >= nContigs || (i && rec[i - 1].seqId > m.seqId)) atomicOr(&diag[MM_IX_FLAT_BAD_REC], 1ull);
   const long long len = (long long)m.wpos_end - m.wpos;
-  if (len > 0) atomicMax(&diag[2], (unsigned long long)len);
+  if (len > 0) atomicMax(&diag[MM_IX_FLAT_MAX_LEN], (unsigned long long)len);
 }
 // first record of every contig (records are grouped by ascending seqId) and the wpos of its last record
 __global__ void k_contig_ranges(size_t n, const mm_minmer* __restrict__ rec, int nContigs, int64_t* __restrict__ first, int32_t* __restrict__ lastW) {
@@ -237,7 +237,7 @@ k_ht_clear(size_t cap, HtSlot* __restrict__ ht) {
 __global__ void __launch_bounds__(256)
 k_ht_insert(size_t nk, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ keyOff, const uint8_t* __restrict__ freq, HtSlot* __restrict__ ht,
             uint64_t mask, unsigned long long* __restrict__ filter, uint64_t filterMask, uint8_t* __restrict__ tags /* non-null: bucketised placement + tag bytes */,
-            unsigned long long* __restrict__ diag /* [3] |= 1 value overflow, |= 2 duplicate key */) {
+            unsigned long long* __restrict__ diag /* dCounters + MM_CW_INDEX_FLATTEN: MM_IX_FLAT_TABLE |= 1 value overflow, |= 2 duplicate key */) {
   const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= nk) return;
   const uint64_t key = keys[k];
@@ -246,7 +246,7 @@ k_ht_insert(size_t nk, const uint64_t* __restrict__ keys, const uint64_t* __rest
   // a frequent seed is removed from the query sketch before any lookup (getSeedHits, computeMap.hpp:834-837): its point list is never
   // read on the device, so however long it is (satellite arrays) it needs no room in the packed value
   if (f) { off = 0; cnt = 0; }
-  if (cnt >= (1ull << 23) || off >= (1ull << 40)) { atomicOr(&diag[3], 1ull); return; }
+  if (cnt >= (1ull << 23) || off >= (1ull << 40)) { atomicOr(&diag[MM_IX_FLAT_TABLE], 1ull); return; }
   const uint64_t val = (off << 24) | (cnt << 1) | (f ? 1ull : 0ull);
   if (tags) {
     // tagged table: the key goes into the first bucket, from its home bucket on, that still has a free slot (no deletions: the
@@ -258,7 +258,7 @@ k_ht_insert(size_t nk, const uint64_t* __restrict__ keys, const uint64_t* __rest
         const uint64_t slot = b + ((start + i) & (MM_TAG_BUCKET - 1));
         const unsigned long long prev = atomicCAS((unsigned long long*)&ht[slot].key, (unsigned long long)MM_EMPTY, (unsigned long long)key);
         if (prev == MM_EMPTY) { ht[slot].val = val; tags[slot] = (uint8_t)mm_seed_tag(key); return; }
-        if (prev == key) { atomicOr(&diag[3], 2ull); return; }
+        if (prev == key) { atomicOr(&diag[MM_IX_FLAT_TABLE], 2ull); return; }
       }
       b = (b + MM_TAG_BUCKET) & mask;
     }
@@ -267,7 +267,7 @@ k_ht_insert(size_t nk, const uint64_t* __restrict__ keys, const uint64_t* __rest
   while (true) {
     const unsigned long long prev = atomicCAS((unsigned long long*)&ht[slot].key, (unsigned long long)MM_EMPTY, (unsigned long long)key);
     if (prev == MM_EMPTY) { ht[slot].val = val; break; }
-    if (prev == key) { atomicOr(&diag[3], 2ull); break; }
+    if (prev == key) { atomicOr(&diag[MM_IX_FLAT_TABLE], 2ull); break; }
     slot = (slot + 1) & mask;
   }
   if (filterMask) atomicOr(&filter[mm_filter_word(key, filterMask)], (unsigned long long)mm_filter_bits(key));
@@ -320,7 +320,7 @@ int mm_flatten_device_index(mm_ctx* c, const mm_minmer* dRec, size_t n, size_t n
   I.ready = false;
   Tmp T;
   DevBuf& scratch = *T.make();
-  unsigned long long* diag = c->dCounters.as<unsigned long long>() + 20;       // [20..23]
+  unsigned long long* diag = c->dCounters.as<unsigned long long>() + MM_CW_INDEX_FLATTEN;   // MM_IX_FLAT_*
   MM_HIP(c, hipMemsetAsync(diag, 0, 32, c->stream));
   const int nC = (int)nContigs;
   if (n) K_LAUNCH(k_check_records, n, n, dRec, nC, diag);
@@ -332,8 +332,8 @@ int mm_flatten_device_index(mm_ctx* c, const mm_minmer* dRec, size_t n, size_t n
   MM_HIP(c, hipMemcpyAsync(lastW.data(), dLastW.p, nContigs * 4, hipMemcpyDeviceToHost, c->stream));
   MM_HIP(c, hipMemcpyAsync(hd, diag, 32, hipMemcpyDeviceToHost, c->stream));
   MM_HIP(c, hipStreamSynchronize(c->stream));
-  if (hd[1]) { c->err = "mm_index_upload: minmerIndex is not grouped by ascending seqId, or holds a negative position / unknown seqId"; return MM_ERR_ARG; }
-  const int maxLen = (int)hd[2];
+  if (hd[MM_IX_FLAT_BAD_REC]) { c->err = "mm_index_upload: minmerIndex is not grouped by ascending seqId, or holds a negative position / unknown seqId"; return MM_ERR_ARG; }
+  const int maxLen = (int)hd[MM_IX_FLAT_MAX_LEN];
   // ---- event stream
   const size_t nEv = 2 * n;
   MM_HIP(c, I.evKey.ensure(nEv * 4 + 256)); MM_HIP(c, I.evAux.ensure(nEv * 4 + 256)); MM_HIP(c, I.evHash.ensure(nEv * 8 + 512));
@@ -409,8 +409,8 @@ int mm_flatten_device_index(mm_ctx* c, const mm_minmer* dRec, size_t n, size_t n
   MM_HIP(c, hipMemcpyAsync(I.refGroup.p, grp.data(), nContigs * 4, hipMemcpyHostToDevice, c->stream));
   MM_HIP(c, hipMemcpyAsync(hd, diag, 32, hipMemcpyDeviceToHost, c->stream));
   MM_HIP(c, hipStreamSynchronize(c->stream));
-  if (hd[3] & 1ull) { c->err = "mm_index_upload: a non-frequent seed with 2^23 or more interval points (or 2^40 points in total) does not fit the packed table value"; return MM_ERR_ARG; }
-  if (hd[3] & 2ull) { c->err = "mm_index_upload: duplicate key"; return MM_ERR_ARG; }
+  if (hd[MM_IX_FLAT_TABLE] & 1ull) { c->err = "mm_index_upload: a non-frequent seed with 2^23 or more interval points (or 2^40 points in total) does not fit the packed table value"; return MM_ERR_ARG; }
+  if (hd[MM_IX_FLAT_TABLE] & 2ull) { c->err = "mm_index_upload: duplicate key"; return MM_ERR_ARG; }
   I.filterMask = fbits ? fbits / 64 - 1 : 0;                                   // word mask
   I.nRec = n; I.nKeys = nk; I.nPoints = np; I.nContigs = nContigs; I.htCap = cap; I.nOpen = (size_t)nOpen; I.ready = true;
   return MM_OK;
@@ -428,8 +428,8 @@ int mm_finalize_index_device(mm_ctx* c, const std::vector<std::pair<const mm_min
   Tmp T;
   DevBuf& scratch = *T.make();
   DevBuf& dAll = *T.make();
-  MM_HIP(c, c->dCounters.ensure(256));
-  unsigned long long* diag = c->dCounters.as<unsigned long long>() + 16;       // [16] sort check, [17] nFreq, [18] list cursor, [19] threshold
+  MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
+  unsigned long long* diag = c->dCounters.as<unsigned long long>() + MM_CW_INDEX_BUILD;   // MM_IX_BUILD_*
   MM_HIP(c, hipMemsetAsync(diag, 0, 32, c->stream));
   MM_HIP(c, dAll.ensure(nAll * sizeof(mm_minmer) + 64));
   {
@@ -489,19 +489,19 @@ int mm_finalize_index_device(mm_ctx* c, const std::vector<std::pair<const mm_min
     MM_HIP(c, rocprim::radix_sort_keys(scratch.p, bytes, c0.as<uint32_t>(), c1.as<uint32_t>(), nk, 0u, 32u, c->stream));
     const int64_t total = (int64_t)nk;
     const int64_t toIgnore = (int64_t)(total * kmerPctThreshold / 100);        // int64 * float / int, as winSketch.hpp:425
-    int32_t* dThr = (int32_t*)(diag + 3);
+    int32_t* dThr = (int32_t*)(diag + MM_IX_BUILD_THRESHOLD);
     hipLaunchKernelGGL(k_freq_threshold, dim3(1), dim3(64), 0, c->stream, nk, c1.as<uint32_t>(), (unsigned long long)(toIgnore < 0 ? 0 : toIgnore), dThr);
-    K_LAUNCH(k_key_freq, nk, nk, I.keyOff.as<uint64_t>(), dThr, I.keyFreq.as<uint8_t>(), diag + 1);
+    K_LAUNCH(k_key_freq, nk, nk, I.keyOff.as<uint64_t>(), dThr, I.keyFreq.as<uint8_t>(), diag + MM_IX_BUILD_NFREQ);
     unsigned long long hd[4];
     MM_HIP(c, hipMemcpyAsync(hd, diag, 32, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipStreamSynchronize(c->stream));
-    if (hd[0] & 1ull) { c->err = "mm_index_build: the device sort did not keep the records of a hash in minmerIndex order"; return MM_ERR_STATE; }
-    std::memcpy(&freqThreshold, &hd[3], 4);
-    const size_t nFreq = (size_t)hd[1];
+    if (hd[MM_IX_BUILD_UNSTABLE] & 1ull) { c->err = "mm_index_build: the device sort did not keep the records of a hash in minmerIndex order"; return MM_ERR_STATE; }
+    std::memcpy(&freqThreshold, &hd[MM_IX_BUILD_THRESHOLD], 4);
+    const size_t nFreq = (size_t)hd[MM_IX_BUILD_NFREQ];
     if (nFreq) {
       DevBuf& fl = *T.make();
       MM_HIP(c, fl.ensure(nFreq * 8));
-      K_LAUNCH(k_freq_list, nk, nk, I.keys.as<uint64_t>(), I.keyFreq.as<uint8_t>(), fl.as<uint64_t>(), diag + 2);
+      K_LAUNCH(k_freq_list, nk, nk, I.keys.as<uint64_t>(), I.keyFreq.as<uint8_t>(), fl.as<uint64_t>(), diag + MM_IX_BUILD_CURSOR);
       c->hFreq.resize(nFreq);
       MM_HIP(c, hipMemcpyAsync(c->hFreq.data(), fl.p, nFreq * 8, hipMemcpyDeviceToHost, c->stream));
       // dropFreqSeedSet: minmerIndex without the frequent hashes, order kept

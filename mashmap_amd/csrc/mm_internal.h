@@ -82,6 +82,91 @@ struct DeviceIndex {
   bool ready = false;
 };
 
+// ---------------------------------------------------------------------------------------------
+// mm_ctx::dCounters: ONE block of MM_CW_WORDS 64-bit words that the sketch launcher, the index build and every stage of a mapping
+// pass count in.  MM_CW_*: word indexes from the start of the block -- where each part begins (and, *_END, the word behind it).
+// The words inside a part are named relative to the part's first word, because that is the pointer the kernels are handed:
+// MM_PC_* under MM_CW_PASS, MM_MC_* under MM_CW_MAP, MM_SL_* (32-bit) under MM_CW_SORT_LENS, MM_IX_* under MM_CW_INDEX_*.
+// ---------------------------------------------------------------------------------------------
+enum : int {
+  MM_CW_SKETCH        = 0,    //  0..7  the sketch launcher's (reset by it before its kernels).  In use: the low 32 bits of word 0, the
+  MM_CW_SKETCH_END    = 8,    //        length of the hard list, which the sketch kernels take as a uint32_t* to the start of the block
+  MM_CW_PASS          = 8,    //  8..   the mapping pass: `counters` of its kernels, `cnt` of its launchers, `passCnt` of k_l2_select (MM_PC_*)
+  MM_CW_PASS_END      = 16,   //        ... the words a stage reads back in one copy (MM_PC_READ of them)
+  MM_CW_SORT_LENS     = 16,   // 16..17 mapping pass, as 32-bit words: the lengths of the point path's lists (MM_SL_*)
+  MM_CW_SORT_LENS_END = 18,
+  MM_CW_INDEX_BUILD   = 16,   // 16..19 index build only (mm_finalize_index_device): MM_IX_BUILD_*
+  MM_CW_INDEX_FLATTEN = 20,   // 20..23 index build only (mm_flatten_device_index): MM_IX_FLAT_*
+  MM_CW_INDEX_END     = 24,
+  MM_CW_MID_LEN       = 24,   // 24     mapping pass: fragments on k_lookup_mid's list (MM_PC_MID_LEN from MM_CW_PASS) ...
+  MM_CW_SKETCH_PHASES = 24,   // 24..31 ... and, under MM_SKETCH_STATS, the sketch kernel's phase cycles (read and printed by the sketch launcher
+  MM_CW_SKETCH_PHASES_END = 32, //      before the pass resets them); word 24 is also the sink of k_hash_only, which never stores to it
+  MM_CW_MAP           = 32,   // 32..39 mapping pass: what a steady-state pass reports besides MM_CW_PASS (MM_MC_*); `result` of k_l2_select
+  MM_CW_MAP_END       = 40,
+  MM_CW_HARD_COPY     = 48,   // 48     copy of word MM_CW_SKETCH (the hard-list length), taken before the pass resets [0, MM_CW_MAP)
+  MM_CW_WORDS         = 64
+};
+#define MM_COUNTER_BYTES ((size_t)MM_CW_WORDS * 8)   // every ensure() of dCounters, and the page-locked mirror mm_ctx::hPass
+
+// Words of the mapping pass, relative to MM_CW_PASS.  Two of them are used twice, by stages that do not overlap in time: the L2 sweep
+// launcher resets them when the L1 stage is done with them.  A steady-state pass reads the block back once, at its end, and so sees
+// the L2 sweep's values there: it cannot report how many fragments went through the HBM point path, and mm_ctx::lastBig repeats the
+// figure of the last sized pass (prevBig) instead.
+enum : int {
+  MM_PC_POINT_CURSOR   = 0,   // L1 stage: interval points handed out in dPts
+  MM_PC_L2_EXACT_LEN   = 0,   // L2 sweep: candidates on the list of k_l2_sweep_exact (dL2Exact)
+  MM_PC_POINT_OVERFLOW = 1,   // the interval-point buffer overflowed
+  MM_PC_L1_CAND        = 2,   // L1 candidates: the fused ones after k_l1_regions, all of them after the sweeps (their cursor behind the fused ones)
+  MM_PC_L1_OVERFLOW    = 3,   // the L1 candidate buffer (a region of it, or the dense buffer) overflowed
+  MM_PC_L2_LOCI        = 4,   // L2 locus cursor
+  MM_PC_L2_OVERFLOW    = 5,   // the L2 locus buffer overflowed
+  MM_PC_L2_FLAGS       = 6,   // MM_L2F_* bits
+  MM_PC_BIG_LEN        = 7,   // L1 stage: fragments queued for the HBM point path (dBigList)
+  MM_PC_L2_WIDE_LEN    = 7,   // L2 sweep: candidates on the list of the 16-bit-cell sweep (dL2Wide)
+  MM_PC_READ           = MM_CW_PASS_END - MM_CW_PASS,
+  MM_PC_MID_LEN        = MM_CW_MID_LEN - MM_CW_PASS
+};
+constexpr unsigned long long MM_OVERFLOWED = 1ull;   // what the kernels raise an overflow word to
+// bits of MM_PC_L2_FLAGS; any of them set in a steady-state pass has it redone the sized way
+constexpr unsigned long long MM_L2F_SLOTS  = 1ull;   // a candidate has more tied loci than the staging slots per candidate (the sized pass doubles them)
+constexpr unsigned long long MM_L2F_STREAM = 4ull;   // a stream outgrew the reservation k_l2_extents made for it
+constexpr unsigned long long MM_L2F_OPS    = 8ull;   // steady-state pass: the streams do not fit dL2Ops as it is
+constexpr unsigned long long MM_L2F_LIST   = 16ull;  // steady-state pass: the wide / exact list is longer than the launch covers
+constexpr unsigned long long MM_L2F_CANDS  = 32ull;  // steady-state pass: more candidates than the buffers of this pass hold
+// "some stage before this one ran out of room": asked by k_l2_select on the device and by map_pass on the host, of the same words
+__host__ __device__ inline bool mm_pass_incomplete(const unsigned long long* pc) {
+  return (pc[MM_PC_POINT_OVERFLOW] | pc[MM_PC_L1_OVERFLOW] | pc[MM_PC_L2_OVERFLOW] | pc[MM_PC_L2_FLAGS]) != 0;
+}
+enum : int {                  // relative to MM_CW_MAP
+  MM_MC_MAPPINGS = 0,         // candidate mappings k_l2_select<true> found
+  MM_MC_OVERFLOW = 1,         // ... more than dMappings holds
+  MM_MC_L2_OPS   = 2          // L2 stream entries reserved (copied here by the L2 launcher)
+};
+enum : int {                  // 32-bit words relative to MM_CW_SORT_LENS
+  MM_SL_BLOCK   = 0,          // list of k_sort_points_block (listB of k_classify_sort)
+  MM_SL_GLOBAL  = 1,          // list of k_sort_points_global (listC)
+  MM_SL_LITERAL = 2,          // the fragments k_l1_stream leaves for k_l1_sweep (a word of its own: the two above still feed the sorters in flight)
+  MM_SL_END     = 4
+};
+enum : int {                  // index build diagnostics, relative to MM_CW_INDEX_BUILD / MM_CW_INDEX_FLATTEN
+  MM_IX_BUILD_UNSTABLE = 0,   // |= 1: the sort did not keep the records of a hash in minmerIndex order
+  MM_IX_BUILD_NFREQ    = 1,   // frequent keys
+  MM_IX_BUILD_CURSOR   = 2,   // cursor of the frequent-key list
+  MM_IX_BUILD_THRESHOLD = 3,  // int32: the frequency threshold
+  MM_IX_FLAT_BAD_REC   = 1,   // a record out of order or with a bad position
+  MM_IX_FLAT_MAX_LEN   = 2,   // longest window
+  MM_IX_FLAT_TABLE     = 3    // |= 1 value overflow, |= 2 duplicate key
+};
+static_assert(MM_CW_SKETCH_END <= MM_CW_PASS && MM_CW_PASS_END <= MM_CW_SORT_LENS && MM_CW_SORT_LENS_END <= MM_CW_MID_LEN, "mapping pass: parts overlap");
+static_assert(MM_CW_SORT_LENS * 2 + MM_SL_END <= MM_CW_SORT_LENS_END * 2, "the 32-bit list lengths outgrow their words");
+static_assert(MM_CW_MID_LEN < MM_CW_MAP && MM_CW_MAP + MM_MC_L2_OPS < MM_CW_MAP_END && MM_CW_MAP_END <= MM_CW_HARD_COPY && MM_CW_HARD_COPY < MM_CW_WORDS, "mapping pass: parts overlap");
+static_assert(MM_CW_INDEX_BUILD + 4 == MM_CW_INDEX_FLATTEN && MM_CW_INDEX_FLATTEN + 4 == MM_CW_INDEX_END && MM_CW_SKETCH_END <= MM_CW_INDEX_BUILD, "index build: parts overlap");
+static_assert(MM_CW_SKETCH_PHASES >= MM_CW_INDEX_END && MM_CW_SKETCH_PHASES_END <= MM_CW_MAP, "the sketch statistics must stay clear of the words that outlive the sketch launcher");
+static_assert(MM_PC_POINT_CURSOR == MM_PC_L2_EXACT_LEN && MM_PC_BIG_LEN == MM_PC_L2_WIDE_LEN, "the words shared by the L1 stage and the L2 sweep");
+static_assert(MM_CW_PASS + MM_PC_MID_LEN == MM_CW_SKETCH_PHASES, "k_lookup_mid's list length shares its word with the sketch statistics");
+static_assert(MM_PC_L2_LOCI + 1 == MM_PC_L2_OVERFLOW && MM_PC_L2_OVERFLOW + 1 == MM_PC_L2_FLAGS && MM_PC_L2_FLAGS < MM_PC_READ, "the L2 words are reset as one range");
+static_assert(MM_PC_L1_CAND + 1 == MM_PC_L1_OVERFLOW, "the L1 cursor and its flag are read back as one range");
+
 // The device library's environment switches ("Environment switches"), read once per context by mm_create: a switch
 // set after a context was created does not reach it
 struct mm_env {
@@ -170,7 +255,7 @@ struct mm_ctx {
   bool sketched = false, mapped = false;
   // steady state: the previous pass of this context went through and left every buffer sized (mm_launch_map); what it saw
   bool steadyOk = false, lastSteady = false; size_t prevBig = 0, candCap = 0, l2Chunks = 1, sizedFrags = 0; int prevLocap = 0, steadyFails = 0;   // sizedFrags: fragments of the last sized pass
-  unsigned long long* hPass = nullptr;                  // page-locked: the counters of a pass as read back at its end
+  unsigned long long* hPass = nullptr;                  // page-locked mirror of dCounters (MM_COUNTER_BYTES, word for word): the parts a pass reads back at its end
   size_t lastHard = 0;                                  // fragments the fast sketch kernel handed to the hard list in the last pass
   size_t prevMid = 0, lastMid = 0; bool midKnown = false;   // fragments k_lookup_mid took in the last sized pass (its grid in the steady-state passes behind it)
   size_t lastOps = 0, lastBig = 0;                      // L2 stream entries reserved / fragments queued for the HBM point path in the last pass
@@ -197,6 +282,8 @@ struct mm_ctx {
       return MM_ERR_DEVICE;                                                                      \
     }                                                                                            \
   } while (0)
+// a host synchronisation of a mapping pass: counted (mm_pass_syncs)
+#define MM_SYNC(c) do { MM_HIP(c, hipStreamSynchronize((c)->stream)); (c)->nSyncs++; } while (0)
 
 // RAII hipEvent bracket on the ctx stream.  The two events are only RECORDED here (a pair out of a pool that grows with the number of
 // brackets in flight); their times are read by mm_profile_collect once the stream has been synchronised anyway -- measuring a pass does
@@ -267,7 +354,7 @@ int mm_launch_map(mm_ctx* c);
 #define MM_PASS_REDO 1
 int mm_launch_select(mm_ctx* c, bool steady = false);
 void mm_comm_release(mm_ctx* c);
-int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady = false);   // cnt: device counters [2] candidates [4] cursor [5] overflow [6] flags
+int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady = false);   // cnt: dCounters + MM_CW_PASS (MM_PC_*)
 int mm_build_device_index(mm_ctx* c, const int32_t* contigLen, const int32_t* refGroup, size_t nContigs);   // from the host mirrors
 int mm_flatten_device_index(mm_ctx* c, const mm_minmer* dRec, size_t n, size_t nk, size_t np, const int32_t* contigLen, const int32_t* refGroup, size_t nContigs);
 int mm_finalize_index_device(mm_ctx* c, const std::vector<std::pair<const mm_minmer*, size_t>>& parts, float kmerPctThreshold, const int32_t* contigLen,

@@ -74,11 +74,11 @@ __global__ void __launch_bounds__(256)
 k_l2_extents(int nCand, int segLength, int deltaBits, const mm_l1_candidate* __restrict__ l1, const mm_frag_stats* __restrict__ stats, const uint32_t* __restrict__ evKey,
              const int64_t* __restrict__ contigBlock, const int64_t* __restrict__ blockOff,
              const int64_t* __restrict__ evBlock, L2Info* __restrict__ info, int32_t* __restrict__ cnt, const unsigned long long* __restrict__ nDev,
-             unsigned long long* __restrict__ counters /* [6] |= 32: more candidates than the buffers of this (steady-state) pass hold */) {
+             unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS: MM_L2F_CANDS */) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (nDev) {                                                     // steady state: the launch covers the buffers' capacity, the count is on the device
     const long long n = (long long)*nDev;
-    if (c == 0 && n > nCand) atomicOr(&counters[6], 32ull);
+    if (c == 0 && n > nCand) atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_CANDS);
     if (c >= n) { if (c < nCand) { cnt[c] = 0; info[c].e0 = 0; } return; }
   }
   if (c >= nCand) return;
@@ -168,8 +168,8 @@ k_scan_add(int64_t n, int64_t* __restrict__ out, const int64_t* __restrict__ til
 // steady-state passes: the streams' total (the scan's last word) against the buffer as the previous pass left it; a batch that does not
 // fit is flagged and its candidate count zeroed, so that the kernels behind this one do nothing (the pass is then redone with the
 // host's sizing)
-__global__ void k_l2_gate(const int64_t* __restrict__ total, int64_t opsCap, unsigned long long* __restrict__ counters /* [2] candidates, [6] |= 8 */) {
-  if (*total > opsCap) { counters[6] |= 8ull; counters[2] = 0ull; }
+__global__ void k_l2_gate(const int64_t* __restrict__ total, int64_t opsCap, unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS */) {
+  if (*total > opsCap) { counters[MM_PC_L2_FLAGS] |= MM_L2F_OPS; counters[MM_PC_L1_CAND] = 0ull; }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -205,7 +205,7 @@ k_l2_locate(int cBase, int nCand, int64_t opsBase, int s, int NB, const mm_l1_ca
             const uint32_t* __restrict__ opKey, const uint32_t* __restrict__ opAux, const uint64_t* __restrict__ opHash,
             const int64_t* __restrict__ contigOff, const L2Info* __restrict__ info, const int64_t* __restrict__ opOff,
             const int32_t* __restrict__ opCnt, uint32_t* __restrict__ ops, const int32_t* __restrict__ order /* candidates in reference order, or null */,
-            unsigned long long* __restrict__ counters /* [6] |= 4: a stream outgrew its reservation */,
+            unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS: MM_L2F_STREAM */,
             const unsigned long long* __restrict__ nDev, uint16_t* __restrict__ initCells, L2Init* __restrict__ initState, int initStride, int preLimit) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;   // (readfirstlane: the candidate's extents then live in scalar registers)
@@ -416,7 +416,7 @@ k_l2_locate(int cBase, int nCand, int64_t opsBase, int s, int NB, const mm_l1_ca
       if (at < cap) out[at] = (1u << E_END_BIT) | (delta << EF<JB>::DELTA_SHIFT);
       else tooWide = true;                                         // cannot happen: the reservation covers every event + skips
     }
-    if (mm_ballot(tooWide) && lane == 0) atomicOr(&counters[6], 4ull);
+    if (mm_ballot(tooWide) && lane == 0) atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_STREAM);
     // ---- the state after the pre-load, in closed form (see L2Init): pivot = number of cells p with count(1) + .. + count(p) <= S (the sums
     // grow with p), pivRank = that sum at the pivot, shared / votes over the active cells up to it
     __threadfence_block();
@@ -470,7 +470,7 @@ k_l2_sweep(int cBase, int nCand, int64_t opsBase, const int32_t* __restrict__ ca
            const int64_t* __restrict__ opOff, const int32_t* __restrict__ opCnt, const uint32_t* __restrict__ ops,
            const int64_t* __restrict__ l1Off, L2Tmp* __restrict__ tmp, int locap, mm_l2_locus* __restrict__ l2, unsigned long long l2Cap,
            int32_t* __restrict__ wideList, int32_t* __restrict__ exactList, int64_t* __restrict__ l2First, int32_t* __restrict__ l2Num,
-           unsigned long long* __restrict__ counters /* [0] candidates queued for the exact pass, [4] l2 cursor, [5] overflow, [6] flags, [7] queued for the wide pass */,
+           unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS: the L2 words and the two lists' lengths */,
            const unsigned long long* __restrict__ nDev /* non-null: the number of candidates (minus cBase) or of list entries lives there */, int listCap,
            const uint16_t* __restrict__ initCells, const L2Init* __restrict__ initState, int initStride, int initBase /* rows of the chunk: candidate - initBase */) {
   typedef typename std::conditional<WIDE, uint16_t, uint8_t>::type CellT;
@@ -485,7 +485,7 @@ k_l2_sweep(int cBase, int nCand, int64_t opsBase, const int32_t* __restrict__ ca
   const int li = blockIdx.x * LPW + lane;
   if (nDev) {
     const long long nd = (long long)*nDev - (listCap ? 0 : cBase);
-    if (listCap && nd > listCap && li == 0) atomicOr(&counters[6], 16ull);   // more listed candidates than this launch covers: the pass is redone with the host's sizing
+    if (listCap && nd > listCap && li == 0) atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_LIST);   // more listed candidates than this launch covers: the pass is redone with the host's sizing
     nCand = (int)(nd < (listCap ? listCap : nCand) ? nd : (listCap ? listCap : nCand));
   }
   const bool live = lane < LPW && li < nCand;          // (the other lanes of the wave only help with the initial state)
@@ -651,14 +651,14 @@ k_l2_sweep(int cBase, int nCand, int64_t opsBase, const int32_t* __restrict__ ca
   int total = nFlushed + (havePend ? 1 : 0);
   if (cntOverflow) {
     total = 0;
-    if (WIDE) exactList[atomicAdd(&counters[0], 1ull)] = cIdx;   // > 4094 open reference-only hashes between two query hashes: the literal kernel counts in 32 bits
-    else wideList[atomicAdd(&counters[7], 1ull)] = cIdx;
+    if (WIDE) exactList[atomicAdd(&counters[MM_PC_L2_EXACT_LEN], 1ull)] = cIdx;   // > 4094 open reference-only hashes between two query hashes: the literal kernel counts in 32 bits
+    else wideList[atomicAdd(&counters[MM_PC_L2_WIDE_LEN], 1ull)] = cIdx;
   }
   if (doubleOpen && !cntOverflow) {                    // a query hash with two reference windows open at once: the 2-bit vote cell cannot hold it;
     total = 0; slotOverflow = false;                   // the candidate is redone by k_l2_sweep_exact
-    exactList[atomicAdd(&counters[0], 1ull)] = cIdx;
+    exactList[atomicAdd(&counters[MM_PC_L2_EXACT_LEN], 1ull)] = cIdx;
   }
-  if (slotOverflow && !cntOverflow) { atomicOr(&counters[6], 1ull); total = 0; }
+  if (slotOverflow && !cntOverflow) { atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_SLOTS); total = 0; }
   // one reservation per wave (64 candidates): exclusive scan of the lanes' counts, lane 63 of the active lanes asks
   int incl = total;
 #pragma unroll
@@ -667,9 +667,9 @@ k_l2_sweep(int cBase, int nCand, int64_t opsBase, const int32_t* __restrict__ ca
   const int lastLane = 63 - __builtin_clzll(activeMask);
   const int waveTotal = __shfl(incl, lastLane);
   unsigned long long wbase = 0;
-  if (lane == lastLane && waveTotal > 0) wbase = atomicAdd(&counters[4], (unsigned long long)waveTotal);
+  if (lane == lastLane && waveTotal > 0) wbase = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)waveTotal);
   wbase = ((unsigned long long)(uint32_t)__shfl((int)(wbase >> 32), lastLane) << 32) | (uint32_t)__shfl((int)(uint32_t)wbase, lastLane);
-  if (waveTotal > 0 && wbase + (unsigned long long)waveTotal > l2Cap) { if (lane == lastLane) atomicOr(&counters[5], 1ull); return; }
+  if (waveTotal > 0 && wbase + (unsigned long long)waveTotal > l2Cap) { if (lane == lastLane) atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); return; }
   l2First[cIdx] = (int64_t)(wbase + (unsigned long long)(incl - total)); l2Num[cIdx] = total;   // where k_l2_select finds this candidate's loci
   if (total > 0) {
     const unsigned long long base = wbase + (unsigned long long)(incl - total);
@@ -706,7 +706,7 @@ k_l2_sweep_exact(int jb, int nList, int64_t opsBase, const int32_t* __restrict__
   const int li = blockIdx.x * 64 + threadIdx.x;
   if (nDev) {                                          // steady state: the launch covers nList entries, the list's length is on the device
     const long long nd = (long long)*nDev;
-    if (nd > nList && li == 0) atomicOr(&counters[6], 16ull);
+    if (nd > nList && li == 0) atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_LIST);
     if (nd < nList) nList = (int)nd;
   }
   if (li >= nList) return;
@@ -822,11 +822,11 @@ k_l2_sweep_exact(int jb, int nList, int64_t opsBase, const int32_t* __restrict__
   }
   if (inRun) close_run(votes >= 0 ? 1 : -1);
   int total = nFlushed + (havePend ? 1 : 0);
-  if (slotOverflow) { atomicOr(&counters[6], 1ull); total = 0; }
+  if (slotOverflow) { atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_SLOTS); total = 0; }
   unsigned long long base = 0;
   if (total > 0) {
-    base = atomicAdd(&counters[4], (unsigned long long)total);
-    if (base + (unsigned long long)total > l2Cap) { atomicOr(&counters[5], 1ull); return; }
+    base = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
+    if (base + (unsigned long long)total > l2Cap) { atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); return; }
   }
   l2First[cIdx] = (int64_t)base; l2Num[cIdx] = total;
   const int candLocal = (int)(cIdx - l1Off[f]);
@@ -1003,11 +1003,11 @@ k_l2_window(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__
   }
   if (inRun) close_run(votes >= 0 ? 1 : -1);
   int total = nFlushed + (havePend ? 1 : 0);
-  if (slotOverflow) { atomicOr(&counters[6], 1ull); total = 0; }
+  if (slotOverflow) { atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_SLOTS); total = 0; }
   unsigned long long base = 0;
   if (total > 0) {
-    base = atomicAdd(&counters[4], (unsigned long long)total);
-    if (base + (unsigned long long)total > l2Cap) { atomicOr(&counters[5], 1ull); return; }
+    base = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
+    if (base + (unsigned long long)total > l2Cap) { atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); return; }
   }
   l2First[c] = (int64_t)base; l2Num[c] = total;
   const int candLocal = (int)(c - l1Off[f]);
@@ -1018,6 +1018,16 @@ k_l2_window(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__
     o.meanOptimalPos = (t.start + t.end) / 2; o.sharedSketchSize = t.shared; o.strand = t.strand;
     l2[base + k] = o;
   }
+}
+
+// the end of a sized L2 stage: the counters as last read back (MM_PC_*) become the number of loci, or the reason there is none
+// (MM_L2F_STREAM is raised by k_l2_locate alone: the literal launcher never sees it)
+static int mm_l2_verdict(mm_ctx* c, const unsigned long long* hc) {
+  if (hc[MM_PC_L2_FLAGS] & MM_L2F_STREAM) { c->err = "internal: an L2 stream outgrew the reservation k_l2_extents made for it"; return MM_ERR_CAPACITY; }
+  if (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) { c->err = "an L1 candidate with more tied L2 loci than 64 GiB of staging can hold"; return MM_ERR_CAPACITY; }
+  if (hc[MM_PC_L2_OVERFLOW]) { c->err = "L2 locus buffer overflow"; return MM_ERR_CAPACITY; }
+  c->nL2 = (size_t)hc[MM_PC_L2_LOCI];
+  return MM_OK;
 }
 
 static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
@@ -1041,12 +1051,12 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
   MM_HIP(c, c->dWinHeap.ensure((size_t)totH * 4 + 64)); MM_HIP(c, c->dWinKeys.ensure((size_t)totT * 8 + 64)); MM_HIP(c, c->dWinVals.ensure((size_t)totT * 4 + 64));
   MM_HIP(c, c->dL2Cells.ensure((size_t)nC * (size_t)(s + 1) * sizeof(ExactCell) + 64));
   if (c->l2Cap < c->nL1 * 2 + 1024) c->l2Cap = c->nL1 * 2 + 1024;
-  unsigned long long hc[8];
+  unsigned long long hc[MM_PC_READ];
   int locap = MM_LOCAP0;
   for (int attempt = 0; attempt < 24; attempt++) {
     MM_HIP(c, c->dL2.ensure(c->l2Cap * sizeof(mm_l2_locus) + 64));
     MM_HIP(c, c->dL2Tmp.ensure((size_t)nC * locap * sizeof(L2Tmp) + 64));
-    MM_HIP(c, hipMemsetAsync(cnt + 4, 0, 24, c->stream));
+    MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow, flags
     {
       KernelTimer t(c, MM_K_L2);
       hipLaunchKernelGGL(k_l2_window, dim3((nC + 63) / 64), dim3(64), 0, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
@@ -1057,16 +1067,13 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
                          (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt);
       MM_HIP(c, hipGetLastError());
     }
-    MM_HIP(c, hipMemcpyAsync(hc, cnt, 64, hipMemcpyDeviceToHost, c->stream));
+    MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipStreamSynchronize(c->stream));
-    if (hc[6] & 1ull) { if ((size_t)nC * (size_t)locap * 2 * sizeof(L2Tmp) > ((size_t)64 << 30)) break; locap *= 2; continue; }
-    if (hc[5]) { const size_t need = mm_scaled(c, (size_t)hc[4], sizeof(mm_l2_locus)); c->l2Cap = need + need / 8 + 1024; continue; }
+    if (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) { if ((size_t)nC * (size_t)locap * 2 * sizeof(L2Tmp) > ((size_t)64 << 30)) break; locap *= 2; continue; }
+    if (hc[MM_PC_L2_OVERFLOW]) { const size_t need = mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus)); c->l2Cap = need + need / 8 + 1024; continue; }
     break;
   }
-  if (hc[6] & 1ull) { c->err = "an L1 candidate with more tied L2 loci than 64 GiB of staging can hold"; return MM_ERR_CAPACITY; }
-  if (hc[5]) { c->err = "L2 locus buffer overflow"; return MM_ERR_CAPACITY; }
-  c->nL2 = (size_t)hc[4];
-  return MM_OK;
+  return mm_l2_verdict(c, hc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1091,7 +1098,6 @@ int mm_scan_i32_to_i64(mm_ctx* c, int64_t n, const int32_t* dIn, int64_t* dOut, 
   return MM_OK;
 }
 
-#define MM_SYNC(c) do { MM_HIP(c, hipStreamSynchronize((c)->stream)); (c)->nSyncs++; } while (0)
 #define MM_WIDE_CAP 4096     // steady-state passes: candidates the 16-bit re-run / the exact kernel are launched for without knowing their number
 #define MM_EXACT_CAP 1024
 
@@ -1100,16 +1106,16 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
   const DeviceIndex& I = c->idx;
   const int s = c->P.sketchSize;
   // sized pass: the candidates are counted (c->nL1) and the candidate-indexed buffers get an eighth of head room, which is what a
-  // steady-state pass (count on the device: cnt[2]) launches against
+  // steady-state pass (count on the device: MM_PC_L1_CAND) launches against
   if (!steady) { const size_t n1 = mm_scaled(c, c->nL1, 96 + 2 * (size_t)((c->P.sketchSize + 3) & ~1)); c->candCap = n1 + n1 / 8 + 1024; }
   const int nC = steady ? (int)c->candCap : (int)c->nL1;              // candidates the launches cover
   const int nCbuf = (int)c->candCap;
-  const unsigned long long* nDev = steady ? cnt + 2 : nullptr;
+  const unsigned long long* nDev = steady ? cnt + MM_PC_L1_CAND : nullptr;
   const int JB = mm_l2_jb(s);                                              // width of the stream entries' sketch-position field
   MM_HIP(c, c->dL2Info.ensure((size_t)nCbuf * sizeof(L2Info) + 64));
   MM_HIP(c, c->dL2Cnt.ensure((size_t)nCbuf * 4 + 64));
   MM_HIP(c, c->dL2Off.ensure((size_t)nCbuf * 8 + 64));
-  MM_HIP(c, hipMemsetAsync(cnt + 4, 0, 24, c->stream));
+  MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow, flags
   int64_t totalOps = 0;
   {
     KernelTimer t(c, MM_K_L2_LOCATE);
@@ -1120,7 +1126,7 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
     if (steady) {
       const int64_t* dTotal = nullptr;
       const int rc = mm_scan_i32_to_i64_dev(c, nC, c->dL2Cnt.as<int32_t>(), c->dL2Off.as<int64_t>(), &dTotal); if (rc != MM_OK) return rc;
-      MM_HIP(c, hipMemcpyAsync(c->dCounters.as<unsigned long long>() + 34, dTotal, 8, hipMemcpyDeviceToDevice, c->stream));   // read back with the pass's counters
+      MM_HIP(c, hipMemcpyAsync(c->dCounters.as<unsigned long long>() + MM_CW_MAP + MM_MC_L2_OPS, dTotal, 8, hipMemcpyDeviceToDevice, c->stream));   // read back with the pass's counters
       hipLaunchKernelGGL(k_l2_gate, dim3(1), dim3(1), 0, c->stream, dTotal, (int64_t)(c->dL2Ops.bytes / 4) - 64, cnt);
       MM_HIP(c, hipGetLastError());
     } else { const int rc = mm_scan_i32_to_i64(c, nC, c->dL2Cnt.as<int32_t>(), c->dL2Off.as<int64_t>(), &totalOps); c->nSyncs++; if (rc != MM_OK) return rc; c->lastOps = (size_t)totalOps; }
@@ -1259,16 +1265,16 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
   MM_HIP(c, c->dL2Wide.ensure((size_t)nCbuf * 4 + 64)); MM_HIP(c, c->dL2Exact.ensure((size_t)nCbuf * 4 + 64));
   MM_HIP(c, c->dL2First.ensure((size_t)nCbuf * 8 + 64)); MM_HIP(c, c->dL2Num.ensure((size_t)nCbuf * 4 + 64));
   if (c->l2Cap < (size_t)nCbuf * 2 + 1024) c->l2Cap = (size_t)nCbuf * 2 + 1024;
-  unsigned long long hc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long hc[MM_PC_READ] = {0};
   int locap = steady && c->prevLocap ? c->prevLocap : MM_LOCAP0;
   for (int attempt = 0; attempt < 24; attempt++) {
     MM_HIP(c, c->dL2.ensure(c->l2Cap * sizeof(mm_l2_locus) + 64));
     MM_HIP(c, c->dL2Tmp.ensure((size_t)nCbuf * locap * sizeof(L2Tmp) + 64));
-    MM_HIP(c, hipMemsetAsync(cnt + 4, 0, 16, c->stream));                  // [4] cursor [5] overflow; [6] keeps the locate kernel's flag
+    MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow; MM_PC_L2_FLAGS keeps the locate kernel's
     for (const Chunk& ch : chunks) {
       if (!oneChunk) { const int rc = locate(ch); if (rc != MM_OK) return rc; }
-      MM_HIP(c, hipMemsetAsync(cnt + 7, 0, 8, c->stream));                 // [7] candidates queued for the wide pass
-      MM_HIP(c, hipMemsetAsync(cnt, 0, 8, c->stream));                     // [0] candidates queued for the exact pass (the lookup stage is done with it)
+      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_WIDE_LEN, 0, 8, c->stream));
+      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_EXACT_LEN, 0, 8, c->stream));   // (the L1 stage is done with both words)
       {
         KernelTimer t(c, MM_K_L2);
         // lane-per-candidate sweep: candidates in order of descending stream length, so that the 64 streams of a wave end together
@@ -1287,31 +1293,31 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
         // the 16-bit re-run and the exact kernel for however many candidates the narrow sweep has queued (usually none): launched for
         // a fixed number of them, the lists' lengths are read on the device
         KernelTimer t(c, MM_K_L2);
-        sweep(true, 0, MM_WIDE_CAP, ch.base, c->dL2Wide.as<int32_t>(), locap, cnt + 7, MM_WIDE_CAP, ch.c0);
+        sweep(true, 0, MM_WIDE_CAP, ch.base, c->dL2Wide.as<int32_t>(), locap, cnt + MM_PC_L2_WIDE_LEN, MM_WIDE_CAP, ch.c0);
         MM_HIP(c, hipGetLastError());
         MM_HIP(c, c->dL2Cells.ensure((size_t)MM_EXACT_CAP * (size_t)(s + 1) * sizeof(ExactCell) + 64));
         hipLaunchKernelGGL(k_l2_sweep_exact, dim3((unsigned)((MM_EXACT_CAP + 63) / 64)), dim3(64), 0, c->stream, JB, MM_EXACT_CAP, ch.base, c->dL2Exact.as<int32_t>(), c->P.segLength,
                            c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(), c->dL2Off.as<int64_t>(), c->dL2Cnt.as<int32_t>(), c->dL2Ops.as<uint32_t>(),
                            c->dL1Off.as<int64_t>(), c->dL2Cells.as<ExactCell>(), s + 1, c->dL2Tmp.as<L2Tmp>(), locap, c->dL2.as<mm_l2_locus>(),
-                           (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt, cnt,
+                           (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt, cnt + MM_PC_L2_EXACT_LEN,
                            c->dL2Info.as<L2Info>(), s, c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
                            I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>());
         MM_HIP(c, hipGetLastError());
         continue;
       }
-      MM_HIP(c, hipMemcpyAsync(hc, cnt, 64, hipMemcpyDeviceToHost, c->stream));
+      MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
       MM_SYNC(c);
-      if (hc[7] && !(hc[6] & 1ull) && !hc[5]) {                            // the few candidates whose 5-bit counters overflowed
-        const int nWide = (int)hc[7];
+      if (hc[MM_PC_L2_WIDE_LEN] && !(hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) && !hc[MM_PC_L2_OVERFLOW]) {                            // the few candidates whose 5-bit counters overflowed
+        const int nWide = (int)hc[MM_PC_L2_WIDE_LEN];
         if (c->env.debug) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone with 16-bit cells\n", nWide, ch.n);
         KernelTimer t(c, MM_K_L2);
         sweep(true, 0, nWide, ch.base, c->dL2Wide.as<int32_t>(), locap, nullptr, 0, ch.c0);
         MM_HIP(c, hipGetLastError());
-        MM_HIP(c, hipMemcpyAsync(hc, cnt, 64, hipMemcpyDeviceToHost, c->stream));
+        MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
         MM_SYNC(c);
       }
-      if (hc[0] && !(hc[6] & 1ull) && !hc[5]) {                            // candidates with a doubly open query hash: the literal sweep
-        const int nExact = (int)hc[0];
+      if (hc[MM_PC_L2_EXACT_LEN] && !(hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) && !hc[MM_PC_L2_OVERFLOW]) {                            // candidates with a doubly open query hash: the literal sweep
+        const int nExact = (int)hc[MM_PC_L2_EXACT_LEN];
         if (c->env.debug) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone by the exact kernel (overlapping windows of one hash)\n", nExact, ch.n);
         MM_HIP(c, c->dL2Cells.ensure((size_t)nExact * (size_t)(s + 1) * sizeof(ExactCell) + 64));
         KernelTimer t(c, MM_K_L2);
@@ -1322,27 +1328,24 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
                            c->dL2Info.as<L2Info>(), s, c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
                            I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>());
         MM_HIP(c, hipGetLastError());
-        MM_HIP(c, hipMemcpyAsync(hc, cnt, 64, hipMemcpyDeviceToHost, c->stream));
+        MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
         MM_SYNC(c);
       }
-      if (hc[6] & 1ull) break;                                             // slots ran out: everything is redone below with more of them (a full locus
+      if (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) break;                                             // slots ran out: everything is redone below with more of them (a full locus
                                                                            // buffer lets the other chunks run on, so that the cursor ends at the total demand)
     }
     if (steady) return MM_OK;                                              // the flags and the count are read when the pass is over
-    if (hc[6] & 1ull) {                                                    // a candidate with more tied loci than slots (tandem repeats): more slots, again
+    if (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) {                                                    // a candidate with more tied loci than slots (tandem repeats): more slots, again
       if ((size_t)nC * (size_t)locap * 2 * sizeof(L2Tmp) > ((size_t)64 << 30)) break;
       locap *= 2;
-      const unsigned long long flags = hc[6] & ~1ull;
-      MM_HIP(c, hipMemcpyAsync(cnt + 6, &flags, 8, hipMemcpyHostToDevice, c->stream));
+      const unsigned long long flags = hc[MM_PC_L2_FLAGS] & ~MM_L2F_SLOTS;
+      MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_FLAGS, &flags, 8, hipMemcpyHostToDevice, c->stream));
       continue;
     }
-    if (hc[5]) { const size_t need = mm_scaled(c, (size_t)hc[4], sizeof(mm_l2_locus)); c->l2Cap = need + need / 8 + 1024; continue; }
+    if (hc[MM_PC_L2_OVERFLOW]) { const size_t need = mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus)); c->l2Cap = need + need / 8 + 1024; continue; }
     break;
   }
-  if (hc[6] & 4ull) { c->err = "internal: an L2 stream outgrew the reservation k_l2_extents made for it"; return MM_ERR_CAPACITY; }
-  if (hc[6] & 1ull) { c->err = "an L1 candidate with more tied L2 loci than 64 GiB of staging can hold"; return MM_ERR_CAPACITY; }
-  if (hc[5]) { c->err = "L2 locus buffer overflow"; return MM_ERR_CAPACITY; }
-  c->nL2 = (size_t)hc[4];
-  c->prevLocap = locap;
-  return MM_OK;
+  const int rc = mm_l2_verdict(c, hc);
+  if (rc == MM_OK) c->prevLocap = locap;
+  return rc;
 }

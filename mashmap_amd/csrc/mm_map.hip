@@ -1,11 +1,22 @@
-// mashmap_amd/csrc/mm_map.hip -- device index + L1/L2 mapping kernels (gfx950).
+// mashmap_amd/csrc/mm_map.hip -- device index + seed lookup + L1 mapping kernels (gfx950), and the launcher of a mapping pass.
 //
 //   mm_build_device_index   flattening of skch::Sketch for the device     winSketch.hpp:100-102
 //   k_lookup_l1             getSeedHits (freq. seed removal) + getSeedIntervalPoints + computeL1CandidateRegions, fused:
-//                           wave per fragment, points sorted in registers   computeMap.hpp:818-843, 857-912, 916-1116
-//   k_sort_points_* / k_l1_sweep   the same through HBM for the fragments the fused path hands over (> 128 points,
-//                           -Y groups, position groups spanning contigs) or when MM_OPT_KEEP_POINTS is set
-//   (L2 lives in mm_l2.hip)
+//                           wave per fragment, up to 128 / 256 / 512 points sorted in registers   computeMap.hpp:818-843, 857-912, 916-1116
+//   k_lookup_mid            the same for the fragments with more points than that (up to MM_MID_MAXPTS): wave per fragment, the
+//                           points that can reach minimumHits picked by position bins in LDS
+//   k_l1_regions / k_l1_compact / k_l1_fix_offsets / k_l1_gate
+//                           the fused kernels' candidates, written into 64 regions, made one dense array; the steady-state gate
+//   the HBM point path, for what the fused kernels hand over (more points still, -Y groups, position groups spanning contigs), for
+//   every fragment under MM_OPT_KEEP_POINTS / --skipPrefix, and for fragments longer than segLength (--noSplit):
+//     k_gather_points, k_filter_points                    the interval points into dPts; those that cannot reach minimumHits dropped
+//     k_sort_points_wave / _block / _global, k_classify_sort   sorters by list length (registers, LDS, HBM) and the split between them
+//     k_l1_stream           L1 by a wave that streams the sorted points
+//     k_l1_sweep            L1 by the literal one-thread-per-fragment sweep (what k_l1_stream leaves, or everything)
+//     k_l1_window           L1 of fragments longer than segLength (windowLen != 0)
+//   map_pass / mm_launch_map   one pass over the resident sketches, stage by stage; sized or steady-state
+//   mm_results_download, mm_query_sketch_download, mm_points_download
+//   (L2 lives in mm_l2.hip, the selection in mm_select.hip; the pass's device counters are described in mm_internal.h: MM_CW_*)
 #include "mm_internal.h"
 #include "mm_device.h"
 #include <algorithm>
@@ -29,7 +40,7 @@ int mm_build_device_index(mm_ctx* c, const int32_t* contigLen, const int32_t* re
   DeviceIndex& I = c->idx;
   I.ready = false;
   const size_t n = c->hMinmers.size(), nk = c->hKeys.size(), np = c->hPoints.size();
-  MM_HIP(c, c->dCounters.ensure(256));
+  MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
   std::vector<uint64_t> pk(np);
   for (size_t i = 0; i < np; i++) pk[i] = pack_point(c->hPoints[i].seqId, c->hPoints[i].pos, c->hPoints[i].side);
   std::vector<uint8_t> fq(nk, 0);
@@ -408,7 +419,7 @@ k_lookup_l1(int nFrags, int s, const DFrag* __restrict__ frags,
             const int32_t* __restrict__ minHitsTab, const int32_t* __restrict__ cutoffs, int nCutoffs, int segLength,
             mm_l1_candidate* __restrict__ l1, unsigned long long regionCap, unsigned long long* __restrict__ l1Cursors,
             int64_t* __restrict__ l1Off, int32_t* __restrict__ bigList, int32_t* __restrict__ midList,
-            unsigned long long* __restrict__ counters /* [0] point cursor [1] pts overflow [3] l1 overflow [7] big count [16] mid count */) {
+            unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS */) {
   typedef FuseScratchT<MAXPTS> FuseScratch;
   __shared__ FuseScratch scratch[MM_LOOKUP_WPB];
   const int wv = threadIdx.x >> 6;
@@ -532,7 +543,7 @@ k_lookup_l1(int nFrags, int s, const DFrag* __restrict__ frags,
       mm_frag_stats st;
       st.rawSketchSize = cnt; st.sketchSize = outIdx; st.maxHash = lastHash; st.nPoints = 0; st.nL1 = 0; stats[f] = st;
       ptOff[2 * f] = 0; ptOff[2 * f + 1] = 0; l1Off[f] = 0;
-      midList[atomicAdd(&counters[16], 1ull)] = f;
+      midList[atomicAdd(&counters[MM_PC_MID_LEN], 1ull)] = f;
     }
   } else if (nOut < 0) {
     // slow path: the fragment's points go to HBM -- gathered by k_gather_points (which looks the seeds up once more: this kernel keeps no
@@ -543,13 +554,13 @@ k_lookup_l1(int nFrags, int s, const DFrag* __restrict__ frags,
     else if (keepPoints == 2 && P > 0) { slots = 2; while (slots < P) slots <<= 1; }      // windowed mode: every list goes through the LDS / HBM sorters
     if (lane == 0) {
       unsigned long long off = 0;
-      if (slots > 0) off = atomicAdd(&counters[0], (unsigned long long)slots);
+      if (slots > 0) off = atomicAdd(&counters[MM_PC_POINT_CURSOR], (unsigned long long)slots);
       bool ok = true;
-      if (slots > 0 && off + (unsigned long long)slots > ptsCap) { ok = false; atomicOr(&counters[1], 1ull); }
+      if (slots > 0 && off + (unsigned long long)slots > ptsCap) { ok = false; atomicOr(&counters[MM_PC_POINT_OVERFLOW], MM_OVERFLOWED); }
       mm_frag_stats st;
       st.rawSketchSize = cnt; st.sketchSize = outIdx; st.maxHash = lastHash; st.nPoints = 0; st.nL1 = 0; stats[f] = st;
       ptOff[2 * f] = (int64_t)off; ptOff[2 * f + 1] = ok ? (int64_t)slots : 0; l1Off[f] = 0;
-      if (slots > 0 && ok) bigList[atomicAdd(&counters[7], 1ull)] = f;
+      if (slots > 0 && ok) bigList[atomicAdd(&counters[MM_PC_BIG_LEN], 1ull)] = f;
     }
   }
   }  // live
@@ -560,7 +571,7 @@ k_lookup_l1(int nFrags, int s, const DFrag* __restrict__ frags,
     if (nOut > 0) {
       if (lane == 0) at = atomicAdd(&l1Cursors[(size_t)region * MM_L1_CURSOR_STRIDE], (unsigned long long)nOut);
       at = ((unsigned long long)(uint32_t)__shfl((int)(at >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)at, 0);
-      if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[3], 1ull); nOut = 0; }
+      if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
     }
     const unsigned long long base = (unsigned long long)region * regionCap + at;
     for (int i = lane; i < nOut; i += 64) {
@@ -858,11 +869,11 @@ k_lookup_mid(int nList, const unsigned long long* __restrict__ nDev, const int32
     if (nOut < 0) {                                                // to the HBM path after all, as k_lookup_l1 queues a fragment
       int slots = 128; while (slots < P) slots <<= 1;
       if (lane == 0) {
-        const unsigned long long off = atomicAdd(&counters[0], (unsigned long long)slots);
+        const unsigned long long off = atomicAdd(&counters[MM_PC_POINT_CURSOR], (unsigned long long)slots);
         bool ok = true;
-        if (off + (unsigned long long)slots > ptsCap) { ok = false; atomicOr(&counters[1], 1ull); }
+        if (off + (unsigned long long)slots > ptsCap) { ok = false; atomicOr(&counters[MM_PC_POINT_OVERFLOW], MM_OVERFLOWED); }
         ptOff[2 * f] = (int64_t)off; ptOff[2 * f + 1] = ok ? (int64_t)slots : 0; l1Off[f] = 0;
-        if (ok) bigList[atomicAdd(&counters[7], 1ull)] = f;
+        if (ok) bigList[atomicAdd(&counters[MM_PC_BIG_LEN], 1ull)] = f;
       }
     } else {
       const int region = f & (MM_L1_REGIONS - 1);
@@ -870,7 +881,7 @@ k_lookup_mid(int nList, const unsigned long long* __restrict__ nDev, const int32
       if (nOut > 0) {
         if (lane == 0) at = atomicAdd(&l1Cursors[(size_t)region * MM_L1_CURSOR_STRIDE], (unsigned long long)nOut);
         at = ((unsigned long long)(uint32_t)__shfl((int)(at >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)at, 0);
-        if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[3], 1ull); nOut = 0; }
+        if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
       }
       const unsigned long long base = (unsigned long long)region * regionCap + at;
       for (int i = lane; i < nOut; i += 64) {
@@ -892,15 +903,15 @@ k_lookup_mid(int nList, const unsigned long long* __restrict__ nDev, const int32
 // the fragments' first-candidate offsets follow
 struct L1Regions { unsigned long long prefix[MM_L1_REGIONS]; unsigned long long count[MM_L1_REGIONS]; };
 // the regions' fill counts -> their prefix positions in the dense buffer (device-resident: no host round trip between the lookup kernel
-// and the compaction) and the number of fused candidates (counters[2])
+// and the compaction) and the number of fused candidates (counters[MM_PC_L1_CAND])
 __global__ void __launch_bounds__(64)
 k_l1_regions(const unsigned long long* __restrict__ l1Cursors, unsigned long long regionCap, L1Regions* __restrict__ R, unsigned long long* __restrict__ counters) {
   const int r = threadIdx.x;
   unsigned long long n = l1Cursors[(size_t)r * MM_L1_CURSOR_STRIDE];
-  if (n > regionCap) n = regionCap;                              // an overflowed region (counters[3] is set): what was written
+  if (n > regionCap) n = regionCap;                              // an overflowed region (counters[MM_PC_L1_OVERFLOW] is set): what was written
   const int ex = mm_wave_excl_scan((int)n);
   R->count[r] = n; R->prefix[r] = (unsigned long long)ex;
-  if (r == 63) counters[2] = (unsigned long long)ex + n;
+  if (r == 63) counters[MM_PC_L1_CAND] = (unsigned long long)ex + n;
 }
 __global__ void __launch_bounds__(256)
 k_l1_compact(const mm_l1_candidate* __restrict__ src, mm_l1_candidate* __restrict__ dst, unsigned long long regionCap, const L1Regions* __restrict__ R) {
@@ -917,15 +928,15 @@ k_l1_fix_offsets(int nFrags, const mm_frag_stats* __restrict__ stats, int64_t* _
   l1Off[f] = l1Off[f] - (int64_t)((unsigned long long)r * regionCap) + (int64_t)R->prefix[r];
 }
 
-// Steady-state passes read the L1 stage's overflow flags (counters[1] interval points, counters[3] L1 candidates) only when the whole
+// Steady-state passes read the L1 stage's overflow flags (counters[MM_PC_POINT_OVERFLOW] interval points, counters[MM_PC_L1_OVERFLOW] L1 candidates) only when the whole
 // pass is over, so the L2 stage must be kept off what an overflowed L1 stage left behind: a region that overflowed has never-written
 // slots below its clamped count, the sweep path may have counted past the dense buffer, and more candidates than the previous pass
 // sized the candidate-indexed buffers for (candCap) do not fit them either.  One thread, behind the last L1 kernel: any of these zeroes
-// the candidate count -- every kernel of the L2 stage covers [0, counters[2]) and k_l2_select returns on a set flag -- and leaves (or
+// the candidate count -- every kernel of the L2 stage covers [0, counters[MM_PC_L1_CAND]) and k_l2_select returns on a set flag -- and leaves (or
 // sets) the flag that makes the host redo the pass the sized way.
 __global__ void k_l1_gate(unsigned long long* __restrict__ counters, unsigned long long candCap) {
-  if (counters[1] | counters[3]) counters[2] = 0ull;
-  else if (counters[2] > candCap) { counters[3] = 1ull; counters[2] = 0ull; }
+  if (counters[MM_PC_POINT_OVERFLOW] | counters[MM_PC_L1_OVERFLOW]) counters[MM_PC_L1_CAND] = 0ull;
+  else if (counters[MM_PC_L1_CAND] > candCap) { counters[MM_PC_L1_OVERFLOW] = MM_OVERFLOWED; counters[MM_PC_L1_CAND] = 0ull; }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1026,7 +1037,7 @@ k_sort_points_global(const unsigned int* __restrict__ nListDev, const int64_t* _
 
 // splits the queued fragments into the block / global sorter lists (wave-aggregated cursors)
 __global__ void k_classify_sort(int nList, const unsigned long long* __restrict__ nDev, const int32_t* __restrict__ list, const int64_t* __restrict__ ptOff,
-                                int32_t* __restrict__ listB, int32_t* __restrict__ listC, unsigned int* __restrict__ cnt /* [0] B, [1] C */, int minB /* lists longer than this go to the LDS sorter */) {
+                                int32_t* __restrict__ listB, int32_t* __restrict__ listC, unsigned int* __restrict__ lens /* dCounters + MM_CW_SORT_LENS, 32-bit words */, int minB /* lists longer than this go to the LDS sorter */) {
   if (nDev) nList = (int)*nDev;
   for (int base = blockIdx.x * blockDim.x; base < nList; base += gridDim.x * blockDim.x) {
     const int li = base + threadIdx.x;
@@ -1035,8 +1046,8 @@ __global__ void k_classify_sort(int nList, const unsigned long long* __restrict_
     const bool isC = n > MM_SORT_LDSCAP, isB = !isC && n > minB;
     const uint64_t mB = __ballot(isB), mC = __ballot(isC);
     unsigned int bB = 0, bC = 0;
-    if (mB && mm_lane() == (uint32_t)__builtin_ctzll(mB)) bB = atomicAdd(&cnt[0], (unsigned int)__popcll(mB));
-    if (mC && mm_lane() == (uint32_t)__builtin_ctzll(mC)) bC = atomicAdd(&cnt[1], (unsigned int)__popcll(mC));
+    if (mB && mm_lane() == (uint32_t)__builtin_ctzll(mB)) bB = atomicAdd(&lens[MM_SL_BLOCK], (unsigned int)__popcll(mB));
+    if (mC && mm_lane() == (uint32_t)__builtin_ctzll(mC)) bC = atomicAdd(&lens[MM_SL_GLOBAL], (unsigned int)__popcll(mC));
     if (mB) bB = __shfl(bB, __builtin_ctzll(mB));
     if (mC) bC = __shfl(bC, __builtin_ctzll(mC));
     if (isB) listB[bB + mm_popc_below(mB)] = f;
@@ -1142,16 +1153,15 @@ __device__ void l1_sweep_fragment(const uint64_t* __restrict__ p, int nPts, int 
 // one-thread-per-fragment kernel costs 50-170 ns per fragment (profiles/r03j_repeat_probe.txt).
 // ---------------------------------------------------------------------------------------------
 #define MM_STREAM_BUF 64            // candidates kept in LDS by the counting pass (more: the writing pass runs again)
-struct L1RunS { int32_t seq, start, end, isize; };
 __global__ void __launch_bounds__(256)
 k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restrict__ ptOff, const uint64_t* __restrict__ pts,
             mm_frag_stats* __restrict__ stats, const int32_t* __restrict__ minHitsTab, const int32_t* __restrict__ cutoffs, int nCutoffs,
             int sParam, int segLength, int hg, mm_l1_candidate* __restrict__ l1, unsigned long long l1Cap, int64_t* __restrict__ l1Off,
-            int32_t* __restrict__ lit, unsigned int* __restrict__ litCount, unsigned long long* __restrict__ counters /* [2] l1 cursor, [3] overflow */,
+            int32_t* __restrict__ lit, unsigned int* __restrict__ litCount, unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS: the L1 cursor and its overflow flag */,
             const unsigned long long* __restrict__ nDev, const int32_t* __restrict__ ptKept /* points at the head of the sorted list (k_gather_points / k_filter_points) */) {
-  __shared__ L1RunS bufAll[4][MM_STREAM_BUF];
+  __shared__ L1Run bufAll[4][MM_STREAM_BUF];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  L1RunS* buf = bufAll[wave];
+  L1Run* buf = bufAll[wave];
   if (nDev) nList = (int)*nDev;
   auto one = [&](const int f) {
   const int nPts = ptKept[f], S = stats[f].sketchSize;
@@ -1208,7 +1218,7 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
   for (int pass = 0; pass < 2; pass++) {
     const bool write = pass == 1;
     int count = 0;
-    bool have = false; L1RunS pend{0, 0, 0, 0};
+    bool have = false; L1Run pend{0, 0, 0, 0};
     auto flush = [&]() {
       if (have) {
         if (lane == 0) {
@@ -1284,13 +1294,13 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
       total = count;
       if (total > 0) {
         long long b0 = 0;
-        if (lane == 0) b0 = (long long)atomicAdd(&counters[2], (unsigned long long)total);
+        if (lane == 0) b0 = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)total);
         base = ((long long)__builtin_amdgcn_readfirstlane((int)(b0 >> 32)) << 32) | (unsigned int)__builtin_amdgcn_readfirstlane((int)b0);
-        if ((unsigned long long)base + (unsigned long long)total > l1Cap) { if (lane == 0) atomicOr(&counters[3], 1ull); total = 0; }
+        if ((unsigned long long)base + (unsigned long long)total > l1Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); total = 0; }
       }
       if (total > 0 && total <= MM_STREAM_BUF) {                   // the counting pass kept them all
         __threadfence_block();
-        if (lane < total) { const L1RunS r = buf[lane]; mm_l1_candidate o; o.frag = f; o.seqId = r.seq; o.rangeStartPos = r.start; o.rangeEndPos = r.end; o.intersectionSize = r.isize; l1[base + lane] = o; }
+        if (lane < total) { const L1Run r = buf[lane]; mm_l1_candidate o; o.frag = f; o.seqId = r.seq; o.rangeStartPos = r.start; o.rangeEndPos = r.end; o.intersectionSize = r.isize; l1[base + lane] = o; }
         break;
       }
       if (total == 0) break;
@@ -1306,7 +1316,7 @@ k_l1_sweep(int nList, const int32_t* __restrict__ list, const int64_t* __restric
            mm_frag_stats* __restrict__ stats,
            const int32_t* __restrict__ minHitsTab, const int32_t* __restrict__ cutoffs, int nCutoffs, int sParam, int segLength,
            MapFlags fl, const int32_t* __restrict__ refGroup, mm_l1_candidate* __restrict__ l1, unsigned long long l1Cap,
-           int64_t* __restrict__ l1Off, unsigned long long* __restrict__ counters /* [2] l1 cursor, [3] overflow */,
+           int64_t* __restrict__ l1Off, unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS: the L1 cursor and its overflow flag */,
            const unsigned int* __restrict__ nListDev /* non-null: the list's length lives on the device (what k_l1_stream left over) */,
            const unsigned long long* __restrict__ nDev64 /* non-null: the same as a 64-bit counter (the hand-over count of k_lookup_l1) */,
            const int32_t* __restrict__ ptKept) {
@@ -1323,8 +1333,8 @@ k_l1_sweep(int nList, const int32_t* __restrict__ list, const int64_t* __restric
     l1_sweep_fragment(p, nPts, S, minHits0, cutoffs, nCutoffs, sParam, segLength, fl, refGroup, em);
     nOut = em.count;
     if (nOut > 0) {
-      base = (long long)atomicAdd(&counters[2], (unsigned long long)nOut);
-      if ((unsigned long long)base + nOut > l1Cap) { atomicOr(&counters[3], 1ull); nOut = 0; }
+      base = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)nOut);
+      if ((unsigned long long)base + nOut > l1Cap) { atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
       else if (nOut <= 2) { l1[base] = em.b0; if (nOut == 2) l1[base + 1] = em.b1; }
       else {
         L1Emit ew; ew.out = l1 + base; ew.frag = f; ew.count = 0; ew.write = true; ew.have = false;
@@ -1412,7 +1422,7 @@ __global__ void __launch_bounds__(64)
 k_l1_window(int nList, const int32_t* __restrict__ list, const DFrag* __restrict__ frags, const int64_t* __restrict__ ptOff, const uint64_t* __restrict__ pts,
             const uint16_t* __restrict__ ptIds, mm_frag_stats* __restrict__ stats, const int32_t* __restrict__ minHitsTab, const int32_t* __restrict__ cutoffs,
             int nCutoffs, int sParam, int segLength, MapFlags fl, const int32_t* __restrict__ refGroup, int32_t* __restrict__ freqAll, int nFreq,
-            mm_l1_candidate* __restrict__ l1, unsigned long long l1Cap, int64_t* __restrict__ l1Off, unsigned long long* __restrict__ counters /* [2] l1 cursor, [3] overflow */) {
+            mm_l1_candidate* __restrict__ l1, unsigned long long l1Cap, int64_t* __restrict__ l1Off, unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS: the L1 cursor and its overflow flag */) {
   const int li = blockIdx.x * blockDim.x + threadIdx.x;
   if (li >= nList) return;
   const int f = list[li];
@@ -1428,8 +1438,8 @@ k_l1_window(int nList, const int32_t* __restrict__ list, const DFrag* __restrict
     l1_window_fragment(p, ids, nPts, W, freq, nFreq, S, minHits0, cutoffs, nCutoffs, sParam, segLength, fl, refGroup, em);
     nOut = em.count;
     if (nOut > 0) {
-      base = (long long)atomicAdd(&counters[2], (unsigned long long)nOut);
-      if ((unsigned long long)base + nOut > l1Cap) { atomicOr(&counters[3], 1ull); nOut = 0; }
+      base = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)nOut);
+      if ((unsigned long long)base + nOut > l1Cap) { atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
       else if (nOut <= 2) { l1[base] = em.b0; if (nOut == 2) l1[base + 1] = em.b1; }
       else {
         L1Emit ew; ew.out = l1 + base; ew.frag = f; ew.count = 0; ew.write = true; ew.have = false;
@@ -1444,8 +1454,6 @@ k_l1_window(int nList, const int32_t* __restrict__ list, const DFrag* __restrict
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-#define MM_SYNC(c) do { MM_HIP(c, hipStreamSynchronize((c)->stream)); (c)->nSyncs++; } while (0)
-
 // One pass of seed lookup + L1 + L2 + selection over the resident sketches.
 //   steady == false: every stage is sized from the counts of the one before it, read back from the device (and grown + retried when a
 //                    buffer overflows): five to seven host synchronisations per pass.
@@ -1453,45 +1461,67 @@ k_l1_window(int nList, const int32_t* __restrict__ list, const DFrag* __restrict
 //                    the counts left on the device (kernels over lists take their lengths from there, kernels over candidates cover the
 //                    buffers' capacity), and one block of counters is read back at the end: ONE synchronisation per pass.  A pass that
 //                    outgrew a buffer has its overflow flag set there and is redone the sized way (MM_PASS_REDO).
-static int map_pass(mm_ctx* c, const bool steady) {
-  const int nF = (int)c->nFrags, s = c->P.sketchSize;
+// What the stages of a pass hand on (map_pass calls them in order; each one is a sequence of operations on c->stream).
+struct MapPass {
+  bool steady, windowed, allSlow, useMid;
+  int nF, s;
+  MapFlags fl;
+  SeedTable seedTab;
+  unsigned long long* cnt;                 // dCounters + MM_CW_PASS (MM_PC_*)
+  unsigned int* lens;                      // dCounters + MM_CW_SORT_LENS, 32-bit words (MM_SL_*)
+  const unsigned long long* nBigDev;       // steady-state pass: the length of dBigList where the kernels read it
+  unsigned long long regionCap = 0;        // candidates per output region of the fused kernels
+  size_t denseCap = 0;                     // candidates the dense L1 buffer holds
+  // what a sized pass has read back (a steady-state pass never reads them: all zero)
+  unsigned long long hc[MM_PC_READ] = {0}, hMid = 0, hcur[MM_L1_REGIONS * MM_L1_CURSOR_STRIDE] = {0};
+  int nBig = 0;                            // sized pass: fragments queued for the HBM point path
+  unsigned gWave = 0, gThread = 0;         // grids over those: a wave / a thread per fragment
+};
+
+// stage 1: what the pass is, and the buffers that are sized by the number of fragments
+static int pass_prepare(mm_ctx* c, MapPass& p) {
   const DeviceIndex& I = c->idx;
-  MapFlags fl{(c->P.flags & MM_FLAG_HG_FILTER) ? 1 : 0, (c->P.flags & MM_FLAG_SKIP_SELF) ? 1 : 0,
-              (c->P.flags & MM_FLAG_SKIP_PREFIX) ? 1 : 0, (c->P.flags & MM_FLAG_LOWER_TRIANGULAR) ? 1 : 0};
+  p.nF = (int)c->nFrags; p.s = c->P.sketchSize;
+  p.fl = MapFlags{(c->P.flags & MM_FLAG_HG_FILTER) ? 1 : 0, (c->P.flags & MM_FLAG_SKIP_SELF) ? 1 : 0,
+                  (c->P.flags & MM_FLAG_SKIP_PREFIX) ? 1 : 0, (c->P.flags & MM_FLAG_LOWER_TRIANGULAR) ? 1 : 0};
   // fragments longer than segLength (--noSplit): windowLen != 0 -- every fragment takes the literal path with its points (and their
   // seeds' numbers) in HBM: k_l1_window here, k_l2_window in mm_l2.hip
-  const bool windowed = c->windowed;
-  const bool allSlow = c->keepPoints || fl.skipPrefix || windowed;
-  const size_t cF = mm_frag_cap(c, (size_t)nF);
-  if (c->ptsCap == 0) c->ptsCap = allSlow ? cF * 128 + 4096 : cF * 8 + 65536;
+  p.windowed = c->windowed;
+  p.allSlow = c->keepPoints || p.fl.skipPrefix || p.windowed;
+  const size_t cF = mm_frag_cap(c, (size_t)p.nF);
+  if (c->ptsCap == 0) c->ptsCap = p.allSlow ? cF * 128 + 4096 : cF * 8 + 65536;
   if (c->l1Cap < cF * 2 + 1024) c->l1Cap = cF * 2 + 1024;
-  DevBuf& listB = c->dListB; DevBuf& listC = c->dListC;
-  MM_HIP(c, listB.ensure(cF * 4 + 16)); MM_HIP(c, listC.ensure(cF * 4 + 16)); MM_HIP(c, c->dBigList.ensure(cF * 4 + 16));
+  MM_HIP(c, c->dListB.ensure(cF * 4 + 16)); MM_HIP(c, c->dListC.ensure(cF * 4 + 16)); MM_HIP(c, c->dBigList.ensure(cF * 4 + 16));
   // fragments with more interval points than k_lookup_l1 sorts go through k_lookup_mid first
-  const bool useMid = !allSlow && s <= MM_MID_MAXSKETCH;
-  if (useMid) MM_HIP(c, c->dMidList.ensure(cF * 4 + 16));
-  unsigned long long hMid = 0;
+  p.useMid = !p.allSlow && p.s <= MM_MID_MAXSKETCH;
+  if (p.useMid) MM_HIP(c, c->dMidList.ensure(cF * 4 + 16));
   MM_HIP(c, c->dL1Regions.ensure(sizeof(L1Regions)));
-  int rc = MM_OK;
-  unsigned long long hc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long* cnt = c->dCounters.as<unsigned long long>() + 8;   // [8..15]; [0..7] belong to the sketch launcher
-  unsigned long long* cnt2 = c->dCounters.as<unsigned long long>() + 32; // [32..]: [0] candidate mappings [1] their buffer overflowed
-  const unsigned long long* nBigDev = steady ? cnt + 7 : nullptr;
+  p.cnt = c->dCounters.as<unsigned long long>() + MM_CW_PASS;
+  p.lens = (unsigned int*)(c->dCounters.as<unsigned long long>() + MM_CW_SORT_LENS);
+  p.nBigDev = p.steady ? p.cnt + MM_PC_BIG_LEN : nullptr;
+  p.seedTab = SeedTable{I.htSlots.as<HtSlot>(), (uint64_t)(I.htCap - 1), I.filter.as<uint64_t>(), (uint64_t)I.filterMask, I.tagged ? I.htTags.as<uint8_t>() : (const uint8_t*)nullptr};
+  return MM_OK;
+}
 
-  const SeedTable seedTab{I.htSlots.as<HtSlot>(), (uint64_t)(I.htCap - 1), I.filter.as<uint64_t>(), (uint64_t)I.filterMask, I.tagged ? I.htTags.as<uint8_t>() : (const uint8_t*)nullptr};
-  unsigned long long hcur[MM_L1_REGIONS * MM_L1_CURSOR_STRIDE] = {0};   // a steady-state pass never reads the cursors back
-  unsigned long long regionCap = 0;
+// stage 2: the counters' reset, k_lookup_l1 and k_lookup_mid; a sized pass reads the counts back and grows + retries when the
+// interval points or a region of L1 candidates did not fit
+static int pass_lookup(mm_ctx* c, MapPass& p) {
+  const DeviceIndex& I = c->idx;
+  const int nF = p.nF, s = p.s;
+  unsigned long long* const cnt = p.cnt;
+  unsigned long long* const all = c->dCounters.as<unsigned long long>();
   for (int attempt = 0; attempt < 10; attempt++) {          // grow-and-retry on capacity overflow (points or L1 candidates)
-    regionCap = (c->l1Cap + MM_L1_REGIONS - 1) / MM_L1_REGIONS + 64;
+    p.regionCap = (c->l1Cap + MM_L1_REGIONS - 1) / MM_L1_REGIONS + 64;
     MM_HIP(c, c->dPts.ensure(c->ptsCap * 8 + 64));
-    MM_HIP(c, c->dPtIds.ensure(windowed ? c->ptsCap * 2 + 64 : 64));
-    MM_HIP(c, c->dL1.ensure(regionCap * MM_L1_REGIONS * sizeof(mm_l1_candidate) + 64));
-    MM_HIP(c, c->dL1b.ensure(regionCap * MM_L1_REGIONS * sizeof(mm_l1_candidate) + 64));
-    MM_HIP(c, c->dL1Cursors.ensure(sizeof hcur));
-    if (attempt == 0) MM_HIP(c, hipMemcpyAsync(c->dCounters.as<unsigned long long>() + 48, c->dCounters.p, 8, hipMemcpyDeviceToDevice, c->stream));   // the sketch launcher's hard-list length ([0], 32 bits) survives the reset below
-    MM_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 256, c->stream));
-    MM_HIP(c, hipMemsetAsync(cnt2, 0, 64, c->stream));
-    MM_HIP(c, hipMemsetAsync(c->dL1Cursors.p, 0, sizeof hcur, c->stream));
+    MM_HIP(c, c->dPtIds.ensure(p.windowed ? c->ptsCap * 2 + 64 : 64));
+    MM_HIP(c, c->dL1.ensure(p.regionCap * MM_L1_REGIONS * sizeof(mm_l1_candidate) + 64));
+    MM_HIP(c, c->dL1b.ensure(p.regionCap * MM_L1_REGIONS * sizeof(mm_l1_candidate) + 64));
+    MM_HIP(c, c->dL1Cursors.ensure(sizeof p.hcur));
+    // the sketch launcher's hard-list length (32 bits of its first word) survives the reset below
+    if (attempt == 0) MM_HIP(c, hipMemcpyAsync(all + MM_CW_HARD_COPY, all + MM_CW_SKETCH, 8, hipMemcpyDeviceToDevice, c->stream));
+    MM_HIP(c, hipMemsetAsync(all, 0, (size_t)MM_CW_MAP * 8, c->stream));
+    MM_HIP(c, hipMemsetAsync(all + MM_CW_MAP, 0, (size_t)(MM_CW_MAP_END - MM_CW_MAP) * 8, c->stream));
+    MM_HIP(c, hipMemsetAsync(c->dL1Cursors.p, 0, sizeof p.hcur, c->stream));
     {
       KernelTimer t(c, MM_K_LOOKUP);
       // the fused path holds a fragment's interval points in LDS + registers: up to 128 of them for the default sketch, 256 / 512 for
@@ -1500,191 +1530,214 @@ static int map_pass(mm_ctx* c, const bool steady) {
       auto kern = I.tagged ? (fuse == 512 ? k_lookup_l1<512, true> : fuse == 256 ? k_lookup_l1<256, true> : k_lookup_l1<128, true>)
                            : (fuse == 512 ? k_lookup_l1<512, false> : fuse == 256 ? k_lookup_l1<256, false> : k_lookup_l1<128, false>);
       hipLaunchKernelGGL(kern, dim3((nF + MM_LOOKUP_WPB - 1) / MM_LOOKUP_WPB), dim3(MM_LOOKUP_WPB * 64), 0, c->stream, nF, s, c->dFrags.as<DFrag>(),
-                         c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(), c->dSkCount.as<uint32_t>(), seedTab, I.ptKeys.as<uint64_t>(),
-                         c->dReadSelf.as<int32_t>(), c->seqCounterBase, fl, windowed ? 2 : (c->keepPoints ? 1 : 0),
+                         c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(), c->dSkCount.as<uint32_t>(), p.seedTab, I.ptKeys.as<uint64_t>(),
+                         c->dReadSelf.as<int32_t>(), c->seqCounterBase, p.fl, p.windowed ? 2 : (c->keepPoints ? 1 : 0),
                          c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(),
                          c->dStats.as<mm_frag_stats>(), c->dPtOff.as<int64_t>(), (unsigned long long)c->ptsCap,
                          c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(), (int)c->nCutoffs, c->P.segLength,
-                         c->dL1.as<mm_l1_candidate>(), regionCap, c->dL1Cursors.as<unsigned long long>(), c->dL1Off.as<int64_t>(),
-                         c->dBigList.as<int32_t>(), useMid ? c->dMidList.as<int32_t>() : (int32_t*)nullptr, cnt);
+                         c->dL1.as<mm_l1_candidate>(), p.regionCap, c->dL1Cursors.as<unsigned long long>(), c->dL1Off.as<int64_t>(),
+                         c->dBigList.as<int32_t>(), p.useMid ? c->dMidList.as<int32_t>() : (int32_t*)nullptr, cnt);
       MM_HIP(c, hipGetLastError());
     }
-    if (useMid) {
-      // its list's length stays on the device (cnt[16]); the grid is what the last sized pass saw plus a half (the kernel walks the list
-      // with whatever grid it gets), every fragment when nothing is known yet
+    if (p.useMid) {
+      // its list's length stays on the device (MM_PC_MID_LEN); the grid is what the last sized pass saw plus a half (the kernel walks the
+      // list with whatever grid it gets), every fragment when nothing is known yet
       KernelTimer t(c, MM_K_SORT);
       const size_t guess = c->midKnown ? c->prevMid + c->prevMid / 2 + 256 : (size_t)nF;
       const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(guess, (size_t)nF));
       auto mk = I.tagged ? k_lookup_mid<true> : k_lookup_mid<false>;
-      hipLaunchKernelGGL(mk, dim3(grid), dim3(64), 0, c->stream, 0, cnt + 16, c->dMidList.as<int32_t>(), s, c->dFrags.as<DFrag>(), c->dSkHash.as<uint64_t>(),
-                         c->dSkCount.as<uint32_t>(), seedTab, I.ptKeys.as<uint64_t>(), c->dReadSelf.as<int32_t>(), c->seqCounterBase, fl, c->dStats.as<mm_frag_stats>(),
+      hipLaunchKernelGGL(mk, dim3(grid), dim3(64), 0, c->stream, 0, cnt + MM_PC_MID_LEN, c->dMidList.as<int32_t>(), s, c->dFrags.as<DFrag>(), c->dSkHash.as<uint64_t>(),
+                         c->dSkCount.as<uint32_t>(), p.seedTab, I.ptKeys.as<uint64_t>(), c->dReadSelf.as<int32_t>(), c->seqCounterBase, p.fl, c->dStats.as<mm_frag_stats>(),
                          c->dPtOff.as<int64_t>(), (unsigned long long)c->ptsCap, c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(), (int)c->nCutoffs, c->P.segLength,
-                         c->dL1.as<mm_l1_candidate>(), regionCap, c->dL1Cursors.as<unsigned long long>(), c->dL1Off.as<int64_t>(), c->dBigList.as<int32_t>(), cnt);
+                         c->dL1.as<mm_l1_candidate>(), p.regionCap, c->dL1Cursors.as<unsigned long long>(), c->dL1Off.as<int64_t>(), c->dBigList.as<int32_t>(), cnt);
       MM_HIP(c, hipGetLastError());
     }
-    if (steady) break;                                        // overflow flags ([1], [3]) are looked at when the pass is over
-    MM_HIP(c, hipMemcpyAsync(hc, cnt, 64, hipMemcpyDeviceToHost, c->stream));
-    MM_HIP(c, hipMemcpyAsync(&hMid, cnt + 16, 8, hipMemcpyDeviceToHost, c->stream));
-    MM_HIP(c, hipMemcpyAsync(hcur, c->dL1Cursors.p, sizeof hcur, hipMemcpyDeviceToHost, c->stream));
-    MM_HIP(c, hipMemcpyAsync(c->hPass + 16, c->dCounters.as<unsigned long long>() + 48, 8, hipMemcpyDeviceToHost, c->stream));
+    if (p.steady) return MM_OK;                               // the overflow flags are looked at when the pass is over
+    MM_HIP(c, hipMemcpyAsync(p.hc, cnt, sizeof p.hc, hipMemcpyDeviceToHost, c->stream));
+    MM_HIP(c, hipMemcpyAsync(&p.hMid, cnt + MM_PC_MID_LEN, 8, hipMemcpyDeviceToHost, c->stream));
+    MM_HIP(c, hipMemcpyAsync(p.hcur, c->dL1Cursors.p, sizeof p.hcur, hipMemcpyDeviceToHost, c->stream));
+    MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_HARD_COPY, all + MM_CW_HARD_COPY, 8, hipMemcpyDeviceToHost, c->stream));
     MM_SYNC(c);
-    c->lastHard = (size_t)(c->hPass[16] & 0xffffffffull);
-    if (hc[1]) { const size_t need = mm_scaled(c, (size_t)hc[0], 16); c->ptsCap = need + need / 8 + 4096; continue; }
-    if (hc[3]) {                                              // some region overflowed: size for the largest one seen
+    c->lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
+    if (p.hc[MM_PC_POINT_OVERFLOW]) { const size_t need = mm_scaled(c, (size_t)p.hc[MM_PC_POINT_CURSOR], 16); c->ptsCap = need + need / 8 + 4096; continue; }
+    if (p.hc[MM_PC_L1_OVERFLOW]) {                            // some region overflowed: size for the largest one seen
       unsigned long long mx = 0;
-      for (int r = 0; r < MM_L1_REGIONS; r++) mx = std::max(mx, hcur[(size_t)r * MM_L1_CURSOR_STRIDE]);
+      for (int r = 0; r < MM_L1_REGIONS; r++) mx = std::max(mx, p.hcur[(size_t)r * MM_L1_CURSOR_STRIDE]);
       mx = (unsigned long long)mm_scaled(c, (size_t)mx, sizeof(mm_l1_candidate) * MM_L1_REGIONS);
       c->l1Cap = (size_t)(mx + mx / 4 + 256) * MM_L1_REGIONS; continue;
     }
     break;
   }
-  if (hc[1]) { c->err = "interval-point buffer overflow"; return MM_ERR_CAPACITY; }
-  if (hc[3]) { c->err = "L1 candidate buffer overflow"; return MM_ERR_CAPACITY; }
-  {
-    // the regions' prefix positions and the number of fused candidates (cnt[2]) are computed on the device; the sized pass knows them
-    // from the cursors it has read
-    unsigned long long tot = 0;
-    for (int r = 0; r < MM_L1_REGIONS; r++) tot += hcur[(size_t)r * MM_L1_CURSOR_STRIDE];
-    hc[2] = steady ? 0 : tot;
-    if (steady || tot) {
-      KernelTimer t(c, MM_K_L1);
-      hipLaunchKernelGGL(k_l1_regions, dim3(1), dim3(64), 0, c->stream, c->dL1Cursors.as<unsigned long long>(), regionCap, c->dL1Regions.as<L1Regions>(), cnt);
-      hipLaunchKernelGGL(k_l1_compact, dim3(64, MM_L1_REGIONS), dim3(256), 0, c->stream, c->dL1.as<mm_l1_candidate>(), c->dL1b.as<mm_l1_candidate>(), regionCap, c->dL1Regions.as<L1Regions>());
-      hipLaunchKernelGGL(k_l1_fix_offsets, dim3((nF + 255) / 256), dim3(256), 0, c->stream, nF, c->dStats.as<mm_frag_stats>(), c->dL1Off.as<int64_t>(), regionCap, c->dL1Regions.as<L1Regions>());
-      MM_HIP(c, hipGetLastError());
-    }
-    std::swap(c->dL1, c->dL1b);                               // dL1 is the dense buffer from here on
-  }
-  size_t denseCap = c->dL1.bytes / sizeof(mm_l1_candidate) - 4;   // room behind the fused candidates for the sweep path's
-  const int nBig = (int)hc[7];
-  if (c->env.debug) {
-    if (steady) fprintf(stderr, "[mm] lookup+L1: %d fragments, steady-state pass (the counts stay on the device)\n", nF);
-    else fprintf(stderr, "[mm] lookup+L1: %d fragments, %llu through k_lookup_mid, %d to the sort+sweep path, %llu fused candidates\n", nF, hMid, nBig, hc[2]);
-  }
-  if (steady || nBig > 0) {
-    unsigned int* cls = (unsigned int*)(c->dCounters.as<unsigned long long>() + 16);   // [16] two 32-bit class counters
-    // grids over the queued fragments: exact when their number is known, otherwise sized by what the previous pass saw (the kernels
-    // walk the list with whatever grid they get)
-    const int nB = steady ? (int)std::min<size_t>(c->prevBig + c->prevBig / 2 + 1024, (size_t)nF) : nBig;
-    const unsigned gWave = (unsigned)((nB + 3) / 4), gThread = (unsigned)((nB + 255) / 256);
-    {
-      KernelTimer t(c, MM_K_SORT);
-      uint16_t* sortIds = windowed ? c->dPtIds.as<uint16_t>() : (uint16_t*)nullptr;
-      {
-        auto gk = I.tagged ? k_gather_points<true> : k_gather_points<false>;
-        hipLaunchKernelGGL(gk, dim3(gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), s, c->dFrags.as<DFrag>(), c->dSkHash.as<uint64_t>(),
-                           c->dSkCount.as<uint32_t>(), seedTab, I.ptKeys.as<uint64_t>(), I.refGroup.as<int32_t>(),
-                           c->dReadGroup.as<int32_t>(), c->dReadSelf.as<int32_t>(), c->seqCounterBase, fl, c->dStats.as<mm_frag_stats>(), c->dPtOff.as<int64_t>(),
-                           c->dPts.as<uint64_t>(), sortIds, c->dPtKept.as<int32_t>(), nBigDev);
-        MM_HIP(c, hipGetLastError());
-        // split mode, plain L1: the points that cannot reach minimumHits go before the sort (k_filter_points)
-        if (!windowed && (!c->keepPoints || c->keepFiltered) && !fl.skipPrefix) {
-          hipLaunchKernelGGL(k_filter_points, dim3(gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(),
-                             c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), c->dPtKept.as<int32_t>(), nBigDev);
-          MM_HIP(c, hipGetLastError());
-        }
-      }
-      if (!windowed) hipLaunchKernelGGL(k_sort_points_wave, dim3(gWave), dim3(256), 0, c->stream, nBig, nBigDev, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>());
-      hipLaunchKernelGGL(k_classify_sort, dim3(gThread), dim3(256), 0, c->stream, nBig, nBigDev, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
-                         listB.as<int32_t>(), listC.as<int32_t>(), cls, windowed ? 1 : MM_SORT_WAVECAP);
-      MM_HIP(c, hipGetLastError());
-      unsigned int hcls[2] = {1024u, 16u};                    // steady: fixed grids over the two lists (their lengths stay on the device)
-      if (!steady) {
-        MM_HIP(c, hipMemcpyAsync(hcls, cls, 8, hipMemcpyDeviceToHost, c->stream));
-        MM_SYNC(c);
-        if (c->env.debug) fprintf(stderr, "[mm] point path: %d queued fragments, after the filter %u lists of more than %d points (LDS sorter), %u beyond the LDS sorter\n", nBig, hcls[0], MM_SORT_WAVECAP, hcls[1]);
-      }
-      if (hcls[0]) hipLaunchKernelGGL(k_sort_points_block, dim3(hcls[0]), dim3(256), 0, c->stream, cls, c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), listB.as<int32_t>(), sortIds);
-      if (hcls[1]) hipLaunchKernelGGL(k_sort_points_global, dim3(hcls[1]), dim3(1024), 0, c->stream, cls + 1, c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), listC.as<int32_t>(), sortIds);
-      MM_HIP(c, hipGetLastError());
-    }
-    for (int attempt = 0; attempt < 8; attempt++) {
-      // candidates of the fused path sit at [0, fusedL1); the sweep appends behind them, so a retry only rewinds to fusedL1
-      const unsigned long long fusedL1 = hc[2];
-      if (!steady) {
-        MM_HIP(c, hipMemcpyAsync(cnt + 2, &fusedL1, 8, hipMemcpyHostToDevice, c->stream));
-        MM_HIP(c, hipMemsetAsync(cnt + 3, 0, 8, c->stream));
-      }
-      {
-        KernelTimer t(c, MM_K_L1);
-        // a wave per fragment streams the sorted points; what it cannot take (a position group across two contigs, minimumHits 0) and
-        // every fragment under -Y reference groups goes to the literal one-thread-per-fragment kernel
-        const bool stream = !fl.skipPrefix && !c->env.l1Literal && !windowed;
-        const int32_t* sweepList = c->dBigList.as<int32_t>(); const unsigned int* sweepCount = nullptr;
-        if (windowed) {
-          const int nFreq = s > 256 ? s : 256;                                     // seeds are numbered by their index in the raw sketch
-          MM_HIP(c, c->dWinFreq.ensure((size_t)nBig * nFreq * 4 + 64));
-          hipLaunchKernelGGL(k_l1_window, dim3((nBig + 63) / 64), dim3(64), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dFrags.as<DFrag>(), c->dPtOff.as<int64_t>(),
-                             c->dPts.as<uint64_t>(), c->dPtIds.as<uint16_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
-                             (int)c->nCutoffs, s, c->P.segLength, fl, I.refGroup.as<int32_t>(), c->dWinFreq.as<int32_t>(), nFreq, c->dL1.as<mm_l1_candidate>(),
-                             (unsigned long long)denseCap, c->dL1Off.as<int64_t>(), cnt);
-          MM_HIP(c, hipGetLastError());
-        } else {
-        unsigned int* lit = cls + 2;                                               // [17]: the list k_l1_stream leaves over (cls itself still feeds the sorters in flight)
-        if (stream) {
-          MM_HIP(c, hipMemsetAsync(lit, 0, 8, c->stream));
-          hipLaunchKernelGGL(k_l1_stream, dim3(gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
-                             c->dPts.as<uint64_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
-                             (int)c->nCutoffs, s, c->P.segLength, fl.hg, c->dL1.as<mm_l1_candidate>(), (unsigned long long)denseCap,
-                             c->dL1Off.as<int64_t>(), listB.as<int32_t>(), lit, cnt, nBigDev, c->dPtKept.as<int32_t>());
-          MM_HIP(c, hipGetLastError());
-          sweepList = listB.as<int32_t>(); sweepCount = lit;
-        }
-        hipLaunchKernelGGL(k_l1_sweep, dim3(stream && steady ? 64u : gThread), dim3(256), 0, c->stream, nBig, sweepList, c->dPtOff.as<int64_t>(),
-                           c->dPts.as<uint64_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
-                           (int)c->nCutoffs, s, c->P.segLength, fl, I.refGroup.as<int32_t>(), c->dL1.as<mm_l1_candidate>(),
-                           (unsigned long long)denseCap, c->dL1Off.as<int64_t>(), cnt, sweepCount, sweepCount ? (const unsigned long long*)nullptr : nBigDev, c->dPtKept.as<int32_t>());
-        MM_HIP(c, hipGetLastError());
-        }
-      }
-      if (steady) break;
-      unsigned long long h2[2];
-      MM_HIP(c, hipMemcpyAsync(h2, cnt + 2, 16, hipMemcpyDeviceToHost, c->stream));
-      MM_SYNC(c);
-      if (h2[1]) {
-        // grow, keeping the fused candidates already in the buffer
-        const size_t newCap = (size_t)h2[0] + (size_t)h2[0] / 8 + 1024;
-        DevBuf nb; MM_HIP(c, nb.ensure(newCap * sizeof(mm_l1_candidate) + 64));
-        if (fusedL1) MM_HIP(c, hipMemcpyAsync(nb.p, c->dL1.p, (size_t)fusedL1 * sizeof(mm_l1_candidate), hipMemcpyDeviceToDevice, c->stream));
-        MM_SYNC(c);
-        c->dL1.release(); c->dL1 = nb; denseCap = newCap;
-        if (c->l1Cap < newCap) c->l1Cap = newCap;                  // the next pass sizes both candidate buffers for it: no retry, no reallocation
-        hc[3] = 1; continue;
-      }
-      hc[2] = h2[0]; hc[3] = 0;
-      break;
-    }
-    if (hc[3]) { c->err = "L1 candidate buffer overflow"; return MM_ERR_CAPACITY; }
-  }
-  if (!steady) {
-    c->nL1 = (size_t)hc[2];
-    c->prevBig = c->lastBig = (size_t)nBig;
-    c->prevMid = c->lastMid = (size_t)hMid; c->midKnown = useMid;
-    if (c->nL1 == 0) { c->nL2 = 0; return rc; }
-  }
-  if (steady) {
-    // candidates the buffers of this pass hold: what the previous (sized) pass left of candidate-indexed staging, and the dense L1 buffer itself
-    const unsigned long long cap = (unsigned long long)std::min(c->candCap, denseCap);
-    hipLaunchKernelGGL(k_l1_gate, dim3(1), dim3(1), 0, c->stream, cnt, cap);
+  if (p.hc[MM_PC_POINT_OVERFLOW]) { c->err = "interval-point buffer overflow"; return MM_ERR_CAPACITY; }
+  if (p.hc[MM_PC_L1_OVERFLOW]) { c->err = "L1 candidate buffer overflow"; return MM_ERR_CAPACITY; }
+  return MM_OK;
+}
+
+// stage 3: the fused kernels' candidates, one region per cursor, become one dense array.  The regions' prefix positions and the number
+// of fused candidates (MM_PC_L1_CAND) are computed on the device; the sized pass knows them from the cursors it has read
+static int pass_compact(mm_ctx* c, MapPass& p) {
+  unsigned long long* const cnt = p.cnt;
+  unsigned long long tot = 0;
+  for (int r = 0; r < MM_L1_REGIONS; r++) tot += p.hcur[(size_t)r * MM_L1_CURSOR_STRIDE];
+  p.hc[MM_PC_L1_CAND] = p.steady ? 0 : tot;
+  if (p.steady || tot) {
+    KernelTimer t(c, MM_K_L1);
+    hipLaunchKernelGGL(k_l1_regions, dim3(1), dim3(64), 0, c->stream, c->dL1Cursors.as<unsigned long long>(), p.regionCap, c->dL1Regions.as<L1Regions>(), cnt);
+    hipLaunchKernelGGL(k_l1_compact, dim3(64, MM_L1_REGIONS), dim3(256), 0, c->stream, c->dL1.as<mm_l1_candidate>(), c->dL1b.as<mm_l1_candidate>(), p.regionCap, c->dL1Regions.as<L1Regions>());
+    hipLaunchKernelGGL(k_l1_fix_offsets, dim3((p.nF + 255) / 256), dim3(256), 0, c->stream, p.nF, c->dStats.as<mm_frag_stats>(), c->dL1Off.as<int64_t>(), p.regionCap, c->dL1Regions.as<L1Regions>());
     MM_HIP(c, hipGetLastError());
   }
-  rc = mm_launch_l2(c, cnt, steady);
-  if (rc != MM_OK) return rc;
-  rc = mm_launch_select(c, steady);
-  if (rc != MM_OK) return rc;
-  if (steady) {
-    // the pass is over: one block of counters comes back
-    unsigned long long* h = c->hPass;
-    MM_HIP(c, hipMemcpyAsync(h, cnt, 64, hipMemcpyDeviceToHost, c->stream));
-    MM_HIP(c, hipMemcpyAsync(h + 8, cnt2, 64, hipMemcpyDeviceToHost, c->stream));
-    MM_HIP(c, hipMemcpyAsync(h + 16, c->dCounters.as<unsigned long long>() + 48, 8, hipMemcpyDeviceToHost, c->stream));
-    MM_SYNC(c);
-    c->lastHard = (size_t)(h[16] & 0xffffffffull);
-    if (h[1] || h[3] || h[5] || (h[6] & ~0ull) || h[9]) return MM_PASS_REDO;   // some buffer was too small for this batch: the sized pass grows it
-    c->nL1 = (size_t)h[2]; c->nL2 = (size_t)h[4]; c->nMappings = c->haveReplayTables ? (size_t)h[8] : 0;
-    c->lastOps = (size_t)h[10]; c->lastBig = c->prevBig;          // (the queue's length was overwritten by the L2 stage's list counter: the sized pass's stands in)
+  std::swap(c->dL1, c->dL1b);                               // dL1 is the dense buffer from here on
+  p.denseCap = c->dL1.bytes / sizeof(mm_l1_candidate) - 4;  // room behind the fused candidates for the sweep path's
+  p.nBig = (int)p.hc[MM_PC_BIG_LEN];
+  if (c->env.debug) {
+    if (p.steady) fprintf(stderr, "[mm] lookup+L1: %d fragments, steady-state pass (the counts stay on the device)\n", p.nF);
+    else fprintf(stderr, "[mm] lookup+L1: %d fragments, %llu through k_lookup_mid, %d to the sort+sweep path, %llu fused candidates\n", p.nF, p.hMid, p.nBig, p.hc[MM_PC_L1_CAND]);
   }
   return MM_OK;
+}
+
+// stage 4, the HBM point path: the queued fragments' interval points gathered, filtered and sorted (by the sorter their number asks for)
+static int pass_point_path(mm_ctx* c, MapPass& p) {
+  const DeviceIndex& I = c->idx;
+  const int nBig = p.nBig, s = p.s;
+  // grids over the queued fragments: exact when their number is known, otherwise sized by what the previous pass saw (the kernels
+  // walk the list with whatever grid they get)
+  const int nB = p.steady ? (int)std::min<size_t>(c->prevBig + c->prevBig / 2 + 1024, (size_t)p.nF) : nBig;
+  p.gWave = (unsigned)((nB + 3) / 4); p.gThread = (unsigned)((nB + 255) / 256);
+  KernelTimer t(c, MM_K_SORT);
+  uint16_t* sortIds = p.windowed ? c->dPtIds.as<uint16_t>() : (uint16_t*)nullptr;
+  auto gk = I.tagged ? k_gather_points<true> : k_gather_points<false>;
+  hipLaunchKernelGGL(gk, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), s, c->dFrags.as<DFrag>(), c->dSkHash.as<uint64_t>(),
+                     c->dSkCount.as<uint32_t>(), p.seedTab, I.ptKeys.as<uint64_t>(), I.refGroup.as<int32_t>(),
+                     c->dReadGroup.as<int32_t>(), c->dReadSelf.as<int32_t>(), c->seqCounterBase, p.fl, c->dStats.as<mm_frag_stats>(), c->dPtOff.as<int64_t>(),
+                     c->dPts.as<uint64_t>(), sortIds, c->dPtKept.as<int32_t>(), p.nBigDev);
+  MM_HIP(c, hipGetLastError());
+  // split mode, plain L1: the points that cannot reach minimumHits go before the sort (k_filter_points)
+  if (!p.windowed && (!c->keepPoints || c->keepFiltered) && !p.fl.skipPrefix) {
+    hipLaunchKernelGGL(k_filter_points, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(),
+                       c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), c->dPtKept.as<int32_t>(), p.nBigDev);
+    MM_HIP(c, hipGetLastError());
+  }
+  if (!p.windowed) hipLaunchKernelGGL(k_sort_points_wave, dim3(p.gWave), dim3(256), 0, c->stream, nBig, p.nBigDev, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>());
+  hipLaunchKernelGGL(k_classify_sort, dim3(p.gThread), dim3(256), 0, c->stream, nBig, p.nBigDev, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
+                     c->dListB.as<int32_t>(), c->dListC.as<int32_t>(), p.lens, p.windowed ? 1 : MM_SORT_WAVECAP);
+  MM_HIP(c, hipGetLastError());
+  unsigned int hLens[MM_SL_LITERAL] = {1024u, 16u};         // the two sorter lists (the words before MM_SL_LITERAL).  steady: fixed grids over the two lists (their lengths stay on the device)
+  if (!p.steady) {
+    MM_HIP(c, hipMemcpyAsync(hLens, p.lens, sizeof hLens, hipMemcpyDeviceToHost, c->stream));
+    MM_SYNC(c);
+    if (c->env.debug) fprintf(stderr, "[mm] point path: %d queued fragments, after the filter %u lists of more than %d points (LDS sorter), %u beyond the LDS sorter\n", nBig, hLens[MM_SL_BLOCK], MM_SORT_WAVECAP, hLens[MM_SL_GLOBAL]);
+  }
+  if (hLens[MM_SL_BLOCK]) hipLaunchKernelGGL(k_sort_points_block, dim3(hLens[MM_SL_BLOCK]), dim3(256), 0, c->stream, p.lens + MM_SL_BLOCK, c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), c->dListB.as<int32_t>(), sortIds);
+  if (hLens[MM_SL_GLOBAL]) hipLaunchKernelGGL(k_sort_points_global, dim3(hLens[MM_SL_GLOBAL]), dim3(1024), 0, c->stream, p.lens + MM_SL_GLOBAL, c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), c->dListC.as<int32_t>(), sortIds);
+  MM_HIP(c, hipGetLastError());
+  return MM_OK;
+}
+
+// stage 5: L1 over the sorted points.  The candidates of the fused path sit at [0, fusedL1) of the dense buffer; the sweeps append
+// behind them, so a sized pass whose buffer was too small grows it and rewinds to fusedL1 only
+static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
+  const DeviceIndex& I = c->idx;
+  const int nBig = p.nBig, s = p.s;
+  unsigned long long* const cnt = p.cnt;
+  const unsigned long long fusedL1 = p.hc[MM_PC_L1_CAND];
+  for (int attempt = 0; attempt < 8; attempt++) {
+    if (!p.steady) {
+      MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L1_CAND, &fusedL1, 8, hipMemcpyHostToDevice, c->stream));
+      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L1_OVERFLOW, 0, 8, c->stream));
+    }
+    {
+      KernelTimer t(c, MM_K_L1);
+      // a wave per fragment streams the sorted points; what it cannot take (a position group across two contigs, minimumHits 0) and
+      // every fragment under -Y reference groups goes to the literal one-thread-per-fragment kernel
+      const bool stream = !p.fl.skipPrefix && !c->env.l1Literal && !p.windowed;
+      const int32_t* sweepList = c->dBigList.as<int32_t>(); const unsigned int* sweepCount = nullptr;
+      if (p.windowed) {
+        const int nFreq = s > 256 ? s : 256;                                     // seeds are numbered by their index in the raw sketch
+        MM_HIP(c, c->dWinFreq.ensure((size_t)nBig * nFreq * 4 + 64));
+        hipLaunchKernelGGL(k_l1_window, dim3((nBig + 63) / 64), dim3(64), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dFrags.as<DFrag>(), c->dPtOff.as<int64_t>(),
+                           c->dPts.as<uint64_t>(), c->dPtIds.as<uint16_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
+                           (int)c->nCutoffs, s, c->P.segLength, p.fl, I.refGroup.as<int32_t>(), c->dWinFreq.as<int32_t>(), nFreq, c->dL1.as<mm_l1_candidate>(),
+                           (unsigned long long)p.denseCap, c->dL1Off.as<int64_t>(), cnt);
+        MM_HIP(c, hipGetLastError());
+      } else {
+        unsigned int* lit = p.lens + MM_SL_LITERAL;
+        if (stream) {
+          MM_HIP(c, hipMemsetAsync(lit, 0, (size_t)(MM_SL_END - MM_SL_LITERAL) * 4, c->stream));
+          hipLaunchKernelGGL(k_l1_stream, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
+                             c->dPts.as<uint64_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
+                             (int)c->nCutoffs, s, c->P.segLength, p.fl.hg, c->dL1.as<mm_l1_candidate>(), (unsigned long long)p.denseCap,
+                             c->dL1Off.as<int64_t>(), c->dListB.as<int32_t>(), lit, cnt, p.nBigDev, c->dPtKept.as<int32_t>());
+          MM_HIP(c, hipGetLastError());
+          sweepList = c->dListB.as<int32_t>(); sweepCount = lit;
+        }
+        hipLaunchKernelGGL(k_l1_sweep, dim3(stream && p.steady ? 64u : p.gThread), dim3(256), 0, c->stream, nBig, sweepList, c->dPtOff.as<int64_t>(),
+                           c->dPts.as<uint64_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
+                           (int)c->nCutoffs, s, c->P.segLength, p.fl, I.refGroup.as<int32_t>(), c->dL1.as<mm_l1_candidate>(),
+                           (unsigned long long)p.denseCap, c->dL1Off.as<int64_t>(), cnt, sweepCount, sweepCount ? (const unsigned long long*)nullptr : p.nBigDev, c->dPtKept.as<int32_t>());
+        MM_HIP(c, hipGetLastError());
+      }
+    }
+    if (p.steady) return MM_OK;
+    MM_HIP(c, hipMemcpyAsync(p.hc + MM_PC_L1_CAND, cnt + MM_PC_L1_CAND, 16, hipMemcpyDeviceToHost, c->stream));   // the cursor and its overflow flag
+    MM_SYNC(c);
+    if (!p.hc[MM_PC_L1_OVERFLOW]) return MM_OK;
+    // grow, keeping the fused candidates already in the buffer
+    const size_t newCap = (size_t)p.hc[MM_PC_L1_CAND] + (size_t)p.hc[MM_PC_L1_CAND] / 8 + 1024;
+    DevBuf nb; MM_HIP(c, nb.ensure(newCap * sizeof(mm_l1_candidate) + 64));
+    if (fusedL1) MM_HIP(c, hipMemcpyAsync(nb.p, c->dL1.p, (size_t)fusedL1 * sizeof(mm_l1_candidate), hipMemcpyDeviceToDevice, c->stream));
+    MM_SYNC(c);
+    c->dL1.release(); c->dL1 = nb; p.denseCap = newCap;
+    if (c->l1Cap < newCap) c->l1Cap = newCap;                  // the next pass sizes both candidate buffers for it: no retry, no reallocation
+  }
+  c->err = "L1 candidate buffer overflow"; return MM_ERR_CAPACITY;
+}
+
+// stage 6: gate (steady), L2, selection; a steady-state pass then reads its counters back -- the pass's one synchronisation -- and
+// says whether it stands
+static int pass_finish(mm_ctx* c, MapPass& p) {
+  if (p.steady) {
+    // candidates the buffers of this pass hold: what the previous (sized) pass left of candidate-indexed staging, and the dense L1 buffer itself
+    const unsigned long long cap = (unsigned long long)std::min(c->candCap, p.denseCap);
+    hipLaunchKernelGGL(k_l1_gate, dim3(1), dim3(1), 0, c->stream, p.cnt, cap);
+    MM_HIP(c, hipGetLastError());
+  }
+  int rc = mm_launch_l2(c, p.cnt, p.steady);
+  if (rc != MM_OK) return rc;
+  rc = mm_launch_select(c, p.steady);
+  if (rc != MM_OK || !p.steady) return rc;
+  // the pass is over: the parts of the counter block it has written come back, each to its place in the mirror
+  const unsigned long long* all = c->dCounters.as<unsigned long long>();
+  MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_PASS, all + MM_CW_PASS, (size_t)MM_PC_READ * 8, hipMemcpyDeviceToHost, c->stream));
+  MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_MAP, all + MM_CW_MAP, (size_t)(MM_CW_MAP_END - MM_CW_MAP) * 8, hipMemcpyDeviceToHost, c->stream));
+  MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_HARD_COPY, all + MM_CW_HARD_COPY, 8, hipMemcpyDeviceToHost, c->stream));
+  MM_SYNC(c);
+  const unsigned long long* h = c->hPass + MM_CW_PASS; const unsigned long long* hm = c->hPass + MM_CW_MAP;
+  c->lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
+  if (mm_pass_incomplete(h) || hm[MM_MC_OVERFLOW]) return MM_PASS_REDO;   // some buffer was too small for this batch: the sized pass grows it
+  c->nL1 = (size_t)h[MM_PC_L1_CAND]; c->nL2 = (size_t)h[MM_PC_L2_LOCI]; c->nMappings = c->haveReplayTables ? (size_t)hm[MM_MC_MAPPINGS] : 0;
+  c->lastOps = (size_t)hm[MM_MC_L2_OPS]; c->lastBig = c->prevBig;         // (MM_PC_BIG_LEN holds MM_PC_L2_WIDE_LEN by now: the sized pass's figure stands in)
+  return MM_OK;
+}
+
+static int map_pass(mm_ctx* c, const bool steady) {
+  MapPass p; p.steady = steady;
+  int rc = pass_prepare(c, p);
+  if (rc == MM_OK) rc = pass_lookup(c, p);
+  if (rc == MM_OK) rc = pass_compact(c, p);
+  if (rc == MM_OK && (steady || p.nBig > 0)) {
+    rc = pass_point_path(c, p);
+    if (rc == MM_OK) rc = pass_l1_sweeps(c, p);
+  }
+  if (rc != MM_OK) return rc;
+  if (!steady) {
+    c->nL1 = (size_t)p.hc[MM_PC_L1_CAND];
+    c->prevBig = c->lastBig = (size_t)p.nBig;
+    c->prevMid = c->lastMid = (size_t)p.hMid; c->midKnown = p.useMid;
+    if (c->nL1 == 0) { c->nL2 = 0; return MM_OK; }
+  }
+  return pass_finish(c, p);
 }
 
 int mm_launch_map(mm_ctx* c) {
@@ -1693,8 +1746,8 @@ int mm_launch_map(mm_ctx* c) {
   MM_HIP(c, c->dQHash.ensure(cF * s * 8 + 64)); MM_HIP(c, c->dQStrand.ensure(cF * s + 64));
   MM_HIP(c, c->dStats.ensure(cF * sizeof(mm_frag_stats) + 64));
   MM_HIP(c, c->dPtOff.ensure(cF * 16 + 64)); MM_HIP(c, c->dL1Off.ensure(cF * 8 + 64)); MM_HIP(c, c->dPtKept.ensure(cF * 4 + 64));
-  MM_HIP(c, c->dCounters.ensure(512));
-  if (!c->hPass) { MM_HIP(c, hipHostMalloc((void**)&c->hPass, 256, hipHostMallocDefault)); }
+  MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
+  if (!c->hPass) { MM_HIP(c, hipHostMalloc((void**)&c->hPass, MM_COUNTER_BYTES, hipHostMallocDefault)); }
   c->nL1 = c->nL2 = 0; c->nMappings = 0; c->nSyncs = 0; c->lastSteady = false;
   if (nF == 0) return MM_OK;
   const bool allSlow = c->keepPoints || (c->P.flags & MM_FLAG_SKIP_PREFIX) || c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH;

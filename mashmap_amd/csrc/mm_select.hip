@@ -26,16 +26,16 @@ struct SelectArgs {
 template <bool WRITE>
 __global__ void __launch_bounds__(256)
 k_l2_select(SelectArgs A, int32_t* __restrict__ counts, const int64_t* __restrict__ outOff, mm_mapping* __restrict__ out,
-            const int64_t* __restrict__ totalDev, long long outCap, unsigned long long* __restrict__ result /* steady-state passes: [0] = total, [1] = 1 if it exceeds outCap */,
-            const unsigned long long* __restrict__ passCnt /* steady-state passes: the pass's counters; any overflow flag = the stages before this one are incomplete */) {
+            const int64_t* __restrict__ totalDev, long long outCap, unsigned long long* __restrict__ result /* steady-state passes: dCounters + MM_CW_MAP -- the total, and whether it exceeds outCap */,
+            const unsigned long long* __restrict__ passCnt /* steady-state passes: dCounters + MM_CW_PASS; any overflow flag = the stages before this one are incomplete */) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (passCnt && (passCnt[1] | passCnt[3] | passCnt[5] | passCnt[6])) {     // the pass will be redone with the host's sizing: nothing here may be trusted (or dereferenced)
+  if (passCnt && mm_pass_incomplete(passCnt)) {     // the pass will be redone with the host's sizing: nothing here may be trusted (or dereferenced)
     if (!WRITE && f < A.nFrags) counts[f] = 0;
     return;
   }
   if (WRITE && totalDev) {
     const long long total = (long long)*totalDev;
-    if (f == 0) { result[0] = (unsigned long long)total; if (total > outCap) result[1] = 1ull; }
+    if (f == 0) { result[MM_MC_MAPPINGS] = (unsigned long long)total; if (total > outCap) result[MM_MC_OVERFLOW] = MM_OVERFLOWED; }
     if (total > outCap) return;                              // the records do not fit the buffer as it is: the pass is redone with the host's sizing
   }
   if (f >= A.nFrags) return;
@@ -87,17 +87,17 @@ int mm_launch_select(mm_ctx* c, bool steady) {
   A.heap = c->dSelHeap.as<int32_t>();
   KernelTimer t(c, MM_K_SELECT);
   hipLaunchKernelGGL((k_l2_select<false>), dim3((nF + 255) / 256), dim3(256), 0, c->stream, A, c->dSelCnt.as<int32_t>(), (const int64_t*)nullptr, (mm_mapping*)nullptr,
-                     (const int64_t*)nullptr, 0ll, (unsigned long long*)nullptr, steady ? (const unsigned long long*)(c->dCounters.as<unsigned long long>() + 8) : (const unsigned long long*)nullptr);
+                     (const int64_t*)nullptr, 0ll, (unsigned long long*)nullptr, steady ? (const unsigned long long*)(c->dCounters.as<unsigned long long>() + MM_CW_PASS) : (const unsigned long long*)nullptr);
   MM_HIP(c, hipGetLastError());
   if (steady) {
     // the records' number stays on the device: the writing pass checks it against the buffer as the previous pass left it and
-    // reports both in the counters the launcher reads when the pass is over (dCounters[32], [33])
+    // reports both in the counters the launcher reads when the pass is over (MM_CW_MAP: MM_MC_MAPPINGS, MM_MC_OVERFLOW)
     const int64_t* dTotal = nullptr;
     const int rc = mm_scan_i32_to_i64_dev(c, nF, c->dSelCnt.as<int32_t>(), c->dSelOff.as<int64_t>(), &dTotal);
     if (rc != MM_OK) return rc;
     const long long cap = (long long)(c->dMappings.bytes / sizeof(mm_mapping)) - 2;
     hipLaunchKernelGGL((k_l2_select<true>), dim3((nF + 255) / 256), dim3(256), 0, c->stream, A, (int32_t*)nullptr, c->dSelOff.as<int64_t>(), c->dMappings.as<mm_mapping>(),
-                       dTotal, cap, c->dCounters.as<unsigned long long>() + 32, (const unsigned long long*)(c->dCounters.as<unsigned long long>() + 8));
+                       dTotal, cap, c->dCounters.as<unsigned long long>() + MM_CW_MAP, (const unsigned long long*)(c->dCounters.as<unsigned long long>() + MM_CW_PASS));
     MM_HIP(c, hipGetLastError());
     return MM_OK;
   }

@@ -58,9 +58,11 @@ __global__ void k_pack2bit(const uint8_t* __restrict__ ascii, const int64_t* __r
 #define MM_SK_PADH 256             // hard kernel
 #define MM_SK_DUPCAP 256          // repeat occurrences a fast-kernel fragment may defer (more: the hard kernel takes the fragment)
 #define MM_SK_GUARD 4             // always-empty slots on either side of the table: the ranking reads windows of that many neighbours
+// slots of `counters`, the four LDS words each sketch table keeps beside itself (not mm_ctx::dCounters)
+enum : int { MM_TC_KEYS = 0 /* distinct keys */, MM_TC_OVERFLOW = 1 /* load limit passed, spill area or duplicate list full */, MM_TC_OCCUPIED = 2 /* occupied slots */, MM_TC_DUPS = 3 /* deferred duplicates (fast kernel) */ };
 struct SkTable {                  // the hard kernel's table: every occurrence is folded in with atomics as it is hashed
   uint64_t* key; int32_t* first; int32_t* last; int32_t* sum;
-  uint32_t* counters;            // [0] distinct keys  [1] overflow (load limit passed, spill area full)  [2] occupied slots
+  uint32_t* counters;            // MM_TC_KEYS, MM_TC_OVERFLOW, MM_TC_OCCUPIED
   uint64_t* occW; uint32_t* occP; // occupancy bit words and their exclusive prefix counts
   uint32_t nSlots, maxLoad, M; int sh;
 
@@ -73,23 +75,23 @@ struct SkTable {                  // the hard kernel's table: every occurrence i
   }
   __device__ __forceinline__ uint32_t home(uint64_t h) const { return __umulhi((uint32_t)((h << sh) >> 32), M); }
 
-  // the number of distinct keys is kept in counters[0] and the load limit flagged as it is passed: the kernel inserts straight from
+  // the number of distinct keys is kept in counters[MM_TC_KEYS] and the load limit flagged as it is passed: the kernel inserts straight from
   // the hash loop and must notice a flooded table early
   __device__ __forceinline__ void insert(uint64_t h, int pos, int st) {
     uint32_t slot = home(h);
     for (uint32_t probes = 1;; probes++) {
       // a flooded table (cut still too high) is abandoned early; looked at every 16th probe only, the volatile generic load is slow
-      if ((probes & 15u) == 0 && ((volatile uint32_t*)counters)[1]) return;
+      if ((probes & 15u) == 0 && ((volatile uint32_t*)counters)[MM_TC_OVERFLOW]) return;
       const unsigned long long prev = atomicCAS((unsigned long long*)&key[slot], (unsigned long long)MM_HASH_MAX,
                                                 (unsigned long long)h);
       if (prev == MM_HASH_MAX) {
-        if (atomicAdd(&counters[0], 1u) >= maxLoad) atomicOr(&counters[1], 1u);
+        if (atomicAdd(&counters[MM_TC_KEYS], 1u) >= maxLoad) atomicOr(&counters[MM_TC_OVERFLOW], 1u);
       }
       if (prev == MM_HASH_MAX || prev == h) {
         atomicMin(&first[slot], pos); atomicMax(&last[slot], pos); atomicAdd(&sum[slot], st);
         return;
       }
-      if (++slot >= nSlots) { atomicOr(&counters[1], 1u); return; }
+      if (++slot >= nSlots) { atomicOr(&counters[MM_TC_OVERFLOW], 1u); return; }
     }
   }
 };
@@ -258,12 +260,12 @@ mm_sketch_hard(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
         if (w < nOcc) tab.occP[w] = (uint32_t)(carry + ex);
         carry += mm_wave_sum(v);
       }
-      if (tid == 0) tab.counters[2] = (uint32_t)carry;
+      if (tid == 0) tab.counters[MM_TC_OCCUPIED] = (uint32_t)carry;
     }
     __syncthreads();
 
-    D = tab.counters[2];
-    const bool overflow = tab.counters[1] != 0;
+    D = tab.counters[MM_TC_OCCUPIED];
+    const bool overflow = tab.counters[MM_TC_OVERFLOW] != 0;
     if (overflow) { hi = T; hiInf = false; }
     else if (D < (uint32_t)s && T != MM_HASH_MAX) { lo = T; }
     else break;
@@ -350,7 +352,7 @@ k_sketch_all_hard(int nF, int32_t* __restrict__ hardList, uint32_t* __restrict__
 #define MM_SKF_FLAG 0x80000000u
 struct SkFast {
   uint64_t* key; uint32_t* meta;      // meta: bit 31 = has entries on the duplicate list, low bits = pos << 1 | (strand > 0) of the owner
-  uint32_t* dup; uint32_t* counters;  // counters: [1] overflow  [2] occupied slots  [3] duplicates
+  uint32_t* dup; uint32_t* counters;  // counters: MM_TC_OVERFLOW, MM_TC_OCCUPIED, MM_TC_DUPS
   uint64_t* occW; uint32_t* occP;
   uint32_t nSlots, maxLoad, M; int sh;
   __device__ __forceinline__ void set_cut(uint64_t T, uint32_t HT) {
@@ -365,11 +367,11 @@ struct SkFast {
       const unsigned long long prev = atomicCAS((unsigned long long*)&key[slot], (unsigned long long)MM_HASH_MAX, (unsigned long long)h);
       if (prev == MM_HASH_MAX) { meta[slot] = m; return; }                     // the owner: a plain store, nobody reads it before the barrier
       if (prev == h) {
-        const uint32_t at = atomicAdd(&counters[3], 1u);
-        if (at < MM_SK_DUPCAP) dup[at] = slot | (m << 13); else atomicOr(&counters[1], 1u);
+        const uint32_t at = atomicAdd(&counters[MM_TC_DUPS], 1u);
+        if (at < MM_SK_DUPCAP) dup[at] = slot | (m << 13); else atomicOr(&counters[MM_TC_OVERFLOW], 1u);
         return;
       }
-      if (++slot >= nSlots) { atomicOr(&counters[1], 1u); return; }
+      if (++slot >= nSlots) { atomicOr(&counters[MM_TC_OVERFLOW], 1u); return; }
     }
   }
 };
@@ -495,11 +497,11 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   {
     // lanes that left the strip loop early (or never entered it) hold a stale count; lane 0 owns the smallest strip
     const uint32_t qCount = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qHead - qBase));
-    if (mm_lane() == 0) { qCnt[tid >> 6] = qCount; if (qCount > (uint32_t)QC) atomicOr(&tab.counters[1], 1u); }
+    if (mm_lane() == 0) { qCnt[tid >> 6] = qCount; if (qCount > (uint32_t)QC) atomicOr(&tab.counters[MM_TC_OVERFLOW], 1u); }
   }
   __syncthreads();
   mark(2);                                          // waiting for the other waves' hash loops
-  if (tab.counters[1] == 0) {
+  if (tab.counters[MM_TC_OVERFLOW] == 0) {
     // all threads drain all queues: entry g of the concatenated queues goes to thread g mod nthr, so every round of inserts is full
     uint32_t pre[17]; pre[0] = 0;
 #pragma unroll
@@ -528,7 +530,7 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   mark(3);                                          // queues drained into the table
   {
     // owners' stores are visible now: flag the slots that have entries on the duplicate list
-    const uint32_t nd = tab.counters[3] < MM_SK_DUPCAP ? tab.counters[3] : MM_SK_DUPCAP;
+    const uint32_t nd = tab.counters[MM_TC_DUPS] < MM_SK_DUPCAP ? tab.counters[MM_TC_DUPS] : MM_SK_DUPCAP;
     for (uint32_t i = (uint32_t)tid; i < nd; i += (uint32_t)nthr) atomicOr(&tab.meta[tab.dup[i] & 0x1FFFu], MM_SKF_FLAG);
   }
   // ---- occupancy words, their prefix counts (wave 0: one DPP scan per 64 words), number of distinct keys ----
@@ -549,13 +551,13 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
       if (w < nOcc) tab.occP[w] = (uint32_t)(carry + ex);
       carry += mm_wave_sum(v);
     }
-    if (tid == 0) { tab.counters[2] = (uint32_t)carry; if ((uint32_t)carry > tab.maxLoad) tab.counters[1] = 1u; }
+    if (tid == 0) { tab.counters[MM_TC_OCCUPIED] = (uint32_t)carry; if ((uint32_t)carry > tab.maxLoad) tab.counters[MM_TC_OVERFLOW] = 1u; }
   }
   __syncthreads();
-  const uint32_t D = tab.counters[2];
-  if (tab.counters[1] != 0 || (D < (uint32_t)s && T != MM_HASH_MAX)) {
+  const uint32_t D = tab.counters[MM_TC_OCCUPIED];
+  if (tab.counters[MM_TC_OVERFLOW] != 0 || (D < (uint32_t)s && T != MM_HASH_MAX)) {
     // skCount[f] carries the first hint for the hard kernel's cut: the distinct count under this one, unless something overflowed
-    if (tid == 0) { const uint32_t at = atomicAdd(hardCount, 1u); hardList[at] = f; skCount[f] = tab.counters[1] != 0 ? MM_SK_HINT_OVERFLOW : D; }
+    if (tid == 0) { const uint32_t at = atomicAdd(hardCount, 1u); hardList[at] = f; skCount[f] = tab.counters[MM_TC_OVERFLOW] != 0 ? MM_SK_HINT_OVERFLOW : D; }
     return;
   }
   // the occupied slots in slot order (the queue memory is free again): every thread then ranks D / nthr keys instead of visiting
@@ -569,7 +571,7 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   mark(4);                                          // duplicate flags, occupancy, prefix counts, list of occupied slots
 
   // ---- rank every key inside its cluster; emit the s smallest, ascending (commonFunc.hpp:278-286) ----
-  const uint32_t nDup = tab.counters[3];
+  const uint32_t nDup = tab.counters[MM_TC_DUPS];
   for (int it = tid; it < (int)D; it += nthr) {
     const int slot = (int)occList[it];
     const uint64_t k = tab.key[slot];
@@ -824,9 +826,9 @@ static int launch_sketch_k(mm_ctx* c) {
     MM_HIP(c, hipGetLastError());
     c->sketchTabsK = K;
   }
-  MM_HIP(c, hipMemsetAsync(c->dCounters.p, 0, 64, c->stream));
+  MM_HIP(c, hipMemsetAsync(c->dCounters.as<unsigned long long>() + MM_CW_SKETCH, 0, (size_t)(MM_CW_SKETCH_END - MM_CW_SKETCH) * 8, c->stream));
   unsigned long long* phaseStats = nullptr;
-  if (c->env.sketchStats) { phaseStats = c->dCounters.as<unsigned long long>() + 24; MM_HIP(c, hipMemsetAsync(phaseStats, 0, 64, c->stream)); }
+  if (c->env.sketchStats) { phaseStats = c->dCounters.as<unsigned long long>() + MM_CW_SKETCH_PHASES; MM_HIP(c, hipMemsetAsync(phaseStats, 0, (size_t)(MM_CW_SKETCH_PHASES_END - MM_CW_SKETCH_PHASES) * 8, c->stream)); }
   if (plan.useFast) {
     KernelTimer t(c, MM_K_SKETCH);
     auto launch = [&](auto kern) {
@@ -846,8 +848,8 @@ static int launch_sketch_k(mm_ctx* c) {
     MM_HIP(c, hipGetLastError());
   }
   if (phaseStats && plan.useFast) {
-    unsigned long long h[8];
-    MM_HIP(c, hipMemcpyAsync(h, phaseStats, 64, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long h[MM_CW_SKETCH_PHASES_END - MM_CW_SKETCH_PHASES];
+    MM_HIP(c, hipMemcpyAsync(h, phaseStats, sizeof h, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipStreamSynchronize(c->stream));
     fprintf(stderr, "[mm] sketch phases, shader-clock cycles per workgroup (thread 0), %d fragments, %d threads x %d positions, HT %d, queue %d/wave, lds %zu: stage+init %.0f | hash %.0f | wait %.0f | drain %.0f | occupancy+list %.0f | rank+emit %.0f\n",
             nF, g.threads, g.SL, g.HT, g.QC, ldsFast, (double)h[0] / nF, (double)h[1] / nF, (double)h[2] / nF, (double)h[3] / nF, (double)h[4] / nF, (double)h[5] / nF);
@@ -894,14 +896,14 @@ static int launch_hash_only_k(mm_ctx* c, int reps, double* msAvg) {
     MM_HIP(c, hipGetLastError());
     c->sketchTabsK = K;
   }
-  MM_HIP(c, c->dCounters.ensure(256));
+  MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
   float total = 0;
   for (int r = 0; r <= reps; r++) {                 // launch 0 is a warm-up
     MM_HIP(c, hipEventRecord(c->evA, c->stream));
     auto launch = [&](auto kern) {
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL(kern, dim3(nF), dim3(g.threads), lds, c->stream, c->dSketchTabs.as<uint4>(), c->dBases2.as<uint32_t>(), c->dFrags.as<DFrag>(),
-                         c->dCounters.as<uint64_t>() + 24);
+                         c->dCounters.as<uint64_t>() + MM_CW_SKETCH_PHASES);   // the sink (never stored to)
     };
     if constexpr (MMHasSL20<K>::value) { if (g.SL == 20) launch(k_hash_only<K, 20>); else launch(k_hash_only<K, 16>); }
     else launch(k_hash_only<K, 16>);
@@ -932,7 +934,7 @@ int mm_launch_sketch(mm_ctx* c) {
   if (s > MM_LDS_MAX_SKETCH) {
     MM_HIP(c, c->dSkHash.ensure(nF * s * 8 + 64)); MM_HIP(c, c->dSkPos.ensure(nF * s * 8 + 64));
     MM_HIP(c, c->dSkStrand.ensure(nF * s + 64)); MM_HIP(c, c->dSkCount.ensure(nF * 4 + 64));
-    MM_HIP(c, c->dHardList.ensure(nF * 4 + 64)); MM_HIP(c, c->dCounters.ensure(512));
+    MM_HIP(c, c->dHardList.ensure(nF * 4 + 64)); MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
     return mm_launch_sketch_global(c);
   }
   MM_HIP(c, c->dSkHash.ensure(cF * s * 8 + 64));
@@ -940,7 +942,7 @@ int mm_launch_sketch(mm_ctx* c) {
   MM_HIP(c, c->dSkStrand.ensure(cF * s + 64));
   MM_HIP(c, c->dSkCount.ensure(cF * 4 + 64));
   MM_HIP(c, c->dHardList.ensure(cF * 4 + 64));
-  MM_HIP(c, c->dCounters.ensure(256));
+  MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
   if (nF == 0) return MM_OK;
   switch (c->P.kmerSize) {
 #define MM_CASE(KK) case KK: return launch_sketch_k<KK>(c);
