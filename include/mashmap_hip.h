@@ -281,6 +281,25 @@ int mm_pass_stats(const mm_ctx* ctx, uint64_t* hostSyncs, int* steady, uint64_t*
 /* The context's mm_map_fragments calls so far: all of them, those that went through as steady-state passes (one host wait), and the
  * steady-state attempts that outgrew a buffer and were redone the sized way.  Any pointer may be NULL. */
 int mm_pass_totals(const mm_ctx* ctx, uint64_t* passes, uint64_t* steadyPasses, uint64_t* redonePasses);
+/* Why the last mm_map_fragments had its steady-state attempt redone the sized way: *cause = MM_REDO_* bits, taken from the one counter
+ * block that attempt read back (nothing more is read or waited for); 0 when the last mm_map_fragments went through as a steady-state
+ * pass or made no steady-state attempt.  A stage that overflows silences the stages behind it, so the bits name the FIRST stages that
+ * ran out of room, not everything the sized pass then had to grow. */
+enum {
+  MM_REDO_POINTS    = 1,    /* the interval-point buffer of the HBM point path */
+  MM_REDO_L1        = 2,    /* the L1 candidate buffer (one of its output regions, or the dense buffer behind them), or more candidates
+                               than the staging behind L1 holds: the gate between the two stages raises this bit for that as well */
+  MM_REDO_L2_LOCI   = 4,    /* the L2 locus buffer */
+  MM_REDO_L2_SLOTS  = 8,    /* a candidate with more tied loci than the staging slots per candidate */
+  MM_REDO_L2_STREAM = 16,   /* internal error: an L2 stream outgrew the reservation made for it (never expected) */
+  MM_REDO_L2_OPS    = 32,   /* the L2 streams do not fit their buffer as the last sized pass left it */
+  MM_REDO_L2_LIST   = 64,   /* more candidates for the 16-bit-cell re-run or the exact L2 kernel than their launches cover */
+  MM_REDO_L2_CANDS  = 128,  /* more L1 candidates than the candidate-indexed buffers hold (a second line behind the gate: MM_REDO_L1 comes first) */
+  MM_REDO_MAPPINGS  = 256,  /* more candidate mappings than their buffer holds */
+  MM_REDO_NO_STREAM_BUFFER = 512   /* there is no L2 stream buffer yet (the attempt ended before its counters were read).  Not reachable
+                                      today: an attempt needs a sized pass with candidates before it, and that pass allocates the buffer */
+};
+int mm_pass_redo_cause(const mm_ctx* ctx, uint64_t* cause);
 int mm_result_counts(const mm_ctx* ctx, size_t* nL1, size_t* nL2);
 /* any pointer may be NULL.  l1/l2 are sorted by (frag, emission order of the reference) */
 int mm_results_download(mm_ctx* ctx, mm_frag_stats* stats, mm_l1_candidate* l1, mm_l2_locus* l2);

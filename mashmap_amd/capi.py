@@ -13,6 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libmashmap_hip.so")
 
 MM_FLAG_HG_FILTER, MM_FLAG_SKIP_SELF, MM_FLAG_SKIP_PREFIX, MM_FLAG_LOWER_TRIANGULAR, MM_FLAG_NO_SPLIT = 1, 2, 4, 8, 16
+# bits of Context.pass_redo_cause() (include/mashmap_hip.h: MM_REDO_*)
+(MM_REDO_POINTS, MM_REDO_L1, MM_REDO_L2_LOCI, MM_REDO_L2_SLOTS, MM_REDO_L2_STREAM, MM_REDO_L2_OPS, MM_REDO_L2_LIST, MM_REDO_L2_CANDS,
+ MM_REDO_MAPPINGS, MM_REDO_NO_STREAM_BUFFER) = (1 << i for i in range(10))
 KERNELS = ["pack", "sketch", "sketch_hard", "lookup", "sort", "l1", "l2", "refhash", "l2_locate", "winnow", "select"]
 
 
@@ -128,6 +131,7 @@ def load():
         "mm_index_layout_get": (C.c_int, [vp, vp]),
         "mm_pass_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), vp]),
         "mm_pass_totals": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_pass_redo_cause": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "mm_reads_exchange": (C.c_int, [vp, C.c_int]),
         "mm_reads_upload_packed_parts": (C.c_int, [vp, vp, sz, C.c_int32]),
         "mm_reads_prefetch_packed_append": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_int)]),
@@ -158,7 +162,7 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_gathered_counts", "mm_gathered_download", "mm_gathered_device", "mm_index_replicate", "mm_stat_replay_tables", "mm_host_alloc", "mm_host_free", "mm_reads_prefetch",
            "mm_reads_upload_packed", "mm_reads_prefetch_packed", "mm_pack_read", "mm_pack_read_portable", "mm_reads_packed_download",
            "mm_index_layout_get", "mm_pass_stats", "mm_comm_info", "mm_pass_totals", "mm_reads_exchange", "mm_reads_upload_packed_parts",
-           "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve"]
+           "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause"]
 
 
 def stat_sketch_cutoffs(sketchSize, k, hg=True):
@@ -409,6 +413,12 @@ class Context:
         a, b, c_ = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._ck(self.lib.mm_pass_totals(self.h, C.byref(a), C.byref(b), C.byref(c_)), "mm_pass_totals")
         return {"passes": int(a.value), "steady": int(b.value), "redone": int(c_.value)}
+
+    def pass_redo_cause(self):
+        """MM_REDO_* bits: why the last map() had its steady-state attempt redone the sized way; 0 when it had none redone"""
+        v = C.c_uint64()
+        self._ck(self.lib.mm_pass_redo_cause(self.h, C.byref(v)), "mm_pass_redo_cause")
+        return int(v.value)
 
     def reads_exchange(self, slot):
         """swaps the resident batch of reads with the one parked in `slot` (0 .. MM_BATCH_SLOTS - 1); no copy"""

@@ -584,6 +584,11 @@ int mm_pass_totals(const mm_ctx* c, uint64_t* passes, uint64_t* steadyPasses, ui
   return MM_OK;
 }
 
+int mm_pass_redo_cause(const mm_ctx* c, uint64_t* cause) {
+  if (cause) *cause = c->redoCause;
+  return MM_OK;
+}
+
 int mm_pass_stats(const mm_ctx* c, uint64_t* hostSyncs, int* steady, uint64_t* counts) {
   if (!c->mapped) return MM_ERR_STATE;
   if (hostSyncs) *hostSyncs = c->nSyncs;

@@ -142,6 +142,23 @@ enum : int {                  // relative to MM_CW_MAP
   MM_MC_OVERFLOW = 1,         // ... more than dMappings holds
   MM_MC_L2_OPS   = 2          // L2 stream entries reserved (copied here by the L2 launcher)
 };
+// why a steady-state pass is redone, as mm_pass_redo_cause reports it (MM_REDO_*): from the host mirror of the two parts a steady-state
+// pass reads back at its end -- pc: the words under MM_CW_PASS, mc: those under MM_CW_MAP.  Nonzero exactly when pass_finish says MM_PASS_REDO:
+// every MM_L2F_* bit has its MM_REDO_* bit here (a new flag bit needs one too)
+inline uint64_t mm_redo_cause(const unsigned long long* pc, const unsigned long long* mc) {
+  const unsigned long long f = pc[MM_PC_L2_FLAGS];
+  uint64_t cause = 0;
+  if (pc[MM_PC_POINT_OVERFLOW]) cause |= MM_REDO_POINTS;
+  if (pc[MM_PC_L1_OVERFLOW]) cause |= MM_REDO_L1;
+  if (pc[MM_PC_L2_OVERFLOW]) cause |= MM_REDO_L2_LOCI;
+  if (f & MM_L2F_SLOTS) cause |= MM_REDO_L2_SLOTS;
+  if (f & MM_L2F_STREAM) cause |= MM_REDO_L2_STREAM;
+  if (f & MM_L2F_OPS) cause |= MM_REDO_L2_OPS;
+  if (f & MM_L2F_LIST) cause |= MM_REDO_L2_LIST;
+  if (f & MM_L2F_CANDS) cause |= MM_REDO_L2_CANDS;
+  if (mc[MM_MC_OVERFLOW]) cause |= MM_REDO_MAPPINGS;
+  return cause;
+}
 enum : int {                  // 32-bit words relative to MM_CW_SORT_LENS
   MM_SL_BLOCK   = 0,          // list of k_sort_points_block (listB of k_classify_sort)
   MM_SL_GLOBAL  = 1,          // list of k_sort_points_global (listC)
@@ -261,6 +278,7 @@ struct mm_ctx {
   size_t lastOps = 0, lastBig = 0;                      // L2 stream entries reserved / fragments queued for the HBM point path in the last pass
   size_t nSyncs = 0;                                    // host synchronisations inside the last mm_map_fragments (diagnostics: mm_pass_syncs)
   uint64_t nPasses = 0, nSteadyPasses = 0, nRedone = 0; // mm_map_fragments calls of this context: all, those that went through as steady-state passes, steady attempts redone the sized way
+  uint64_t redoCause = 0;                               // MM_REDO_* of the steady attempt the last mm_map_fragments had redone, 0 when it had none (mm_pass_redo_cause)
   bool keepFiltered = false;                            // MM_OPT_KEEP_POINTS = 2: ... and k_filter_points runs on them as it does on a queued fragment's (mm_points_download returns what it leaves)
   bool keepPoints = false;                              // mm_set_option(MM_OPT_KEEP_POINTS): route every fragment through the HBM point list
   size_t reserveFrags = 0;                              // mm_set_option(MM_OPT_RESERVE_FRAGMENTS): fragments of the largest batch the caller will upload; sized passes size for it

@@ -1181,7 +1181,7 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
     MM_HIP(c, c->dL2Ops.ensure((opsFor + opsFor / 16) * 4 + 256));   // a sixteenth of head room for the steady-state passes behind this one
     c->l2Chunks = chunks.size();                                                          // a batch that needs several chunks stays with the sized passes
   }
-  if (steady && c->dL2Ops.bytes == 0) return MM_PASS_REDO;
+  if (steady && c->dL2Ops.bytes == 0) { c->redoCause = MM_REDO_NO_STREAM_BUFFER; return MM_PASS_REDO; }
   // the pre-load states k_l2_locate leaves for the sweeps: a row of s + 2 cells and four integers per candidate of a chunk
   {
     size_t rows = 0;

@@ -1715,7 +1715,7 @@ static int pass_finish(mm_ctx* c, MapPass& p) {
   MM_SYNC(c);
   const unsigned long long* h = c->hPass + MM_CW_PASS; const unsigned long long* hm = c->hPass + MM_CW_MAP;
   c->lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
-  if (mm_pass_incomplete(h) || hm[MM_MC_OVERFLOW]) return MM_PASS_REDO;   // some buffer was too small for this batch: the sized pass grows it
+  if (mm_pass_incomplete(h) || hm[MM_MC_OVERFLOW]) { c->redoCause = mm_redo_cause(h, hm); return MM_PASS_REDO; }   // some buffer was too small for this batch: the sized pass grows it
   c->nL1 = (size_t)h[MM_PC_L1_CAND]; c->nL2 = (size_t)h[MM_PC_L2_LOCI]; c->nMappings = c->haveReplayTables ? (size_t)hm[MM_MC_MAPPINGS] : 0;
   c->lastOps = (size_t)hm[MM_MC_L2_OPS]; c->lastBig = c->prevBig;         // (MM_PC_BIG_LEN holds MM_PC_L2_WIDE_LEN by now: the sized pass's figure stands in)
   return MM_OK;
@@ -1748,7 +1748,7 @@ int mm_launch_map(mm_ctx* c) {
   MM_HIP(c, c->dPtOff.ensure(cF * 16 + 64)); MM_HIP(c, c->dL1Off.ensure(cF * 8 + 64)); MM_HIP(c, c->dPtKept.ensure(cF * 4 + 64));
   MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
   if (!c->hPass) { MM_HIP(c, hipHostMalloc((void**)&c->hPass, MM_COUNTER_BYTES, hipHostMallocDefault)); }
-  c->nL1 = c->nL2 = 0; c->nMappings = 0; c->nSyncs = 0; c->lastSteady = false;
+  c->nL1 = c->nL2 = 0; c->nMappings = 0; c->nSyncs = 0; c->lastSteady = false; c->redoCause = 0;
   if (nF == 0) return MM_OK;
   const bool allSlow = c->keepPoints || (c->P.flags & MM_FLAG_SKIP_PREFIX) || c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH;
   // (a batch with a tenth more fragments than the one the buffers were sized for would only fail and be redone: it is sized right away)

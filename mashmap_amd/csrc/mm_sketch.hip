@@ -935,6 +935,8 @@ int mm_launch_sketch(mm_ctx* c) {
     MM_HIP(c, c->dSkHash.ensure(nF * s * 8 + 64)); MM_HIP(c, c->dSkPos.ensure(nF * s * 8 + 64));
     MM_HIP(c, c->dSkStrand.ensure(nF * s + 64)); MM_HIP(c, c->dSkCount.ensure(nF * 4 + 64));
     MM_HIP(c, c->dHardList.ensure(nF * 4 + 64)); MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
+    // no hard list here, and its length is read all the same (mm_pass_stats): the words every other sketch launch resets
+    MM_HIP(c, hipMemsetAsync(c->dCounters.as<unsigned long long>() + MM_CW_SKETCH, 0, (size_t)(MM_CW_SKETCH_END - MM_CW_SKETCH) * 8, c->stream));
     return mm_launch_sketch_global(c);
   }
   MM_HIP(c, c->dSkHash.ensure(cF * s * 8 + 64));

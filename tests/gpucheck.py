@@ -48,6 +48,53 @@ def prefix_groups(names, delim):
     return pre, grp
 
 
+LDS_MAX_SKETCH = 8190                  # mm_internal.h: MM_LDS_MAX_SKETCH
+STEADY_LOG = []                        # one dict per run_and_compare call of this process: what the rule said and what the second pass was
+
+
+def must_be_steady(flags, s, L, reads, n_l1):
+    """The rule for the second map() of a batch on the context that has just sized itself for it: a steady-state pass, unless the batch
+    takes the literal kernels (-Y reference groups; --noSplit with a read longer than segLength, which is what makes a fragment longer
+    than a segment; a sketch no LDS table holds) or the sized pass found no L1 candidate (there is then nothing behind L1 to have sized).
+    From the inputs alone; returns (steady, reason it is not).  (Narrower on purpose than "the flags have NOSPLIT": a --noSplit batch
+    whose reads all fit a segment has no long fragment -- mm_ctx::windowed stays false -- and must take the steady leg like any other.)"""
+    if flags & U.FLAG_SKIP_PREFIX: return False, "skip_prefix"
+    if (flags & U.FLAG_NOSPLIT) and any(len(a) > L for _, a in reads): return False, "nosplit"
+    if s > LDS_MAX_SKETCH: return False, "sketch"
+    if n_l1 == 0: return False, "no_candidates"
+    return True, None
+
+
+def pass_bytes(ctx):
+    """everything a pass leaves, as bytes: stats, L1, L2, candidate mappings, post-removal query sketches"""
+    return tuple(x.tobytes() for x in ctx.results()) + (ctx.mappings().tobytes(), ctx.query_sketches().tobytes())
+
+
+def steady_leg(ctx, first, rule):
+    """maps the resident batch once more, on the context whose previous map() was the sized pass `first` = pass_bytes(ctx) came from, and
+    holds the second pass against the first: a steady-state pass (one host wait, nothing redone) wherever the rule asks for one, no
+    steady attempt at all where it does not; the same bytes and the same counts either way."""
+    import os
+    want, why = rule
+    assert ctx.pass_stats()[1] is False and ctx.pass_redo_cause() == 0, "the first pass of a context is a sized pass"
+    counts0, tot0 = ctx.pass_counts(), ctx.pass_totals()
+    ctx.map()
+    st, cause, tot1 = ctx.pass_stats(), ctx.pass_redo_cause(), ctx.pass_totals()
+    STEADY_LOG.append(dict(test=os.environ.get("PYTEST_CURRENT_TEST", ""), want=want, why=why, stats=st, cause=cause))
+    assert tot1["redone"] == tot0["redone"] and cause == 0, \
+        "the second pass over the batch the buffers were sized for was redone: cause %#x (MM_REDO_*), %r" % (cause, st)
+    if want:
+        assert st == (1, True), "not a steady-state pass with one wait: %r" % (st,)
+    else:
+        assert not st[1], "a steady-state pass where the rule (%s) has none" % why
+    assert tot1["passes"] == tot0["passes"] + 1 and tot1["steady"] == tot0["steady"] + (1 if want else 0)
+    for a, b, what in zip(pass_bytes(ctx), first, ("stats", "l1", "l2", "mappings", "query sketches")):
+        assert a == b, "the second (%s) pass disagrees with the sized pass on %s" % ("steady-state" if want else "sized", what)
+    counts1 = ctx.pass_counts()
+    for key in ("l1", "l2", "stream_entries", "hard"):       # ("queued" repeats the sized pass's figure in a steady-state pass)
+        assert counts1[key] == counts0[key], (key, counts0, counts1)
+
+
 def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=U.FLAG_HG, delim="\0", kmerPct=0.001,
                     seqCounterBase=0, check_points=True, verbose=True, mutate_index=None, device_index=False):
     """contigs: [(name, uint8 array)], reads: [(name, uint8 array)].  Returns (nFragments, nMappedLoci).
@@ -80,19 +127,22 @@ def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=
     ctx.set_tables(oracle.min_hits_table(s, k, pi), oracle.cutoffs(h))
     ctx.set_replay_tables(*capi.stat_replay_tables(s, k, pi, 0.0, not (flags & U.FLAG_DROP_LOW_ID)))
     nF = ctx.reads_upload([a for _, a in reads], readGroup, selfId, seqCounterBase)
-    # first the default path (interval points stay in LDS/registers: fused lookup + sort + L1), then again with the point lists
-    # kept in HBM (sort + literal sweep kernels); both must reproduce the reference, and agree with each other
+    # first the default path (interval points stay in LDS/registers: fused lookup + sort + L1) -- twice: the sized pass, and the
+    # steady-state pass behind it --, then again with the point lists kept in HBM (sort + literal sweep kernels); all must reproduce
+    # the reference, and agree with each other
     ctx.map()
-    fast = ctx.results()
+    fast = pass_bytes(ctx)
+    steady_leg(ctx, fast, must_be_steady(flags, s, L, reads, ctx.result_counts()[0]))
     ctx.keep_points(True)
     ctx.map()
     stats, l1, l2 = ctx.results()
-    for a, b, what in zip(fast, (stats, l1, l2), ("stats", "l1", "l2")):
-        assert len(a) == len(b) and a.tobytes() == b.tobytes(), "fused and HBM point paths disagree on " + what
     qsk = ctx.query_sketches()
     frs = ctx.fragments()
     # candidate mappings (k_l2_select: doL2Mapping's best-first walk on the device), fragment-major
     recs = ctx.mappings()
+    # (what is compared with the oracle below is therefore what the sized and the steady-state pass of the default path produced as well)
+    for a, b, what in zip(fast, (stats, l1, l2, recs, qsk), ("stats", "l1", "l2", "mappings", "query sketches")):
+        assert a == b.tobytes(), "fused and HBM point paths disagree on " + what
     recs_by_f, f_at = {}, 0
     for m in recs:
         key = (int(m["querySeqId"]) - seqCounterBase, int(m["fragStart"]))

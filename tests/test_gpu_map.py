@@ -506,8 +506,10 @@ def test_resident_batches_take_turns_and_an_l1_overflow_in_a_steady_pass_is_redo
     """mm_reads_exchange: three uploaded batches stay in HBM and take turns (what bench.py's timed loop does) -- every pass returns the
     bytes a fresh context gives for that batch, the passes behind the first one are steady-state passes as long as the incoming batch
     fits the buffers, and mm_pass_totals counts the one that does not.  The batch that does not is built to overflow the L1 STAGE of a
-    steady pass (a read set out of a 30-copy repeat: several times the candidates per fragment the buffers were sized for): the L2 stage
-    must not run on what the overflowed L1 stage left (k_l1_gate; the advisor's round-4 finding), the pass is redone and exact."""
+    steady pass (a read set out of a 30-copy repeat: several times the candidates, and ~2 000 interval points, per fragment): the L2 stage
+    must not run on what the overflowed L1 stage left (k_l1_gate; the advisor's round-4 finding), the pass is redone and exact.
+    What gives way is the interval-point buffer (mm_pass_redo_cause: MM_REDO_POINTS alone) -- the fragments that get no room there never
+    reach the kernels that would overflow the candidate buffer; tests/test_gpu_steady.py has a pair whose cause is the L1 candidates."""
     from mashmap_amd import capi
     unit = U.random_dna(821, 20000)
     rep = np.concatenate([U.mutate(unit, 910 + i, 0.01) for i in range(30)])
@@ -546,6 +548,7 @@ def test_resident_batches_take_turns_and_an_l1_overflow_in_a_steady_pass_is_redo
     ctx.reads_exchange(1); ctx.map()                                             # resident C: L1 candidates overflow the steady pass
     assert got() == wantC and not ctx.pass_stats()[1]
     t = ctx.pass_totals(); assert t == {"passes": 4, "steady": 2, "redone": 1}, t
+    assert ctx.pass_redo_cause() == capi.MM_REDO_POINTS, hex(ctx.pass_redo_cause())   # the interval points and nothing else: what k_l1_gate let through to L2 was nothing
     ctx.map(); assert got() == wantC and ctx.pass_stats() == (1, True)           # sized for C now
     ctx.reads_exchange(0); ctx.map(); assert got() == wantA and ctx.pass_stats() == (1, True)           # slot 0 held A (B sits in slot 1 since C came out of it)
     ctx.reads_exchange(2); assert ctx.num_fragments() == 0                       # an empty slot: nothing resident
@@ -568,8 +571,11 @@ def test_pass_counts_report_the_hard_list(oracle):
     assert ctx.pass_counts()["hard"] == 0
     ctx.reads_upload(reads + [sat, sat]); ctx.map()
     assert ctx.pass_counts()["hard"] == 4                                        # two fragments per satellite read
+    got = lambda: tuple(x.tobytes() for x in ctx.results()) + (ctx.mappings().tobytes(), ctx.query_sketches().tobytes())
+    sized = got()
     ctx.map()
     assert ctx.pass_stats()[1] and ctx.pass_counts()["hard"] == 4                # the count comes back with a steady-state pass's counters too
+    assert got() == sized and ctx.pass_redo_cause() == 0                         # ... and the hard list's fragments with the same results
     ctx.close()
 
 
