@@ -36,7 +36,10 @@ enum {
 enum {
   MM_FLAG_HG_FILTER = 1,        /* stage1_topANI_filter   (parseCmdArgs.hpp:397) */
   MM_FLAG_SKIP_SELF = 2,        /* skip_self              (parseCmdArgs.hpp:341) */
-  MM_FLAG_SKIP_PREFIX = 4,      /* skip_prefix            (parseCmdArgs.hpp:349) */
+  MM_FLAG_SKIP_PREFIX = 4,      /* skip_prefix            (parseCmdArgs.hpp:349): L1 runs once per run of interval points whose contigs share a
+                                   reference group (computeMap.hpp:1146-1165).  Every fragment's points go through HBM (gather, sort), every
+                                   pass is a sized pass, and the L1 stage is the literal one-thread-per-fragment kernel for every queued
+                                   fragment (mm_pass_l1_literal: literal == queued). */
   MM_FLAG_LOWER_TRIANGULAR = 8, /* lower_triangular       (parseCmdArgs.hpp:334) */
   MM_FLAG_NO_SPLIT = 16         /* !split                 (parseCmdArgs.hpp:427): a read longer than segLength is then ONE fragment with
                                    windowLen = len - segLength != 0 (computeMap.hpp:933, :1309); a batch that holds such a read goes through
@@ -300,6 +303,13 @@ enum {
                                       today: an attempt needs a sized pass with candidates before it, and that pass allocates the buffer */
 };
 int mm_pass_redo_cause(const mm_ctx* ctx, uint64_t* cause);
+/* Which L1 kernel took the fragments of the HBM point path, as of the context's last SIZED pass (a steady-state pass leaves both figures
+ * as they were): *queued = fragments queued for that path, *literal = those of them the literal one-thread-per-fragment kernel
+ * (k_l1_sweep) swept -- every one of them (a batch with a read longer than segLength excepted: 0, k_l1_window takes those) under MM_L1_LITERAL
+ * or MM_FLAG_SKIP_PREFIX, otherwise what the wave-per-fragment kernel (k_l1_stream) leaves: a position group across two contigs or
+ * minimumHits <= 0.  Read back with the words the sized pass reads behind the L1 sweeps anyway: no host wait
+ * more.  Either pointer may be NULL.  Purely additive: MM_ABI_VERSION stays 2. */
+int mm_pass_l1_literal(const mm_ctx* ctx, uint64_t* queued, uint64_t* literal);
 int mm_result_counts(const mm_ctx* ctx, size_t* nL1, size_t* nL2);
 /* any pointer may be NULL.  l1/l2 are sorted by (frag, emission order of the reference) */
 int mm_results_download(mm_ctx* ctx, mm_frag_stats* stats, mm_l1_candidate* l1, mm_l2_locus* l2);

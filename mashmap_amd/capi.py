@@ -132,6 +132,7 @@ def load():
         "mm_pass_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int), vp]),
         "mm_pass_totals": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_redo_cause": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "mm_pass_l1_literal": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_reads_exchange": (C.c_int, [vp, C.c_int]),
         "mm_reads_upload_packed_parts": (C.c_int, [vp, vp, sz, C.c_int32]),
         "mm_reads_prefetch_packed_append": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_int)]),
@@ -162,7 +163,8 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_gathered_counts", "mm_gathered_download", "mm_gathered_device", "mm_index_replicate", "mm_stat_replay_tables", "mm_host_alloc", "mm_host_free", "mm_reads_prefetch",
            "mm_reads_upload_packed", "mm_reads_prefetch_packed", "mm_pack_read", "mm_pack_read_portable", "mm_reads_packed_download",
            "mm_index_layout_get", "mm_pass_stats", "mm_comm_info", "mm_pass_totals", "mm_reads_exchange", "mm_reads_upload_packed_parts",
-           "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause"]
+           "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
+           "mm_pass_l1_literal"]
 
 
 def stat_sketch_cutoffs(sketchSize, k, hg=True):
@@ -419,6 +421,12 @@ class Context:
         v = C.c_uint64()
         self._ck(self.lib.mm_pass_redo_cause(self.h, C.byref(v)), "mm_pass_redo_cause")
         return int(v.value)
+
+    def pass_l1_literal(self):
+        """(queued, literal) of the last sized pass: fragments queued for the HBM point path, and those of them the literal k_l1_sweep took"""
+        q, l = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.mm_pass_l1_literal(self.h, C.byref(q), C.byref(l)), "mm_pass_l1_literal")
+        return int(q.value), int(l.value)
 
     def reads_exchange(self, slot):
         """swaps the resident batch of reads with the one parked in `slot` (0 .. MM_BATCH_SLOTS - 1); no copy"""

@@ -589,6 +589,12 @@ int mm_pass_redo_cause(const mm_ctx* c, uint64_t* cause) {
   return MM_OK;
 }
 
+int mm_pass_l1_literal(const mm_ctx* c, uint64_t* queued, uint64_t* literal) {
+  if (queued) *queued = c->prevBig;
+  if (literal) *literal = c->prevLit;
+  return MM_OK;
+}
+
 int mm_pass_stats(const mm_ctx* c, uint64_t* hostSyncs, int* steady, uint64_t* counts) {
   if (!c->mapped) return MM_ERR_STATE;
   if (hostSyncs) *hostSyncs = c->nSyncs;

@@ -162,7 +162,8 @@ inline uint64_t mm_redo_cause(const unsigned long long* pc, const unsigned long 
 enum : int {                  // 32-bit words relative to MM_CW_SORT_LENS
   MM_SL_BLOCK   = 0,          // list of k_sort_points_block (listB of k_classify_sort)
   MM_SL_GLOBAL  = 1,          // list of k_sort_points_global (listC)
-  MM_SL_LITERAL = 2,          // the fragments k_l1_stream leaves for k_l1_sweep (a word of its own: the two above still feed the sorters in flight)
+  MM_SL_LITERAL = 2,          // the fragments k_l1_stream leaves for k_l1_sweep (a word of its own: the two above still feed the sorters
+                              // in flight); a sized pass reads it back behind the L1 sweeps, with the L1 cursor (mm_pass_l1_literal)
   MM_SL_END     = 4
 };
 enum : int {                  // index build diagnostics, relative to MM_CW_INDEX_BUILD / MM_CW_INDEX_FLATTEN
@@ -276,6 +277,7 @@ struct mm_ctx {
   size_t lastHard = 0;                                  // fragments the fast sketch kernel handed to the hard list in the last pass
   size_t prevMid = 0, lastMid = 0; bool midKnown = false;   // fragments k_lookup_mid took in the last sized pass (its grid in the steady-state passes behind it)
   size_t lastOps = 0, lastBig = 0;                      // L2 stream entries reserved / fragments queued for the HBM point path in the last pass
+  size_t prevLit = 0;                                   // of prevBig, the fragments the literal k_l1_sweep took in the last sized pass (mm_pass_l1_literal)
   size_t nSyncs = 0;                                    // host synchronisations inside the last mm_map_fragments (diagnostics: mm_pass_syncs)
   uint64_t nPasses = 0, nSteadyPasses = 0, nRedone = 0; // mm_map_fragments calls of this context: all, those that went through as steady-state passes, steady attempts redone the sized way
   uint64_t redoCause = 0;                               // MM_REDO_* of the steady attempt the last mm_map_fragments had redone, 0 when it had none (mm_pass_redo_cause)

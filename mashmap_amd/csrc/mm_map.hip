@@ -1475,6 +1475,7 @@ struct MapPass {
   // what a sized pass has read back (a steady-state pass never reads them: all zero)
   unsigned long long hc[MM_PC_READ] = {0}, hMid = 0, hcur[MM_L1_REGIONS * MM_L1_CURSOR_STRIDE] = {0};
   int nBig = 0;                            // sized pass: fragments queued for the HBM point path
+  unsigned long long nLit = 0;             // sized pass: of those, the fragments the literal k_l1_sweep took
   unsigned gWave = 0, gThread = 0;         // grids over those: a wave / a thread per fragment
 };
 
@@ -1642,6 +1643,9 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
   const int nBig = p.nBig, s = p.s;
   unsigned long long* const cnt = p.cnt;
   const unsigned long long fusedL1 = p.hc[MM_PC_L1_CAND];
+  // a wave per fragment streams the sorted points; what it cannot take (a position group across two contigs, minimumHits 0) and
+  // every fragment under -Y reference groups goes to the literal one-thread-per-fragment kernel
+  const bool stream = !p.fl.skipPrefix && !c->env.l1Literal && !p.windowed;
   for (int attempt = 0; attempt < 8; attempt++) {
     if (!p.steady) {
       MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L1_CAND, &fusedL1, 8, hipMemcpyHostToDevice, c->stream));
@@ -1649,9 +1653,6 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
     }
     {
       KernelTimer t(c, MM_K_L1);
-      // a wave per fragment streams the sorted points; what it cannot take (a position group across two contigs, minimumHits 0) and
-      // every fragment under -Y reference groups goes to the literal one-thread-per-fragment kernel
-      const bool stream = !p.fl.skipPrefix && !c->env.l1Literal && !p.windowed;
       const int32_t* sweepList = c->dBigList.as<int32_t>(); const unsigned int* sweepCount = nullptr;
       if (p.windowed) {
         const int nFreq = s > 256 ? s : 256;                                     // seeds are numbered by their index in the raw sketch
@@ -1681,7 +1682,12 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
     }
     if (p.steady) return MM_OK;
     MM_HIP(c, hipMemcpyAsync(p.hc + MM_PC_L1_CAND, cnt + MM_PC_L1_CAND, 16, hipMemcpyDeviceToHost, c->stream));   // the cursor and its overflow flag
+    // ... and, with them, the length of the list k_l1_stream left for k_l1_sweep (the 64-bit word that holds MM_SL_LITERAL)
+    constexpr int litWord = MM_CW_SORT_LENS + MM_SL_LITERAL / 2;
+    MM_HIP(c, hipMemcpyAsync(c->hPass + litWord, c->dCounters.as<unsigned long long>() + litWord, 8, hipMemcpyDeviceToHost, c->stream));
     MM_SYNC(c);
+    // (set again by every attempt of this loop: the last one, whose candidates stand, is the one that counts)
+    p.nLit = p.windowed ? 0ull : stream ? (unsigned long long)((const unsigned int*)(c->hPass + MM_CW_SORT_LENS))[MM_SL_LITERAL] : (unsigned long long)nBig;
     if (!p.hc[MM_PC_L1_OVERFLOW]) return MM_OK;
     // grow, keeping the fused candidates already in the buffer
     const size_t newCap = (size_t)p.hc[MM_PC_L1_CAND] + (size_t)p.hc[MM_PC_L1_CAND] / 8 + 1024;
@@ -1733,7 +1739,7 @@ static int map_pass(mm_ctx* c, const bool steady) {
   if (rc != MM_OK) return rc;
   if (!steady) {
     c->nL1 = (size_t)p.hc[MM_PC_L1_CAND];
-    c->prevBig = c->lastBig = (size_t)p.nBig;
+    c->prevBig = c->lastBig = (size_t)p.nBig; c->prevLit = (size_t)p.nLit;
     c->prevMid = c->lastMid = (size_t)p.hMid; c->midKnown = p.useMid;
     if (c->nL1 == 0) { c->nL2 = 0; return MM_OK; }
   }
