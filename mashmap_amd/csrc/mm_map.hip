@@ -12,13 +12,14 @@
 //     k_gather_points, k_filter_points                    the interval points into dPts; those that cannot reach minimumHits dropped
 //     k_sort_points_wave / _block / _global, k_classify_sort   sorters by list length (registers, LDS, HBM) and the split between them
 //     k_l1_stream           L1 by a wave that streams the sorted points
-//     k_l1_sweep            L1 by the literal one-thread-per-fragment sweep (what k_l1_stream leaves, or everything)
-//     k_l1_window           L1 of fragments longer than segLength (windowLen != 0)
+//     k_l1_sweep            L1 by the literal one-thread-per-fragment sweep of mm_l1_core.h (what k_l1_stream leaves, or everything)
+//     k_l1_window           the same sweep for fragments longer than segLength (windowLen != 0)
 //   map_pass / mm_launch_map   one pass over the resident sketches, stage by stage; sized or steady-state
 //   mm_results_download, mm_query_sketch_download, mm_points_download
 //   (L2 lives in mm_l2.hip, the selection in mm_select.hip; the pass's device counters are described in mm_internal.h: MM_CW_*)
 #include "mm_internal.h"
 #include "mm_device.h"
+#include "mm_l1_core.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -1056,93 +1057,6 @@ __global__ void k_classify_sort(int nList, const unsigned long long* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_l1_sweep: one thread per queued fragment over its sorted points (windowLen == 0, i.e. split mode).
-// Literal two-pointer restatement of computeMap.hpp:948-1115 on packed keys:
-//   key>>1 == (seqId<<32 | pos)  so  "trail <= lead in (seqId,pos)"  is one 64-bit compare.
-// Emits the joined candidates of each reference group (skip_prefix) in the reference's order.
-// ---------------------------------------------------------------------------------------------
-struct L1Emit {
-  mm_l1_candidate* out; int frag; int count; bool write;
-  bool have; mm_l1_candidate pend;
-  __device__ __forceinline__ void run(int seqId, int start, int end, int isize, int clusterLen, bool& firstOfGroup) {
-    // join with the previous candidate of the same computeL1CandidateRegions call when close (computeMap.hpp:1102-1115)
-    if (have && !firstOfGroup && seqId == pend.seqId && !(start > pend.rangeEndPos + clusterLen)) {
-      pend.rangeEndPos = end; pend.intersectionSize = isize > pend.intersectionSize ? isize : pend.intersectionSize;
-    } else {
-      flush();
-      pend.frag = frag; pend.seqId = seqId; pend.rangeStartPos = start; pend.rangeEndPos = end; pend.intersectionSize = isize; have = true;
-    }
-    firstOfGroup = false;
-  }
-  mm_l1_candidate b0, b1;                             // the first two candidates of a counting pass: most fragments need no second pass
-  __device__ __forceinline__ void flush() {
-    if (have) {
-      if (write) out[count] = pend;
-      else if (count == 0) b0 = pend;
-      else if (count == 1) b1 = pend;
-      count++; have = false;
-    }
-  }
-};
-
-__device__ void l1_sweep_fragment(const uint64_t* __restrict__ p, int nPts, int sketchSizeQ, int minHits0, const int32_t* __restrict__ cutoffs,
-                                  int nCutoffs, int sParam, int segLength, MapFlags fl, const int32_t* __restrict__ refGroup, L1Emit& em) {
-  int b = 0;
-  while (b < nPts) {
-    int e = nPts;
-    if (fl.skipPrefix) {
-      const int g = refGroup[(int)(p[b] >> 33)];
-      e = b; while (e < nPts && refGroup[(int)(p[e] >> 33)] == g) e++;
-    }
-    int minHits = minHits0;
-    bool go = true;
-    if (fl.hg) {                                                 // pass 1: best overlap (computeMap.hpp:948-999)
-      int overlap = 0, best = 0, trail = b, lead = b;
-      while (lead < e) {
-        const uint64_t lk = p[lead] >> 1;
-        while (trail < e && (p[trail] >> 1) <= lk) { if (!(p[trail] & 1ull)) overlap--; trail++; }
-        const uint32_t cur = (uint32_t)lk;
-        while (lead < e && (uint32_t)(p[lead] >> 1) == cur) { if (p[lead] & 1ull) overlap++; lead++; }
-        best = overlap > best ? overlap : best;
-      }
-      if (best < minHits) go = false;
-      else {
-        const double div = (double)sParam / 1000.0 > 1.0 ? (double)sParam / 1000.0 : 1.0;
-        int ci = (int)((double)(best < sketchSizeQ ? best : sketchSizeQ) / div);
-        if (ci >= nCutoffs) ci = nCutoffs - 1;
-        const int cut = cutoffs[ci];
-        minHits = cut > minHits ? cut : minHits;
-      }
-    }
-    if (go) {                                                    // pass 2: runs (computeMap.hpp:1009-1098)
-      bool firstOfGroup = true, inRun = false;
-      int rSeq = 0, rStart = 0, rEnd = 0, rSize = 0;
-      int overlap = 0, trail = b, lead = b;
-      int prevSeq = 0, prevPos = 0;
-      int curSeq = (int)(p[b] >> 33), curPos = (int)(uint32_t)(p[b] >> 1);
-      while (lead < e) {
-        const int prevOverlap = overlap;
-        const uint64_t lk = p[lead] >> 1;
-        while (trail < e && (p[trail] >> 1) <= lk) { if (!(p[trail] & 1ull)) overlap--; trail++; }
-        if ((int)(uint32_t)lk != curPos) { prevSeq = curSeq; prevPos = curPos; curSeq = (int)(lk >> 32); curPos = (int)(uint32_t)lk; }
-        while (lead < e && (int)(uint32_t)(p[lead] >> 1) == curPos) { if (p[lead] & 1ull) overlap++; lead++; }
-        if (prevOverlap >= minHits) {
-          if (inRun && rSeq != prevSeq) { em.run(rSeq, rStart, rEnd, rSize, segLength, firstOfGroup); inRun = false; }
-          if (!inRun) { rStart = prevPos; rEnd = prevPos; rSeq = prevSeq; rSize = prevOverlap; inRun = true; }
-          else { rSize = prevOverlap > rSize ? prevOverlap : rSize; rEnd = prevPos; }
-        } else {
-          if (inRun) em.run(rSeq, rStart, rEnd, rSize, segLength, firstOfGroup);
-          inRun = false;
-        }
-      }
-      if (inRun) em.run(rSeq, rStart, rEnd, rSize, segLength, firstOfGroup);
-    }
-    em.flush();
-    b = e;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // k_l1_stream: the L1 stage of a queued fragment by one WAVE, streaming its sorted points from HBM 64 at a time (coalesced) -- any
 // number of points.  Same formulation as mm_l1_fused: the overlap count after a position group is the running sum of +1 (OPEN) / -1
 // (CLOSE) up to its last point; pass 1 finds the best count (computeMap.hpp:948-999), pass 2 folds the groups whose count reaches
@@ -1311,6 +1225,19 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
   for (int li = blockIdx.x * 4 + wave; li < nList; li += gridDim.x * 4) { one(list[li]); __threadfence_block(); }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_l1_sweep: one thread per queued fragment over its sorted points (windowLen == 0, i.e. split mode): the literal two-pointer
+// restatement of computeMap.hpp:916-1116 in mm_l1_core.h, which the CPU suite checks against the oracle.
+// ---------------------------------------------------------------------------------------------
+struct L1Claim {                                      // nOut slots of the pass's L1 buffer: the cursor, and its overflow flag when they do not fit
+  unsigned long long* counters; unsigned long long l1Cap;
+  __device__ __forceinline__ bool operator()(int nOut, long long& base) const {
+    base = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)nOut);
+    if ((unsigned long long)base + nOut <= l1Cap) return true;
+    atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED);
+    return false;
+  }
+};
 __global__ void __launch_bounds__(256)
 k_l1_sweep(int nList, const int32_t* __restrict__ list, const int64_t* __restrict__ ptOff, const uint64_t* __restrict__ pts,
            mm_frag_stats* __restrict__ stats,
@@ -1323,101 +1250,23 @@ k_l1_sweep(int nList, const int32_t* __restrict__ list, const int64_t* __restric
   if (nListDev) nList = (int)*nListDev;
   if (nDev64) nList = (int)*nDev64;
   for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < nList; li += gridDim.x * blockDim.x) {
-  const int f = list[li];
-  const int nPts = ptKept[f], S = stats[f].sketchSize;
-  int nOut = 0; long long base = 0;
-  if (nPts > 0 && S > 0) {
-    const uint64_t* p = pts + ptOff[2 * f];
-    const int minHits0 = minHitsTab[S];
-    L1Emit em; em.out = nullptr; em.frag = f; em.count = 0; em.write = false; em.have = false;
-    l1_sweep_fragment(p, nPts, S, minHits0, cutoffs, nCutoffs, sParam, segLength, fl, refGroup, em);
-    nOut = em.count;
-    if (nOut > 0) {
-      base = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)nOut);
-      if ((unsigned long long)base + nOut > l1Cap) { atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
-      else if (nOut <= 2) { l1[base] = em.b0; if (nOut == 2) l1[base + 1] = em.b1; }
-      else {
-        L1Emit ew; ew.out = l1 + base; ew.frag = f; ew.count = 0; ew.write = true; ew.have = false;
-        l1_sweep_fragment(p, nPts, S, minHits0, cutoffs, nCutoffs, sParam, segLength, fl, refGroup, ew);
-      }
+    const int f = list[li];
+    const int nPts = ptKept[f], S = stats[f].sketchSize;
+    L1Stored r{0, 0};
+    if (nPts > 0 && S > 0) {
+      const L1Frag q{pts + ptOff[2 * f], nPts, nullptr, 0, nullptr, 0, S, minHitsTab[S], cutoffs, nCutoffs, sParam, segLength, fl.hg, fl.skipPrefix, refGroup};
+      r = mm_l1_literal_store<false>(q, f, l1, L1Claim{counters, l1Cap});
     }
-  }
-  stats[f].nL1 = nOut;
-  l1Off[f] = base;
+    stats[f].nL1 = r.nOut;
+    l1Off[f] = r.base;
   }
 }
 
-
 // ---------------------------------------------------------------------------------------------
-// k_l1_window: computeL1CandidateRegions for fragments LONGER than segLength (--noSplit: Q.len > segLength, windowLen =
-// Q.len - segLength != 0, computeMap.hpp:933), literally: one thread per fragment over its sorted points, the trailing pointer windowLen
-// behind the leading one, and a count of open windows per seed (hash_to_freq, :948) -- a seed adds to the overlap only while its count
-// goes 0 -> 1 and leaves it only when it returns to 0.  `ids` numbers the seeds of a fragment (mm_gather_points); `freq` is this
-// thread's slice of a zero-initialised scratch array.  Handles windowLen == 0 as well (a batch may mix short and long reads).
+// k_l1_window: the same for fragments LONGER than segLength (--noSplit: Q.len > segLength, windowLen = Q.len - segLength != 0,
+// computeMap.hpp:933): the WINDOWED form of mm_l1_literal_fragment.  `ptIds` numbers the seeds of a fragment (mm_gather_points);
+// `freqAll` gives every thread nFreq counters.  Handles windowLen == 0 as well (a batch may mix short and long reads).
 // ---------------------------------------------------------------------------------------------
-__device__ void l1_window_fragment(const uint64_t* __restrict__ p, const uint16_t* __restrict__ ids, int nPts, int W, int32_t* __restrict__ freq, int nFreq,
-                                   int sketchSizeQ, int minHits0, const int32_t* __restrict__ cutoffs, int nCutoffs, int sParam, int segLength, MapFlags fl,
-                                   const int32_t* __restrict__ refGroup, L1Emit& em) {
-  auto seqOf = [&](int i) { return (int)(p[i] >> 33); };
-  auto posOf = [&](int i) { return (int)(uint32_t)(p[i] >> 1); };
-  auto behind = [&](int t, int l) { const int st = seqOf(t), sl = seqOf(l); return (st == sl && posOf(t) <= posOf(l) - W) || st < sl; };   // :952-954
-  auto closeAt = [&](int t, int& overlap) { if (!(p[t] & 1ull)) { const int id = ids[t]; if (W != 0) freq[id]--; if (W == 0 || freq[id] == 0) overlap--; } };
-  auto openAt = [&](int l, int& overlap) { if (p[l] & 1ull) { const int id = ids[l]; if (W == 0 || freq[id] == 0) overlap++; if (W != 0) freq[id]++; } };
-  int b = 0;
-  while (b < nPts) {
-    int e = nPts;
-    if (fl.skipPrefix) {
-      const int g = refGroup[seqOf(b)];
-      e = b; while (e < nPts && refGroup[seqOf(e)] == g) e++;
-    }
-    int minHits = minHits0;
-    bool go = true;
-    if (fl.hg) {                                                 // pass 1: best overlap (:948-999)
-      for (int i = 0; i < nFreq; i++) freq[i] = 0;
-      int overlap = 0, best = 0, trail = b, lead = b;
-      while (lead < e) {
-        while (trail < e && behind(trail, lead)) { closeAt(trail, overlap); trail++; }
-        const int cur = posOf(lead);
-        while (lead < e && posOf(lead) == cur) { openAt(lead, overlap); lead++; }
-        best = overlap > best ? overlap : best;
-      }
-      if (best < minHits) go = false;
-      else {
-        const double div = (double)sParam / 1000.0 > 1.0 ? (double)sParam / 1000.0 : 1.0;
-        int ci = (int)((double)(best < sketchSizeQ ? best : sketchSizeQ) / div);
-        if (ci >= nCutoffs) ci = nCutoffs - 1;
-        const int cut = cutoffs[ci];
-        minHits = cut > minHits ? cut : minHits;
-      }
-    }
-    if (go) {                                                    // pass 2 (:1001-1098); hash_to_freq.clear() first (:1001-1003)
-      for (int i = 0; i < nFreq; i++) freq[i] = 0;
-      bool firstOfGroup = true, inRun = false;
-      int rSeq = 0, rStart = 0, rEnd = 0, rSize = 0;
-      int overlap = 0, trail = b, lead = b;
-      int prevSeq = 0, prevPos = 0;
-      int curSeq = seqOf(b), curPos = posOf(b);
-      while (lead < e) {
-        const int prevOverlap = overlap;
-        while (trail < e && behind(trail, lead)) { closeAt(trail, overlap); trail++; }
-        if (posOf(lead) != curPos) { prevSeq = curSeq; prevPos = curPos; curSeq = seqOf(lead); curPos = posOf(lead); }
-        while (lead < e && posOf(lead) == curPos) { openAt(lead, overlap); lead++; }
-        if (prevOverlap >= minHits) {
-          if (inRun && rSeq != prevSeq) { em.run(rSeq, rStart, rEnd, rSize, segLength, firstOfGroup); inRun = false; }
-          if (!inRun) { rStart = prevPos - W; rEnd = prevPos - W; rSeq = prevSeq; rSize = prevOverlap; inRun = true; }
-          else { rSize = prevOverlap > rSize ? prevOverlap : rSize; rEnd = prevPos - W; }
-        } else {
-          if (inRun) em.run(rSeq, rStart, rEnd, rSize, segLength, firstOfGroup);
-          inRun = false;
-        }
-      }
-      if (inRun) em.run(rSeq, rStart, rEnd, rSize, segLength, firstOfGroup);
-    }
-    em.flush();
-    b = e;
-  }
-}
-
 __global__ void __launch_bounds__(64)
 k_l1_window(int nList, const int32_t* __restrict__ list, const DFrag* __restrict__ frags, const int64_t* __restrict__ ptOff, const uint64_t* __restrict__ pts,
             const uint16_t* __restrict__ ptIds, mm_frag_stats* __restrict__ stats, const int32_t* __restrict__ minHitsTab, const int32_t* __restrict__ cutoffs,
@@ -1427,28 +1276,15 @@ k_l1_window(int nList, const int32_t* __restrict__ list, const DFrag* __restrict
   if (li >= nList) return;
   const int f = list[li];
   const int nPts = stats[f].nPoints, S = stats[f].sketchSize;
-  int nOut = 0; long long base = 0;
+  L1Stored r{0, 0};
   if (nPts > 0 && S > 0) {
-    const uint64_t* p = pts + ptOff[2 * f];
-    const uint16_t* ids = ptIds + ptOff[2 * f];
     int W = frags[f].len - segLength; if (W < 0) W = 0;
-    int32_t* freq = freqAll + (size_t)li * nFreq;
-    const int minHits0 = minHitsTab[S];
-    L1Emit em; em.out = nullptr; em.frag = f; em.count = 0; em.write = false; em.have = false;
-    l1_window_fragment(p, ids, nPts, W, freq, nFreq, S, minHits0, cutoffs, nCutoffs, sParam, segLength, fl, refGroup, em);
-    nOut = em.count;
-    if (nOut > 0) {
-      base = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)nOut);
-      if ((unsigned long long)base + nOut > l1Cap) { atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
-      else if (nOut <= 2) { l1[base] = em.b0; if (nOut == 2) l1[base + 1] = em.b1; }
-      else {
-        L1Emit ew; ew.out = l1 + base; ew.frag = f; ew.count = 0; ew.write = true; ew.have = false;
-        l1_window_fragment(p, ids, nPts, W, freq, nFreq, S, minHits0, cutoffs, nCutoffs, sParam, segLength, fl, refGroup, ew);
-      }
-    }
+    const L1Frag q{pts + ptOff[2 * f], nPts, ptIds + ptOff[2 * f], W, freqAll + (size_t)li * nFreq, nFreq, S, minHitsTab[S], cutoffs, nCutoffs, sParam, segLength,
+                   fl.hg, fl.skipPrefix, refGroup};
+    r = mm_l1_literal_store<true>(q, f, l1, L1Claim{counters, l1Cap});
   }
-  stats[f].nL1 = nOut;
-  l1Off[f] = base;
+  stats[f].nL1 = r.nOut;
+  l1Off[f] = r.base;
 }
 
 // ---------------------------------------------------------------------------------------------

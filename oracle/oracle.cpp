@@ -901,7 +901,8 @@ int orc_session_map_fragment(void* h, const char* seq, int len, int fullLen, int
 
 /* computeL1CandidateRegions (l1_candidates above) on a point list the caller made, sorted by (seqId, pos, side): lets a test check that a
  * transformation of the list (the device's pre-filter of points that cannot reach minimumHits, mm_map.hip k_filter_points) leaves the
- * candidates as they are.  Uses the session's segLength, sketchSize, HG flag and cut-off table; fragLen <= segLength (windowLen == 0). */
+ * candidates as they are, or that a restatement of the sweep (mm_l1_core.h) equals it.  Uses the session's segLength, sketchSize, HG flag and
+ * cut-off table; windowLen = max(0, fragLen - segLength), and with windowLen != 0 a point's hash is its seed's key in hash_to_freq. */
 int orc_session_l1_from_points(void* h, const orc_point* pts, int64_t n, int qSketchSize, int fragLen, int minimumHits, orc_l1* out, int cap) {
   const Session& S = *(const Session*)h;
   Frag Q; Q.len = fragLen; Q.fullLen = fragLen; Q.seqCounter = 0; Q.refGroup = -1; Q.sketchSize = qSketchSize; Q.rawSketchSize = qSketchSize;

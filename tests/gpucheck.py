@@ -96,10 +96,11 @@ def steady_leg(ctx, first, rule):
 
 
 def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=U.FLAG_HG, delim="\0", kmerPct=0.001,
-                    seqCounterBase=0, check_points=True, verbose=True, mutate_index=None, device_index=False):
+                    seqCounterBase=0, check_points=True, verbose=True, mutate_index=None, device_index=False, stats_out=None):
     """contigs: [(name, uint8 array)], reads: [(name, uint8 array)].  Returns (nFragments, nMappedLoci).
     device_index: the context builds its own index from the contigs' bases (mm_index_build: a5-a7 on the device) instead of taking the
-    oracle's -- every stage downstream is then checked against the oracle on top of the DEVICE-built index."""
+    oracle's -- every stage downstream is then checked against the oracle on top of the DEVICE-built index.
+    stats_out: a list that receives the per-fragment stats array (mm_frag_stats) of the compared pass."""
     from mashmap_amd import capi
     h = oracle.session(contigs, k, L, s, pi, U.FILTER_MAP, flags, delim.encode() if delim != "\0" else b"\0", kmerPct, mutate_index=mutate_index)
     ix = oracle.export_index(h)
@@ -136,6 +137,7 @@ def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=
     ctx.keep_points(True)
     ctx.map()
     stats, l1, l2 = ctx.results()
+    if stats_out is not None: stats_out.append(stats)
     qsk = ctx.query_sketches()
     frs = ctx.fragments()
     # candidate mappings (k_l2_select: doL2Mapping's best-first walk on the device), fragment-major

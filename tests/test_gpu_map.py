@@ -287,6 +287,30 @@ def test_map_no_split_read_longer_than_the_lds(oracle):
     assert nF == 3 and nl >= 3
 
 
+@pytest.mark.parametrize("prefix", [False, True])
+def test_map_no_split_window_with_many_candidates(oracle, prefix):
+    """the writing pass of the windowed literal L1 (mm_l1_core.h, WINDOWED; more than two candidates per fragment): reads of ~1400 bp of a
+    unit that a contig holds 12 times, every copy further than segLength + windowLen from the next, so that no two candidates join; a 900 bp
+    read goes through the same kernel with windowLen == 0.  Plain, and with -Y groups that separate the two contigs."""
+    L = 1000
+    unit = U.random_dna(4100, 1500)
+    c0, c1 = U.random_dna(4101, 90000), U.random_dna(4102, 50000)
+    for j in range(12):
+        m = U.mutate(unit, 4110 + j, 0.005)[:len(unit)]
+        c0[3000 + j * 7000:3000 + j * 7000 + len(m)] = m
+    for j in range(2):
+        c1[10000 + j * 20000:10000 + j * 20000 + len(unit)] = unit
+    reads = [("r%d" % i, U.mutate(unit[i * 10:i * 10 + 1380 + 5 * i], 4120 + i, 0.02)) for i in range(8)] + [("short", unit[300:1200].copy())]
+    names, flags, delim = ["chr0", "chr1"], U.FLAG_HG | U.FLAG_NOSPLIT, "\0"
+    if prefix:
+        names, flags, delim = ["A#1#x", "B#1#x"], flags | U.FLAG_SKIP_PREFIX, "#"
+        reads = [("C#1#" + nm, a) for nm, a in reads]
+    stats = []
+    nF, nl = run_and_compare(oracle, list(zip(names, (c0, c1))), reads, k=16, L=L, s=80, pi=0.85, flags=flags, delim=delim, kmerPct=0.0, stats_out=stats)
+    assert nF == len(reads) and nl > 0
+    assert int(stats[0]["nL1"].max()) > 2, stats[0]["nL1"]
+
+
 def test_index_with_a_hyper_frequent_seed():
     """a frequent seed's point list is never read on the device (getSeedHits drops the seed first): a list of 2^23 points and more
     (a satellite array in a real genome) must not be refused.  Synthetic index: the resident one plus one such key."""
