@@ -87,11 +87,13 @@ k_key_counts(size_t nk, const uint64_t* __restrict__ keyOff, uint32_t* __restric
   if (k < nk) cnt[k] = (uint32_t)(keyOff[k + 1] - keyOff[k]);
 }
 // computeFreqHist (:424-441) on the ascending counts A[0, nk): walking the histogram from the largest count down, the threshold is
-// the smallest count v such that at most T hashes have >= v points; none (T == 0, or ties at the T-th largest reach further) -> INT_MAX
+// the smallest count v such that at most T hashes have >= v points; none (T == 0, or ties at the T-th largest reach further) -> INT_MAX.
+// T > nk (a --kmerThreshold beyond 100): every step of the walk stays below T, down to the smallest count A[0] -- as with T == nk
 __global__ void k_freq_threshold(size_t nk, const uint32_t* __restrict__ A, unsigned long long T, int32_t* __restrict__ thr) {
   if (threadIdx.x || blockIdx.x) return;
   int32_t out = 0x7fffffff;
-  if (T >= 1 && T <= nk) {
+  if (T > nk) T = nk;
+  if (T >= 1) {
     const uint32_t x = A[nk - T];
     if (nk - T == 0 || A[nk - T - 1] < x) out = (int32_t)x;
     else {

@@ -230,6 +230,32 @@ def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=
     return nF, nloci
 
 
+def compare_index(oracle, contigs, k=19, L=5000, s=130, kmerPct=0.001, out=None):
+    """mm_index_build on the contigs against the oracle's session, record for record: minmerIndex in order, the lookup map's keys, offsets
+    and points, the frequent seeds and their threshold.  Returns (records, frequent seeds) of the oracle's index.
+    out: a dict that receives the oracle's exported index ("oracle"), its threshold ("freqThreshold") and the build's per-kernel
+    (milliseconds, launches) with the timers on ("profile")."""
+    from mashmap_amd import capi
+    h = oracle.session(contigs, k, L, s, 0.85, U.FILTER_MAP, U.FLAG_HG, b"\0", kmerPct)
+    e = oracle.export_index(h)
+    ctx = capi.Context(k=k, segLength=L, sketchSize=s)
+    if out is not None: ctx.profile(True)
+    ctx.index_build([a for _, a in contigs], kmerPct=kmerPct)
+    if out is not None: out.update(oracle=e, freqThreshold=oracle.f("session_freq_threshold")(h), profile=ctx.profile_read())
+    g = ctx.index_download()
+    assert len(g["minmers"]) == len(e["minmers"])
+    for fld in ("hash", "wpos", "wpos_end", "seqId", "strand"):
+        assert (g["minmers"][fld] == e["minmers"][fld]).all(), fld
+    assert len(g["keys"]) == len(e["keys"]) and len(g["points"]) == len(e["points"])
+    assert (g["keys"] == e["keys"]).all() and (g["offsets"] == e["offsets"]).all()
+    for fld in ("pos", "hash", "seqId", "side"):
+        assert (g["points"][fld] == e["points"][fld]).all(), fld
+    assert sorted(g["freq"].tolist()) == sorted(e["freq"].tolist())
+    assert g["freqThreshold"] == oracle.f("session_freq_threshold")(h)
+    ctx.close(); oracle.free(h)
+    return len(e["minmers"]), len(e["freq"])
+
+
 def fuzz_scenario(seed0, it):
     """a random but reproducible (k, segLength, sketchSize, pi, flags, error rate, genome shape) scenario for run_and_compare"""
     r = U.splitmix64(seed0 * 7919 + it, 16)

@@ -116,6 +116,48 @@ def sample_reads(genome_contigs, seed, nreads, readlen, err):
     return out
 
 
+def leading_n(a, k):
+    """an N at (k-1)//2 and an n at k-2: both before position k-1, where the reference's addMinmers has not started looking for
+    ambiguous bases yet (commonFunc.hpp:334) and hashes the k-mers that hold them with the 'N' byte in place"""
+    a = a.copy()
+    if k >= 2: a[(k - 1) // 2] = ord("N")
+    if k >= 3: a[k - 2] = ord("n")
+    return a
+
+
+def index_edge_window(k):
+    """the smallest segment length that keeps three tiles of windows and more k-mer positions per window than either sketch size of
+    index_edge_sketch_sizes"""
+    return max(200, 6 * k)
+
+
+def index_edge_sketch_sizes(k):
+    """(sparse, dense): 2.5 s / (2 (w-k+1)) below 0.45 -- the index build compacts candidates first -- and at or above 0.5 -- every
+    k-mer position is a candidate from the start"""
+    wk = index_edge_window(k) - k + 1
+    return 12, 2 * wk // 5 + 1
+
+
+def index_edge_contigs(k):
+    """seven short contigs around one k-mer size, w = index_edge_window(k): three tiles with Ns before position k-1 and one in the
+    middle; exactly one window; one base short of a window (no record, keeps its seqId); one window and a base; a tandem repeat of
+    at most 7 distinct k-mers; runs of N; shorter than a k-mer"""
+    w = index_edge_window(k)
+    c0 = leading_n(random_dna(7000 + k, 3 * w + 7), k)
+    c0[len(c0) // 2] = ord("N")
+    cs = [c0, random_dna(7100 + k, w), random_dna(7200 + k, w - 1), random_dna(7300 + k, w + 1), tandem_repeat(7400 + k, 2 * w + 16, 7),
+          with_n_runs(random_dna(7500 + k, 2 * w + 33), 3, 4, 30), random_dna(7600 + k, max(k - 1, 1))]
+    return [("c%d" % i, a) for i, a in enumerate(cs)]
+
+
+def freq_edge_contigs():
+    """twelve diverged copies of a 3 kbp unit and 20 kbp of random sequence: at k 19, w 1000, s 50 a point-count histogram from 2 to
+    beyond 80 per seed, for the frequency filter's thresholds"""
+    unit = random_dna(81, 3000)
+    rep = np.concatenate([mutate(unit, 200 + i, 0.01) for i in range(12)])
+    return [("rep", rep), ("uniq", random_dna(82, 20000))]
+
+
 def write_fasta(path, records, width=80):
     with open(path, "wb") as f:
         for name, a in records:

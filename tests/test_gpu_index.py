@@ -5,27 +5,9 @@ import numpy as np
 import pytest
 
 import mmutil as U
+from gpucheck import compare_index as _compare
 
 pytestmark = pytest.mark.gpu
-
-
-def _compare(oracle, contigs, k=19, L=5000, s=130, kmerPct=0.001):
-    from mashmap_amd import capi
-    h = oracle.session(contigs, k, L, s, 0.85, U.FILTER_MAP, U.FLAG_HG, b"\0", kmerPct)
-    e = oracle.export_index(h)
-    ctx = capi.Context(k=k, segLength=L, sketchSize=s)
-    ctx.index_build([a for _, a in contigs], kmerPct=kmerPct)
-    g = ctx.index_download()
-    assert len(g["minmers"]) == len(e["minmers"])
-    for fld in ("hash", "wpos", "wpos_end", "seqId", "strand"):
-        assert (g["minmers"][fld] == e["minmers"][fld]).all(), fld
-    assert (g["keys"] == e["keys"]).all() and (g["offsets"] == e["offsets"]).all()
-    for fld in ("pos", "hash", "seqId", "side"):
-        assert (g["points"][fld] == e["points"][fld]).all(), fld
-    assert sorted(g["freq"].tolist()) == sorted(e["freq"].tolist())
-    assert g["freqThreshold"] == oracle.f("session_freq_threshold")(h)
-    ctx.close(); oracle.free(h)
-    return len(e["minmers"]), len(e["freq"])
 
 
 def test_index_random_contigs(oracle):

@@ -139,3 +139,45 @@ def test_fragments_longer_than_the_segment_window_len(oracle, ref, mode):
             nl2 += len(er["l2"])
         assert nl2 >= 10
         ref.free(hr); oracle.free(ho)
+
+
+@pytest.mark.parametrize("k", range(1, 65))
+def test_add_minmers_at_every_kmer_size(oracle, ref, k):
+    """the oracle the device index build is held against (tests/test_gpu_index_edges.py), against the reference at each k-mer size on the
+    same short contigs: three windows and a tail, exactly one window, one window and a base, and a tandem repeat of 7 (at small k the
+    sketch never fills); Ns before position k-1, which the reference hashes as they are, on the first and the last"""
+    w, s = U.index_edge_window(k), U.index_edge_sketch_sizes(k)[0]
+    c = [a for _, a in U.index_edge_contigs(k)]
+    seqs = [c[0], c[1], c[3], U.leading_n(c[4], k)]
+    assert [len(a) for a in seqs] == [3 * w + 7, w, w + 1, 2 * w + 16]
+    for i, a in enumerate(seqs):
+        got, exp = oracle.add_minmers(a, k, w, s, i), ref.add_minmers(a, k, w, s, i)
+        assert len(got) == len(exp) and len(exp) > 0, (k, i)
+        for f in ("hash", "wpos", "wpos_end", "seqId", "strand"):
+            assert np.array_equal(got[f], exp[f]), (k, i, f)
+
+
+@pytest.mark.parametrize("pct", [0.0, 0.5, 50.0, 100.0, 150.0])
+def test_session_frequency_threshold(oracle, ref, pct):
+    """computeFreqHist / computeFreqSeedSet / dropFreqSeedSet (winSketch.hpp:410-504) from no seed to ignore to more than there are
+    (--kmerThreshold has no range check, parseCmdArgs.hpp:498): keys, point counts, the threshold, the frequent seeds, what is left of
+    minmerIndex"""
+    k, L, s = 19, 1000, 50
+    contigs = U.freq_edge_contigs()
+    with tempfile.TemporaryDirectory() as td:
+        fa = os.path.join(td, "r.fa")
+        U.write_fasta(fa, contigs)
+        hr = ref.session([fa], k, L, s, 0.85, U.FILTER_MAP, U.FLAG_HG, b"\0", pct)
+        ho = oracle.session(contigs, k, L, s, 0.85, U.FILTER_MAP, U.FLAG_HG, b"\0", pct)
+        ko, co = oracle.keys(ho); kr, cr = ref.keys(hr)
+        assert len(kr) == 1717 and np.array_equal(ko, kr) and np.array_equal(co, cr)
+        assert oracle.f("session_freq_threshold")(ho) == ref.f("session_freq_threshold")(hr)
+        fo = [int(x) for x in ko if oracle.f("session_is_freq")(ho, int(x))]
+        fr = [int(x) for x in kr if ref.f("session_is_freq")(hr, int(x))]
+        assert fo == fr and len(fr) == {0.0: 0, 0.5: 8, 50.0: 503, 100.0: 1717, 150.0: 1717}[pct]
+        io_, ir = oracle.index_array(ho), ref.index_array(hr)
+        assert len(io_) == len(ir)
+        for f in ("hash", "wpos", "wpos_end", "seqId", "strand"):
+            assert np.array_equal(io_[f], ir[f]), f
+        assert oracle.cutoffs(ho) == ref.cutoffs(hr)
+        ref.free(hr); oracle.free(ho)
