@@ -39,7 +39,7 @@ enum {
   MM_FLAG_SKIP_PREFIX = 4,      /* skip_prefix            (parseCmdArgs.hpp:349): L1 runs once per run of interval points whose contigs share a
                                    reference group (computeMap.hpp:1146-1165).  Every fragment's points go through HBM (gather, sort), every
                                    pass is a sized pass, and the L1 stage is the literal one-thread-per-fragment kernel for every queued
-                                   fragment (mm_pass_l1_literal: literal == queued). */
+                                   fragment (mm_pass_l1_literal: literal == queued) unless MM_OPT_L1_GROUP_STREAM. */
   MM_FLAG_LOWER_TRIANGULAR = 8, /* lower_triangular       (parseCmdArgs.hpp:334) */
   MM_FLAG_NO_SPLIT = 16         /* !split                 (parseCmdArgs.hpp:427): a read longer than segLength is then ONE fragment with
                                    windowLen = len - segLength != 0 (computeMap.hpp:933, :1309); a batch that holds such a read goes through
@@ -306,8 +306,8 @@ int mm_pass_redo_cause(const mm_ctx* ctx, uint64_t* cause);
 /* Which L1 kernel took the fragments of the HBM point path, as of the context's last SIZED pass (a steady-state pass leaves both figures
  * as they were): *queued = fragments queued for that path, *literal = those of them the literal one-thread-per-fragment kernel
  * (k_l1_sweep) swept -- every one of them (a batch with a read longer than segLength excepted: 0, k_l1_window takes those) under MM_L1_LITERAL
- * or MM_FLAG_SKIP_PREFIX, otherwise what the wave-per-fragment kernel (k_l1_stream) leaves: a position group across two contigs or
- * minimumHits <= 0.  Read back with the words the sized pass reads behind the L1 sweeps anyway: no host wait
+ * or MM_FLAG_SKIP_PREFIX unless MM_OPT_L1_GROUP_STREAM, otherwise what the wave-per-fragment kernel (k_l1_stream) leaves: a position
+ * group across two contigs (of one reference-group extent, in its grouped form) or minimumHits <= 0.  Read back with the words the sized pass reads behind the L1 sweeps anyway: no host wait
  * more.  Either pointer may be NULL.  Purely additive: MM_ABI_VERSION stays 2. */
 int mm_pass_l1_literal(const mm_ctx* ctx, uint64_t* queued, uint64_t* literal);
 int mm_result_counts(const mm_ctx* ctx, size_t* nL1, size_t* nL2);
@@ -335,8 +335,13 @@ int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
  * context's staging buffers (the first one, or one that outgrew them) then sizes them for a batch of that many fragments -- per-fragment
  * buffers directly, count-dependent ones (candidates, L2 streams, mappings) in proportion -- so that a caller whose batches grow (skch::Map
  * ramps its device passes up from one reader batch to four) pays for sizing and allocation once.
+ * MM_OPT_L1_GROUP_STREAM (default 0): with 1, under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped form of the wave-per-fragment
+ * kernel (k_l1_stream: one body per reference-group extent of the sorted points) and the literal kernel takes what it leaves -- a position
+ * group across two contigs of one extent, minimumHits <= 0; mm_pass_l1_literal then reports that list's length.  Same candidates, same
+ * order.  MM_L1_LITERAL still forces the literal kernel; batches with a read longer than segLength are untouched.  Without
+ * MM_FLAG_SKIP_PREFIX the option does nothing.  Purely additive: MM_ABI_VERSION stays 2.
  */
-enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3 };
+enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4 };
 int mm_set_option(mm_ctx* ctx, int option, int value);
 /* sorted interval points of fragment f after the seqId filters of computeMap.hpp:891-896 (needs MM_OPT_KEEP_POINTS; (seqId,pos,side) only, hash = 0) */
 int mm_points_download(mm_ctx* ctx, size_t frag, mm_interval_point* out, size_t cap, size_t* n);

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libmashmap_hip.so")
 
 MM_FLAG_HG_FILTER, MM_FLAG_SKIP_SELF, MM_FLAG_SKIP_PREFIX, MM_FLAG_LOWER_TRIANGULAR, MM_FLAG_NO_SPLIT = 1, 2, 4, 8, 16
+MM_OPT_KEEP_POINTS, MM_OPT_KEEP_FULL_INDEX, MM_OPT_RESERVE_FRAGMENTS, MM_OPT_L1_GROUP_STREAM = 1, 2, 3, 4
 # bits of Context.pass_redo_cause() (include/mashmap_hip.h: MM_REDO_*)
 (MM_REDO_POINTS, MM_REDO_L1, MM_REDO_L2_LOCI, MM_REDO_L2_SLOTS, MM_REDO_L2_STREAM, MM_REDO_L2_OPS, MM_REDO_L2_LIST, MM_REDO_L2_CANDS,
  MM_REDO_MAPPINGS, MM_REDO_NO_STREAM_BUFFER) = (1 << i for i in range(10))
@@ -464,6 +465,11 @@ class Context:
     def reserve_fragments(self, n):
         """MM_OPT_RESERVE_FRAGMENTS: the next sized pass sizes every staging buffer for a batch of n fragments"""
         self._ck(self.lib.mm_set_option(self.h, 3, int(n)), "mm_set_option")
+
+    def l1_group_stream(self, on=True):
+        """MM_OPT_L1_GROUP_STREAM: under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped wave-per-fragment L1 kernel; the
+        literal kernel takes what it leaves (pass_l1_literal() then reports that list's length)"""
+        self._ck(self.lib.mm_set_option(self.h, MM_OPT_L1_GROUP_STREAM, 1 if on else 0), "mm_set_option")
 
     def keep_points(self, on=True):
         """MM_OPT_KEEP_POINTS: keep every fragment's sorted interval points in HBM (needed by points()); on=2: ... after the interval-point

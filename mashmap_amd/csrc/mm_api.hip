@@ -104,6 +104,7 @@ int mm_set_option(mm_ctx* c, int option, int value) {
   if (option == MM_OPT_KEEP_POINTS) { c->keepPoints = value != 0; c->keepFiltered = value == 2; c->ptsCap = 0; return MM_OK; }
   if (option == MM_OPT_KEEP_FULL_INDEX) { c->keepFullIndex = value != 0; return MM_OK; }
   if (option == MM_OPT_RESERVE_FRAGMENTS) { c->reserveFrags = value > 0 ? (size_t)value : 0; return MM_OK; }
+  if (option == MM_OPT_L1_GROUP_STREAM) { c->l1GroupStream = value != 0; return MM_OK; }
   c->err = "mm_set_option: unknown option"; return MM_ERR_ARG;
 }
 

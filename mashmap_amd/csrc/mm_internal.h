@@ -283,6 +283,7 @@ struct mm_ctx {
   uint64_t redoCause = 0;                               // MM_REDO_* of the steady attempt the last mm_map_fragments had redone, 0 when it had none (mm_pass_redo_cause)
   bool keepFiltered = false;                            // MM_OPT_KEEP_POINTS = 2: ... and k_filter_points runs on them as it does on a queued fragment's (mm_points_download returns what it leaves)
   bool keepPoints = false;                              // mm_set_option(MM_OPT_KEEP_POINTS): route every fragment through the HBM point list
+  bool l1GroupStream = false;                           // mm_set_option(MM_OPT_L1_GROUP_STREAM): under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped k_l1_stream first
   size_t reserveFrags = 0;                              // mm_set_option(MM_OPT_RESERVE_FRAGMENTS): fragments of the largest batch the caller will upload; sized passes size for it
 
   // profiling

@@ -12,6 +12,7 @@
 //     k_gather_points, k_filter_points                    the interval points into dPts; those that cannot reach minimumHits dropped
 //     k_sort_points_wave / _block / _global, k_classify_sort   sorters by list length (registers, LDS, HBM) and the split between them
 //     k_l1_stream           L1 by a wave that streams the sorted points
+//     k_l1_stream_groups    the same under -Y reference groups, one body per group extent (MM_OPT_L1_GROUP_STREAM)
 //     k_l1_sweep            L1 by the literal one-thread-per-fragment sweep of mm_l1_core.h (what k_l1_stream leaves, or everything)
 //     k_l1_window           the same sweep for fragments longer than segLength (windowLen != 0)
 //   map_pass / mm_launch_map   one pass over the resident sketches, stage by stage; sized or steady-state
@@ -1226,6 +1227,196 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_l1_stream_groups: k_l1_stream under -Y reference groups (MM_OPT_L1_GROUP_STREAM).  Map::doL1Mapping calls
+// computeL1CandidateRegions once per run of points whose contigs share a reference group (computeMap.hpp:1146-1165).  The wave walks the sorted list in those extents [b, e) -- the next one
+// found 64 points at a time by a ballot of "group differs"; a group whose contigs are not adjacent comes back as an extent of its own,
+// as in the reference -- and runs k_l1_stream's body on each: its own best count, its own copy of minimumHits, its last position group
+// never flagged, the carried count starting at 0, no neighbour across its ends, runs joined inside it only.  The candidates of all
+// extents are counted together, claimed once and written in extent order.  A position group across two contigs INSIDE an extent (one
+// shared by the last point of an extent and the first of the next is none: those are two calls) or minimumHits <= 0 leaves the whole
+// fragment to k_l1_sweep.  A kernel of its own: sharing the body with k_l1_stream changed that kernel's code (register allocation,
+// 23 instructions more), and the plain path is to stay as it is.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_l1_stream_groups(int nList, const int32_t* __restrict__ list, const int64_t* __restrict__ ptOff, const uint64_t* __restrict__ pts,
+            mm_frag_stats* __restrict__ stats, const int32_t* __restrict__ minHitsTab, const int32_t* __restrict__ cutoffs, int nCutoffs,
+            int sParam, int segLength, int hg, mm_l1_candidate* __restrict__ l1, unsigned long long l1Cap, int64_t* __restrict__ l1Off,
+            int32_t* __restrict__ lit, unsigned int* __restrict__ litCount, unsigned long long* __restrict__ counters /* dCounters + MM_CW_PASS: the L1 cursor and its overflow flag */,
+            const unsigned long long* __restrict__ nDev, const int32_t* __restrict__ ptKept /* points at the head of the sorted list (k_gather_points / k_filter_points) */,
+            const int32_t* __restrict__ refGroup) {
+  __shared__ L1Run bufAll[4][MM_STREAM_BUF];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  L1Run* buf = bufAll[wave];
+  if (nDev) nList = (int)*nDev;
+  auto one = [&](const int f) {
+  const int nPts = ptKept[f], S = stats[f].sketchSize;
+  if (nPts <= 0 || S <= 0) { if (lane == 0) { stats[f].nL1 = 0; l1Off[f] = 0; } return; }
+  const uint64_t* p = pts + ptOff[2 * f];
+  int minHits = minHitsTab[S];
+
+  // one chunk of 64 points of the extent [b, e): key, overlap count after the point, whether it ends a position group
+  auto chunk = [&](int b, int e, int i0, int carry, uint64_t& k, int& run, bool& gLast, bool& mixed, int& sum) {
+    const int idx = i0 + lane;
+    const bool valid = idx < e;
+    k = valid ? p[idx] : MM_EMPTY;
+    const uint64_t prv = (valid && idx > b) ? p[idx - 1] : MM_EMPTY;
+    const uint64_t nxt = (idx + 1 < e) ? p[idx + 1] : MM_EMPTY;
+    mixed = valid && prv != MM_EMPTY && (uint32_t)(prv >> 1) == (uint32_t)(k >> 1) && (prv >> 33) != (k >> 33);
+    const int delta = valid ? ((k & 1ull) ? 1 : -1) : 0;
+    run = carry + mm_wave_excl_scan(delta) + delta;
+    gLast = valid && (nxt == MM_EMPTY || (uint32_t)(nxt >> 1) != (uint32_t)(k >> 1));
+    sum = mm_wave_sum(delta);
+  };
+
+  // ---- pass 1 over [b, e): best overlap count, number of groups, the mixed-group test ----
+  auto pass1 = [&](int b, int e, int& best, int& G, bool& anyMixed) {
+    int carry = 0;
+    for (int i0 = b; i0 < e; i0 += 64) {
+      uint64_t k; int run, sum; bool gLast, mixed;
+      chunk(b, e, i0, carry, k, run, gLast, mixed, sum);
+      if (gLast && run > best) best = run;
+      G += (int)__popcll(__ballot(gLast));
+      anyMixed = anyMixed || __ballot(mixed) != 0;
+      carry += sum;
+    }
+    best = mm_wave_max(best);
+  };
+  auto hgRule = [&](int best, int G, int& mh) {                   // computeMap.hpp:984-998
+    bool go = G > 0;
+    if (go && hg) {
+      if (best < mh) go = false;
+      else {
+        const double div = (double)sParam / 1000.0 > 1.0 ? (double)sParam / 1000.0 : 1.0;
+        int ci = (int)((double)(best < S ? best : S) / div);
+        if (ci >= nCutoffs) ci = nCutoffs - 1;
+        const int cut = cutoffs[ci];
+        mh = cut > mh ? cut : mh;
+      }
+    }
+    return go;
+  };
+  auto toLiteral = [&]() { if (lane == 0) lit[atomicAdd(litCount, 1u)] = f; };   // the literal kernel's business
+
+  if (minHits <= 0) { toLiteral(); return; }
+
+  // ---- pass 2: runs of flagged groups -> joined candidates; counted (the first MM_STREAM_BUF kept in LDS), then written ----
+  int total = 0; long long base = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    const bool write = pass == 1;
+    int count = 0;
+    bool have = false; L1Run pend{0, 0, 0, 0};
+    auto flush = [&]() {
+      if (have) {
+        if (lane == 0) {
+          if (write) { mm_l1_candidate o; o.frag = f; o.seqId = pend.seq; o.rangeStartPos = pend.start; o.rangeEndPos = pend.end; o.intersectionSize = pend.isize; l1[base + count] = o; }
+          else if (count < MM_STREAM_BUF) buf[count] = pend;
+        }
+        count++; have = false;
+      }
+    };
+    auto emit = [&](int seq, int start, int end, int isize) {      // L1Emit::run inside one reference group
+      if (have && seq == pend.seq && !(start > pend.end + segLength)) { pend.end = end; pend.isize = isize > pend.isize ? isize : pend.isize; }
+      else { flush(); pend.seq = seq; pend.start = start; pend.end = end; pend.isize = isize; have = true; }
+    };
+    // the extent [b, e) with its G groups and its minimumHits; ends with the pending candidate flushed (L1Emit::run's firstOfGroup)
+    auto pass2 = [&](int b, int e, int G, int minHits) {
+      bool inRun = false; int rSeq = 0, rStart = 0, rEnd = 0, rSize = 0;
+      int carry = 0, gBase = 0;
+      bool prevFlagC = false; int prevSeqC = 0;                   // the last group of the chunks so far: flagged?, its contig
+      for (int i0 = b; i0 < e; i0 += 64) {
+        uint64_t k; int run, sum; bool gLast, mixed;
+        chunk(b, e, i0, carry, k, run, gLast, mixed, sum);
+        carry += sum;
+        const uint64_t GM = __ballot(gLast);
+        if (!GM) continue;
+        const int gidx = gBase + (int)mm_popc_below(GM);
+        gBase += (int)__popcll(GM);
+        const bool flag = gLast && gidx < G - 1 && run >= minHits;
+        const uint64_t FM = __ballot(flag);
+        const int gseq = (int)(k >> 33), gpos = (int)(uint32_t)(k >> 1);
+        const int lastG = 63 - (int)__builtin_clzll(GM);
+        const bool lastFlag = (FM >> lastG) & 1ull; const int lastSeq = __builtin_amdgcn_readlane(gseq, lastG);
+        if (FM || prevFlagC) {
+          // the group before this lane's: in the chunk, or the carried one
+          const uint64_t below = GM & ((1ull << lane) - 1ull);
+          const int pl = below ? 63 - (int)__builtin_clzll(below) : lane;
+          const int sseq = __shfl(gseq, pl);
+          const bool pf = below ? (((FM >> pl) & 1ull) != 0) : prevFlagC;
+          const int ps = below ? sseq : prevSeqC;
+          // a flagged group continues the run of a flagged predecessor on the same contig; the groups that matter are the others:
+          // flagged ones that start a run, and unflagged ones right behind a flagged one, which end it.  Between two of those every
+          // flagged group just extends the run: its end is the last one's position, its size the largest count.
+          const uint64_t startM = __ballot(flag && !(pf && ps == gseq));
+          const uint64_t breakM = __ballot(gLast && !flag && pf);
+          auto extend = [&](int lo, int hi) {                       // flagged groups of the lanes [lo, hi) join the open run
+            if (lo >= 64) return;
+            const uint64_t m = FM & ~((1ull << lo) - 1ull) & (hi >= 64 ? ~0ull : ((1ull << hi) - 1ull));
+            if (!m) return;
+            rEnd = __builtin_amdgcn_readlane(gpos, 63 - (int)__builtin_clzll(m));
+            const int mx = mm_wave_max((flag && lane >= lo && lane < hi) ? run : 0);
+            rSize = mx > rSize ? mx : rSize;
+          };
+          uint64_t ev = startM | breakM;
+          int segLo = 0;
+          while (ev) {
+            const int bpos = (int)__builtin_ctzll(ev);
+            ev &= ev - 1ull;
+            if (inRun) extend(segLo, bpos);
+            if ((breakM >> bpos) & 1ull) { if (inRun) emit(rSeq, rStart, rEnd, rSize); inRun = false; }
+            else {
+              if (inRun) emit(rSeq, rStart, rEnd, rSize);
+              rSeq = __builtin_amdgcn_readlane(gseq, bpos); rStart = __builtin_amdgcn_readlane(gpos, bpos); rEnd = rStart;
+              rSize = __builtin_amdgcn_readlane(run, bpos); inRun = true;
+            }
+            segLo = bpos + 1;
+          }
+          if (inRun) extend(segLo, 64);
+        }
+        prevFlagC = lastFlag; prevSeqC = lastSeq;
+      }
+      if (inRun) emit(rSeq, rStart, rEnd, rSize);
+      flush();
+    };
+    {
+      for (int b = 0; b < nPts;) {
+        // the extent's end: the first point behind b whose contig is of another group
+        const int g0 = refGroup[(int)(p[b] >> 33)];
+        int e = nPts;
+        for (int i0 = b; i0 < nPts; i0 += 64) {
+          const int idx = i0 + lane;
+          const uint64_t D = __ballot(idx < nPts && refGroup[(int)(p[idx < nPts ? idx : b] >> 33)] != g0);
+          if (D) { e = i0 + (int)__builtin_ctzll(D); break; }
+        }
+        int bestE = 0, GE = 0; bool mixedE = false;
+        pass1(b, e, bestE, GE, mixedE);
+        if (mixedE) { toLiteral(); return; }                      // (found by the counting pass: nothing of the fragment is out yet)
+        int mh = minHits;
+        if (hgRule(bestE, GE, mh)) pass2(b, e, GE, mh);
+        b = e;
+      }
+    }
+    if (!write) {
+      total = count;
+      if (total > 0) {
+        long long b0 = 0;
+        if (lane == 0) b0 = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)total);
+        base = ((long long)__builtin_amdgcn_readfirstlane((int)(b0 >> 32)) << 32) | (unsigned int)__builtin_amdgcn_readfirstlane((int)b0);
+        if ((unsigned long long)base + (unsigned long long)total > l1Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); total = 0; }
+      }
+      if (total > 0 && total <= MM_STREAM_BUF) {                   // the counting pass kept them all
+        __threadfence_block();
+        if (lane < total) { const L1Run r = buf[lane]; mm_l1_candidate o; o.frag = f; o.seqId = r.seq; o.rangeStartPos = r.start; o.rangeEndPos = r.end; o.intersectionSize = r.isize; l1[base + lane] = o; }
+        break;
+      }
+      if (total == 0) break;
+    }
+  }
+  if (lane == 0) { stats[f].nL1 = total; l1Off[f] = total > 0 ? base : 0; }
+  };
+  for (int li = blockIdx.x * 4 + wave; li < nList; li += gridDim.x * 4) { one(list[li]); __threadfence_block(); }
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_l1_sweep: one thread per queued fragment over its sorted points (windowLen == 0, i.e. split mode): the literal two-pointer
 // restatement of computeMap.hpp:916-1116 in mm_l1_core.h, which the CPU suite checks against the oracle.
 // ---------------------------------------------------------------------------------------------
@@ -1480,8 +1671,9 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
   unsigned long long* const cnt = p.cnt;
   const unsigned long long fusedL1 = p.hc[MM_PC_L1_CAND];
   // a wave per fragment streams the sorted points; what it cannot take (a position group across two contigs, minimumHits 0) and
-  // every fragment under -Y reference groups goes to the literal one-thread-per-fragment kernel
-  const bool stream = !p.fl.skipPrefix && !c->env.l1Literal && !p.windowed;
+  // every fragment under -Y reference groups goes to the literal one-thread-per-fragment kernel -- unless MM_OPT_L1_GROUP_STREAM: then
+  // the grouped form of the wave kernel comes first there too
+  const bool stream = (!p.fl.skipPrefix || c->l1GroupStream) && !c->env.l1Literal && !p.windowed;
   for (int attempt = 0; attempt < 8; attempt++) {
     if (!p.steady) {
       MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L1_CAND, &fusedL1, 8, hipMemcpyHostToDevice, c->stream));
@@ -1502,7 +1694,11 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
         unsigned int* lit = p.lens + MM_SL_LITERAL;
         if (stream) {
           MM_HIP(c, hipMemsetAsync(lit, 0, (size_t)(MM_SL_END - MM_SL_LITERAL) * 4, c->stream));
-          hipLaunchKernelGGL(k_l1_stream, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
+          if (p.fl.skipPrefix) hipLaunchKernelGGL(k_l1_stream_groups, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
+                             c->dPts.as<uint64_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
+                             (int)c->nCutoffs, s, c->P.segLength, p.fl.hg, c->dL1.as<mm_l1_candidate>(), (unsigned long long)p.denseCap,
+                             c->dL1Off.as<int64_t>(), c->dListB.as<int32_t>(), lit, cnt, p.nBigDev, c->dPtKept.as<int32_t>(), I.refGroup.as<int32_t>());
+          else hipLaunchKernelGGL(k_l1_stream, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
                              c->dPts.as<uint64_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
                              (int)c->nCutoffs, s, c->P.segLength, p.fl.hg, c->dL1.as<mm_l1_candidate>(), (unsigned long long)p.denseCap,
                              c->dL1Off.as<int64_t>(), c->dListB.as<int32_t>(), lit, cnt, p.nBigDev, c->dPtKept.as<int32_t>());
@@ -1524,6 +1720,7 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
     MM_SYNC(c);
     // (set again by every attempt of this loop: the last one, whose candidates stand, is the one that counts)
     p.nLit = p.windowed ? 0ull : stream ? (unsigned long long)((const unsigned int*)(c->hPass + MM_CW_SORT_LENS))[MM_SL_LITERAL] : (unsigned long long)nBig;
+    if (c->env.debug && stream && p.fl.skipPrefix) fprintf(stderr, "[mm] point path: of %d queued fragments the literal L1 kernel took %llu (reference groups on the wave kernel)\n", nBig, p.nLit);
     if (!p.hc[MM_PC_L1_OVERFLOW]) return MM_OK;
     // grow, keeping the fused candidates already in the buffer
     const size_t newCap = (size_t)p.hc[MM_PC_L1_CAND] + (size_t)p.hc[MM_PC_L1_CAND] / 8 + 1024;

@@ -133,6 +133,11 @@ class Sketch {
         std::cerr << "[mashmap_hip::skch::Sketch] ERROR: " << mm_last_error(nullptr) << std::endl;
         exit(1);
       }
+      // -Y: the queued fragments' L1 stage on the grouped wave-per-fragment kernel; the literal kernel takes what that leaves
+      if (p.skip_prefix && mm_set_option(c, MM_OPT_L1_GROUP_STREAM, 1) != MM_OK) {
+        std::cerr << "[mashmap_hip::skch::Sketch] ERROR: mm_set_option: " << mm_last_error(c) << std::endl;
+        exit(1);
+      }
       ctxs_.push_back(c);
     }
     ctx_ = ctxs_[0];
