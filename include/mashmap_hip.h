@@ -43,7 +43,8 @@ enum {
   MM_FLAG_LOWER_TRIANGULAR = 8, /* lower_triangular       (parseCmdArgs.hpp:334) */
   MM_FLAG_NO_SPLIT = 16         /* !split                 (parseCmdArgs.hpp:427): a read longer than segLength is then ONE fragment with
                                    windowLen = len - segLength != 0 (computeMap.hpp:933, :1309); a batch that holds such a read goes through
-                                   the literal kernels (k_l1_window, k_l2_window: exact, not fast).  A read of any length: one that does not
+                                   the literal kernels (k_l1_window, k_l2_window: exact, not fast; MM_OPT_L2_WINDOW_WAVE puts the L2 stage on
+                                   a wave per candidate first).  A read of any length: one that does not
                                    fit a CU's LDS (a whole contig as a read) is sketched by the exact kernel from global memory. */
 };
 
@@ -310,6 +311,13 @@ int mm_pass_redo_cause(const mm_ctx* ctx, uint64_t* cause);
  * group across two contigs (of one reference-group extent, in its grouped form) or minimumHits <= 0.  Read back with the words the sized pass reads behind the L1 sweeps anyway: no host wait
  * more.  Either pointer may be NULL.  Purely additive: MM_ABI_VERSION stays 2. */
 int mm_pass_l1_literal(const mm_ctx* ctx, uint64_t* queued, uint64_t* literal);
+/* Which L2 kernel took the candidates of a batch with a read longer than segLength (MM_FLAG_NO_SPLIT, windowLen != 0), as of the context's
+ * last SIZED pass: *candidates = L1 candidates the windowed L2 stage took, *literal = those of them the literal one-thread-per-candidate
+ * kernel (k_l2_window) swept -- every one without MM_OPT_L2_WINDOW_WAVE, otherwise the ones the wave-per-candidate kernel hands over: more
+ * open records at once than its LDS heap holds (2048), more than 9 tied loci at the best shared count.  0 / 0 for a batch without such a
+ * read.  Read back with the words the stage reads anyway: no host wait more.  Either pointer may be NULL.  Purely additive:
+ * MM_ABI_VERSION stays 2. */
+int mm_pass_l2_window(const mm_ctx* ctx, uint64_t* candidates, uint64_t* literal);
 int mm_result_counts(const mm_ctx* ctx, size_t* nL1, size_t* nL2);
 /* any pointer may be NULL.  l1/l2 are sorted by (frag, emission order of the reference) */
 int mm_results_download(mm_ctx* ctx, mm_frag_stats* stats, mm_l1_candidate* l1, mm_l2_locus* l2);
@@ -340,8 +348,12 @@ int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
  * group across two contigs of one extent, minimumHits <= 0; mm_pass_l1_literal then reports that list's length.  Same candidates, same
  * order.  MM_L1_LITERAL still forces the literal kernel; batches with a read longer than segLength are untouched.  Without
  * MM_FLAG_SKIP_PREFIX the option does nothing.  Purely additive: MM_ABI_VERSION stays 2.
+ * MM_OPT_L2_WINDOW_WAVE (default 0): with 1, the L2 stage of a batch with a read longer than segLength (MM_FLAG_NO_SPLIT) runs on
+ * k_l2_window_wave -- one wave per L1 candidate, its query sketch, SlideMapper cells and heap of open records in LDS, 64 events of the contig's
+ * stream (inserts and evictions; the inserts are the index records) per step, their records located and gated in parallel -- and the literal k_l2_window sweeps the candidates that kernel hands over (mm_pass_l2_window).  Same loci,
+ * same order.  Sketch sizes above 2046 and batches without such a read are untouched.  Purely additive: MM_ABI_VERSION stays 2.
  */
-enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4 };
+enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5 };
 int mm_set_option(mm_ctx* ctx, int option, int value);
 /* sorted interval points of fragment f after the seqId filters of computeMap.hpp:891-896 (needs MM_OPT_KEEP_POINTS; (seqId,pos,side) only, hash = 0) */
 int mm_points_download(mm_ctx* ctx, size_t frag, mm_interval_point* out, size_t cap, size_t* n);

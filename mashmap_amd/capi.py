@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libmashmap_hip.so")
 
 MM_FLAG_HG_FILTER, MM_FLAG_SKIP_SELF, MM_FLAG_SKIP_PREFIX, MM_FLAG_LOWER_TRIANGULAR, MM_FLAG_NO_SPLIT = 1, 2, 4, 8, 16
-MM_OPT_KEEP_POINTS, MM_OPT_KEEP_FULL_INDEX, MM_OPT_RESERVE_FRAGMENTS, MM_OPT_L1_GROUP_STREAM = 1, 2, 3, 4
+MM_OPT_KEEP_POINTS, MM_OPT_KEEP_FULL_INDEX, MM_OPT_RESERVE_FRAGMENTS, MM_OPT_L1_GROUP_STREAM, MM_OPT_L2_WINDOW_WAVE = 1, 2, 3, 4, 5
 # bits of Context.pass_redo_cause() (include/mashmap_hip.h: MM_REDO_*)
 (MM_REDO_POINTS, MM_REDO_L1, MM_REDO_L2_LOCI, MM_REDO_L2_SLOTS, MM_REDO_L2_STREAM, MM_REDO_L2_OPS, MM_REDO_L2_LIST, MM_REDO_L2_CANDS,
  MM_REDO_MAPPINGS, MM_REDO_NO_STREAM_BUFFER) = (1 << i for i in range(10))
@@ -134,6 +134,7 @@ def load():
         "mm_pass_totals": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_redo_cause": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "mm_pass_l1_literal": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_pass_l2_window": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_reads_exchange": (C.c_int, [vp, C.c_int]),
         "mm_reads_upload_packed_parts": (C.c_int, [vp, vp, sz, C.c_int32]),
         "mm_reads_prefetch_packed_append": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_int)]),
@@ -165,7 +166,7 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_reads_upload_packed", "mm_reads_prefetch_packed", "mm_pack_read", "mm_pack_read_portable", "mm_reads_packed_download",
            "mm_index_layout_get", "mm_pass_stats", "mm_comm_info", "mm_pass_totals", "mm_reads_exchange", "mm_reads_upload_packed_parts",
            "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
-           "mm_pass_l1_literal"]
+           "mm_pass_l1_literal", "mm_pass_l2_window"]
 
 
 def stat_sketch_cutoffs(sketchSize, k, hg=True):
@@ -429,6 +430,13 @@ class Context:
         self._ck(self.lib.mm_pass_l1_literal(self.h, C.byref(q), C.byref(l)), "mm_pass_l1_literal")
         return int(q.value), int(l.value)
 
+    def pass_l2_window(self):
+        """(candidates, literal) of the last sized pass: L1 candidates the windowed L2 stage took (a batch with a read longer than segLength
+        under MM_FLAG_NO_SPLIT; 0 otherwise), and those of them the literal k_l2_window swept"""
+        n, l = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.mm_pass_l2_window(self.h, C.byref(n), C.byref(l)), "mm_pass_l2_window")
+        return int(n.value), int(l.value)
+
     def reads_exchange(self, slot):
         """swaps the resident batch of reads with the one parked in `slot` (0 .. MM_BATCH_SLOTS - 1); no copy"""
         self._ck(self.lib.mm_reads_exchange(self.h, slot), "mm_reads_exchange")
@@ -470,6 +478,11 @@ class Context:
         """MM_OPT_L1_GROUP_STREAM: under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped wave-per-fragment L1 kernel; the
         literal kernel takes what it leaves (pass_l1_literal() then reports that list's length)"""
         self._ck(self.lib.mm_set_option(self.h, MM_OPT_L1_GROUP_STREAM, 1 if on else 0), "mm_set_option")
+
+    def l2_window_wave(self, on=True):
+        """MM_OPT_L2_WINDOW_WAVE: the L2 stage of a batch with a read longer than segLength goes to the wave-per-candidate kernel; the
+        literal kernel takes what it hands over (pass_l2_window() then reports that list's length)"""
+        self._ck(self.lib.mm_set_option(self.h, MM_OPT_L2_WINDOW_WAVE, 1 if on else 0), "mm_set_option")
 
     def keep_points(self, on=True):
         """MM_OPT_KEEP_POINTS: keep every fragment's sorted interval points in HBM (needed by points()); on=2: ... after the interval-point

@@ -105,6 +105,7 @@ int mm_set_option(mm_ctx* c, int option, int value) {
   if (option == MM_OPT_KEEP_FULL_INDEX) { c->keepFullIndex = value != 0; return MM_OK; }
   if (option == MM_OPT_RESERVE_FRAGMENTS) { c->reserveFrags = value > 0 ? (size_t)value : 0; return MM_OK; }
   if (option == MM_OPT_L1_GROUP_STREAM) { c->l1GroupStream = value != 0; return MM_OK; }
+  if (option == MM_OPT_L2_WINDOW_WAVE) { c->l2WindowWave = value != 0; return MM_OK; }
   c->err = "mm_set_option: unknown option"; return MM_ERR_ARG;
 }
 
@@ -593,6 +594,12 @@ int mm_pass_redo_cause(const mm_ctx* c, uint64_t* cause) {
 int mm_pass_l1_literal(const mm_ctx* c, uint64_t* queued, uint64_t* literal) {
   if (queued) *queued = c->prevBig;
   if (literal) *literal = c->prevLit;
+  return MM_OK;
+}
+
+int mm_pass_l2_window(const mm_ctx* c, uint64_t* candidates, uint64_t* literal) {
+  if (candidates) *candidates = c->winCands;
+  if (literal) *literal = c->winLit;
   return MM_OK;
 }
 

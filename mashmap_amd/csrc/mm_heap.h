@@ -1,4 +1,4 @@
-// mashmap_amd/csrc/mm_heap.h -- binary max-heap over an index array with the exact element movements of libstdc++'s
+// mashmap_amd/csrc/mm_heap.h -- binary max-heap over an array of indices (or of any trivially copied element type T) with the exact element movements of libstdc++'s
 // std::make_heap / std::pop_heap (bits/stl_heap.h: __push_heap, __adjust_heap, __make_heap, __pop_heap).
 //
 // Map::mapSingleQueryFrag heaps a fragment's L1 candidates by intersectionSize (std::make_heap, computeMap.hpp:791) and
@@ -17,8 +17,8 @@
 #endif
 
 // less(a, b): "a orders before b" == comp(a, b) of the std:: calls (a max-heap keeps the element that is not less than any at the front)
-template <class Less>
-MM_HD void mm_heap_push(int32_t* first, int hole, int top, int32_t value, Less less) {
+template <class T, class Less>
+MM_HD void mm_heap_push(T* first, int hole, int top, T value, Less less) {
   int parent = (hole - 1) / 2;
   while (hole > top && less(first[parent], value)) {
     first[hole] = first[parent];
@@ -28,8 +28,8 @@ MM_HD void mm_heap_push(int32_t* first, int hole, int top, int32_t value, Less l
   first[hole] = value;
 }
 
-template <class Less>
-MM_HD void mm_heap_adjust(int32_t* first, int hole, int len, int32_t value, Less less) {
+template <class T, class Less>
+MM_HD void mm_heap_adjust(T* first, int hole, int len, T value, Less less) {
   const int top = hole;
   int child = hole;
   while (child < (len - 1) / 2) {
@@ -46,12 +46,12 @@ MM_HD void mm_heap_adjust(int32_t* first, int hole, int len, int32_t value, Less
   mm_heap_push(first, hole, top, value, less);
 }
 
-template <class Less>
-MM_HD void mm_make_heap(int32_t* first, int len, Less less) {
+template <class T, class Less>
+MM_HD void mm_make_heap(T* first, int len, Less less) {
   if (len < 2) return;
   int parent = (len - 2) / 2;
   while (true) {
-    const int32_t v = first[parent];
+    const T v = first[parent];
     mm_heap_adjust(first, parent, len, v, less);
     if (parent == 0) return;
     parent--;
@@ -59,10 +59,10 @@ MM_HD void mm_make_heap(int32_t* first, int len, Less less) {
 }
 
 // std::pop_heap(first, first + len): the front moves to first[len - 1], the rest is a heap again
-template <class Less>
-MM_HD void mm_pop_heap(int32_t* first, int len, Less less) {
+template <class T, class Less>
+MM_HD void mm_pop_heap(T* first, int len, Less less) {
   if (len < 2) return;
-  const int32_t v = first[len - 1];
+  const T v = first[len - 1];
   first[len - 1] = first[0];
   mm_heap_adjust(first, 0, len - 1, v, less);
 }

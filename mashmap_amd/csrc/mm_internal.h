@@ -284,6 +284,8 @@ struct mm_ctx {
   bool keepFiltered = false;                            // MM_OPT_KEEP_POINTS = 2: ... and k_filter_points runs on them as it does on a queued fragment's (mm_points_download returns what it leaves)
   bool keepPoints = false;                              // mm_set_option(MM_OPT_KEEP_POINTS): route every fragment through the HBM point list
   bool l1GroupStream = false;                           // mm_set_option(MM_OPT_L1_GROUP_STREAM): under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped k_l1_stream first
+  bool l2WindowWave = false;                            // mm_set_option(MM_OPT_L2_WINDOW_WAVE): the windowed L2 stage on k_l2_window_wave first, the literal k_l2_window takes what it hands over
+  size_t winCands = 0, winLit = 0;                      // candidates the windowed L2 stage took in the last sized pass, and those k_l2_window swept (mm_pass_l2_window)
   size_t reserveFrags = 0;                              // mm_set_option(MM_OPT_RESERVE_FRAGMENTS): fragments of the largest batch the caller will upload; sized passes size for it
 
   // profiling

@@ -25,6 +25,7 @@
 #include "mm_internal.h"
 #include "mm_device.h"
 #include "mm_heap.h"
+#include "mm_l2_window_core.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -877,9 +878,12 @@ k_l2_window(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__
             const WinExt* __restrict__ ext, const int64_t* __restrict__ offH, const int64_t* __restrict__ offT, const int32_t* __restrict__ cntT,
             int32_t* __restrict__ heapAll, uint64_t* __restrict__ tabKeys, int32_t* __restrict__ tabVals, ExactCell* __restrict__ cells,
             const int64_t* __restrict__ l1Off, L2Tmp* __restrict__ tmp, int locap, mm_l2_locus* __restrict__ l2, unsigned long long l2Cap,
-            int64_t* __restrict__ l2First, int32_t* __restrict__ l2Num, unsigned long long* __restrict__ counters) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+            int64_t* __restrict__ l2First, int32_t* __restrict__ l2Num, unsigned long long* __restrict__ counters,
+            const int32_t* __restrict__ list /* null: every candidate; else the candidates k_l2_window_wave handed over ... */,
+            const unsigned long long* __restrict__ nListDev /* ... whose number stays on the device */) {
+  int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nCand) return;
+  if (list) { if ((unsigned long long)c >= *nListDev) return; c = list[c]; }
   const mm_l1_candidate cand = l1[c];
   const int f = cand.frag;
   const mm_frag_stats fst = stats[f];
@@ -1020,6 +1024,164 @@ k_l2_window(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_l2_window_wave (MM_OPT_L2_WINDOW_WAVE): the windowLen != 0 L2 stage with one WAVE per candidate.  k_l2_window above gives a candidate to
+// one thread, whose every step -- a binary search of the sketch in HBM, a probe of its count table, the heap, the cells, all in per-candidate
+// HBM scratch -- waits for the one before it, 64 unrelated chains per wave.  Here the candidate's state is in LDS -- its query sketch, its
+// SlideMapper cells, its heap of open records (each carries its located form, so an eviction searches nothing) -- and the wave takes 64
+// consecutive events of the candidate's slice [e0, e1) per step:
+//   - coalesced loads of evKey / evAux / evHash (the next step's are in flight meanwhile);
+//   - per lane with an index record (an insert event: about half of a step's events, the others are evictions, which the heap replaces here): the binary search of the sketch in LDS, the wpos of the record behind it, the wpos
+//     of the slide record before it, and the probe of the presence table (mm_l2_window_core.h: "absent" or "present with record R" per
+//     hash; the candidate's slice of dWinKeys / dWinVals in HBM, 64 probes at a time);
+//   - then the records the table lets in go through mm_win_enter one by one, in index order, the whole wave running the one sequential
+//     step on LDS: the evictions due, the insert, the push, the evaluation.  A record that enters hands its wpos_end to the later lanes of
+//     the step that carry the same hash, which look at the rule again when their turn comes: same-hash records of one step are resolved
+//     in record order;
+//   - the entries of the records that entered go to the table, one lane each (compare-and-swap on the key: two hashes may want one slot).
+// windowLen == 0 fragments of a windowed batch take the same steps with the gate off.  Loci, l2First / l2Num and the cursor as k_l2_window
+// writes them.  A candidate this state cannot hold is appended to handList (its length in MM_PC_L2_WIDE_LEN, which the split sweeps use for
+// their list and a windowed batch does not) and swept by k_l2_window behind this kernel; each is checked before the write it guards:
+//   - a heap that would outgrow MM_WW_HEAP open records;
+//   - more tied loci at the best count than MM_LOCAP0 slots and the pending one (WinRuns::overflow);
+//   - a fragment sketch larger than the launch's LDS layout (cannot happen: Q.sketchSize <= sketchSize).
+// LDS per wave: MM_WW_HEAP x 8 B + 17 B per sketch entry -- 18.7 KB at s = 130: 8 waves per CU (two per SIMD), against the 2 560 per-lane
+// chains the literal kernel keeps per CU; the heap's share is what a read of 30 kbp at segLength 5000 needs (about 0.05 records per base
+// over windowLen + segLength stay open: 1 300 - 1 600).
+// ---------------------------------------------------------------------------------------------
+#define MM_WW_HEAP 2048            // open records the LDS heap holds
+#define MM_WW_MAX_SKETCH 2046      // sketchSize up to which the option applies (51 KB of LDS per wave there)
+__host__ __device__ static inline size_t mm_ww_lds(int s) {
+  return (size_t)MM_WW_HEAP * 8 + (size_t)(s + 1) * 8 + (size_t)(s + 2) * sizeof(WinCell) + (size_t)MM_LOCAP0 * sizeof(WinLocus) + (((size_t)s + 15) & ~(size_t)15);
+}
+__device__ __forceinline__ int mm_rl(int v, int l) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(l)); }
+__global__ void __launch_bounds__(64)
+k_l2_window_wave(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__ l1, const mm_frag_stats* __restrict__ stats, const DFrag* __restrict__ frags,
+                 const uint64_t* __restrict__ qHash, const int8_t* __restrict__ qStrand, const uint64_t* __restrict__ skHash, const int8_t* __restrict__ skStrand,
+                 const uint32_t* __restrict__ evKey, const uint32_t* __restrict__ evAux, const uint64_t* __restrict__ evHash, const int64_t* __restrict__ contigOff,
+                 const WinExt* __restrict__ ext, const int64_t* __restrict__ offT, const int32_t* __restrict__ cntT, uint64_t* __restrict__ tabKeys, int32_t* __restrict__ tabVals,
+                 const int64_t* __restrict__ l1Off, mm_l2_locus* __restrict__ l2, unsigned long long l2Cap, int64_t* __restrict__ l2First, int32_t* __restrict__ l2Num,
+                 unsigned long long* __restrict__ counters, int32_t* __restrict__ handList) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char wsm[];
+  uint64_t* heap = (uint64_t*)wsm;
+  uint64_t* q = heap + MM_WW_HEAP;                                 // the query sketch, ascending
+  WinCell* cells = (WinCell*)(q + (s + 1));                        // cells 0 .. S
+  WinLocus* slots = (WinLocus*)(cells + (s + 2));
+  int8_t* qs = (int8_t*)(slots + MM_LOCAP0);
+  const int lane = (int)threadIdx.x;
+  for (int c = blockIdx.x; c < nCand; c += gridDim.x) {
+    const mm_l1_candidate cand = l1[c];
+    const int f = cand.frag;
+    const mm_frag_stats fst = stats[f];
+    const int S = fst.sketchSize;
+    int W = frags[f].len - segLength; if (W < 0) W = 0;
+    const WinExt X = ext[c];
+    const int64_t ce = contigOff[cand.seqId + 1];
+    uint64_t* tk = tabKeys + offT[c]; int32_t* tv = tabVals + offT[c];
+    const uint32_t tmask = (uint32_t)cntT[c] - 1u;
+    bool hand = S > s;
+    __threadfence_block();                                         // the previous candidate's LDS reads are done
+    if (!hand) {
+      const bool raw = fst.rawSketchSize == fst.sketchSize;        // no seed was removed: the sketch is the raw one (k_lookup_l1)
+      const uint64_t* srcH = (raw ? skHash : qHash) + (size_t)f * s;
+      const int8_t* srcS = (raw ? skStrand : qStrand) + (size_t)f * s;
+      for (int p = lane; p < S; p += 64) { q[p] = srcH[p]; qs[p] = srcS[p]; }
+      for (int p = lane; p <= S; p += 64) cells[p] = WinCell{p ? 1 : 0, 0, 0};             // SlideMapper::init (slidingMap.hpp:103-121)
+      if (W > 0) for (uint32_t i = (uint32_t)lane; i <= tmask; i += 64u) tk[i] = ~0ull;    // no hash has an entry
+      __threadfence();                                             // ... before the first probe and the first compare-and-swap
+    }
+    WinSlide sm; sm.start(cells, S);
+    WinRuns rn; rn.start(segLength, W, slots, MM_LOCAP0);
+    int nHeap = 0, lastSlideW = MM_WIN_NONE;
+    auto load = [&](int64_t e, uint32_t& key, uint32_t& aux, uint64_t& h) { key = 0; aux = 0; h = 0; if (e < ce) { key = evKey[e]; aux = evAux[e]; h = evHash[e]; } };
+    uint32_t nKey, nAux; uint64_t nH;
+    load(X.e0 + lane, nKey, nAux, nH);
+    for (int64_t base = X.e0; base < X.e1 && !hand; base += 64) {
+      const uint32_t key = nKey, aux = nAux; const uint64_t h = nH;
+      load(base + 64 + lane, nKey, nAux, nH);                      // in flight during this step; to the contig's end, not e1: the record behind the last one
+      const bool isIns = (key & 1u) != 0;                          // minmerIndex records = insert events
+      const int pos = (int)(key >> 1), wend = (int)(aux & 0x7fffffffu);
+      const bool walked = base + lane < X.e1 && isIns;
+      const bool setup = pos < cand.rangeStartPos;                 // the set-up loop (:1323-1338) takes the records still open at rangeStart
+      const bool cons = walked && (!setup || wend > cand.rangeStartPos);
+      // wpos of the record behind this one in the same contig, else its own (:1387-1390)
+      const uint64_t above = mm_ballot(isIns) & ~((2ull << lane) - 1ull);
+      int nextW = __shfl(pos, above ? (int)__builtin_ctzll(above) : lane);
+      if (mm_ballot(cons && !above)) {                             // the last record of the step: the first one behind it
+        uint64_t m = mm_ballot((nKey & 1u) != 0);
+        int tailW = m ? mm_rl((int)(nKey >> 1), (int)__builtin_ctzll(m)) : 0;
+        for (int64_t e2 = base + 128; !m && e2 < ce; e2 += 64) {   // (rare: 64 evictions in a row)
+          const uint32_t k2 = e2 + lane < ce ? evKey[e2 + lane] : 0u;
+          m = mm_ballot((k2 & 1u) != 0);
+          if (m) tailW = mm_rl((int)(k2 >> 1), (int)__builtin_ctzll(m));
+        }
+        if (!above && m) nextW = tailW;
+      }
+      // wpos of the slide record before this one, entering or not: its evictions come before this record's votes are sampled
+      const uint64_t mSl = mm_ballot(walked && !setup);
+      int prevSlideW = lastSlideW;
+      {
+        const uint64_t below = mSl & ((1ull << lane) - 1ull);
+        const int p2 = __shfl(pos, below ? 63 - (int)__builtin_clzll(below) : lane);
+        if (below) prevSlideW = p2;
+      }
+      uint32_t loc = 0, slot = 0; bool exists = false; int entryEnd = 0;
+      if (cons) {
+        loc = mm_win_locate(q, qs, S, h, (aux >> 31) != 0);
+        if (W > 0) {                                               // the presence table: h -> wpos_end of the record that is in
+          slot = (uint32_t)(h * 0x9E3779B97F4A7C15ull >> 40) & tmask;
+          uint64_t k2;
+          while ((k2 = __hip_atomic_load(&tk[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != h && k2 != ~0ull) slot = (slot + 1u) & tmask;
+          if (k2 == h) { exists = true; entryEnd = __hip_atomic_load(&tv[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+        }
+      }
+      // records the table lets in, in index order; the others are final: an earlier record of this step cannot make a hash absent
+      uint64_t todo = mm_ballot(cons && !(W > 0 && mm_win_present(exists, entryEnd, setup, pos, W)));
+      bool writer = false;
+      while (todo) {
+        const int l = (int)__builtin_ctzll(todo); todo &= todo - 1ull;
+        const bool setupL = mm_rl(setup ? 1 : 0, l) != 0;
+        const int posL = mm_rl(pos, l), wendL = mm_rl(wend, l);
+        if (W > 0 && mm_win_present(mm_rl(exists ? 1 : 0, l) != 0, mm_rl(entryEnd, l), setupL, posL, W)) continue;   // a record of this step entered with its hash
+        if (!mm_win_enter(sm, heap, nHeap, MM_WW_HEAP, rn, setupL, posL, wendL, (uint32_t)mm_rl((int)loc, l), mm_rl(nextW, l), mm_rl(prevSlideW, l))) { hand = true; break; }
+        if (W > 0) {
+          const uint64_t hL = ((uint64_t)(uint32_t)mm_rl((int)(uint32_t)(h >> 32), l) << 32) | (uint32_t)mm_rl((int)(uint32_t)h, l);
+          if (cons && h == hL) { writer = lane == l; if (lane > l) { exists = true; entryEnd = wendL; } }
+        }
+      }
+      if (writer) {                                                // the last record of its hash that entered in this step
+        uint32_t i = slot;
+        while (true) {
+          const unsigned long long old = atomicCAS((unsigned long long*)&tk[i], ~0ull, (unsigned long long)h);
+          if (old == ~0ull || old == (unsigned long long)h) break;
+          i = (i + 1u) & tmask;
+        }
+        __hip_atomic_store(&tv[i], wend, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if (W > 0) __threadfence();                                  // the entries are there before the next step's probes
+      if (mSl) lastSlideW = mm_rl(pos, 63 - (int)__builtin_clzll(mSl));
+    }
+    if (!hand) { mm_win_finish(sm, heap, nHeap, rn, lastSlideW); hand = rn.overflow; }
+    if (hand) { if (lane == 0) handList[atomicAdd(&counters[MM_PC_L2_WIDE_LEN], 1ull)] = c; continue; }
+    const int total = rn.total();
+    unsigned long long at = 0;
+    if (total > 0) {
+      if (lane == 0) at = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
+      at = ((unsigned long long)(uint32_t)mm_rl((int)(uint32_t)(at >> 32), 0) << 32) | (uint32_t)mm_rl((int)(uint32_t)at, 0);
+      if (at + (unsigned long long)total > l2Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); continue; }
+    }
+    if (lane == 0) { l2First[c] = (int64_t)at; l2Num[c] = total; }
+    const int candLocal = (int)(c - l1Off[f]);
+    for (int k = lane; k < total; k += 64) {
+      const WinLocus t = rn.locus(k);
+      mm_l2_locus o;
+      o.frag = f; o.cand = candLocal; o.seqId = cand.seqId; o.optimalStart = t.start; o.optimalEnd = t.end;
+      o.meanOptimalPos = (t.start + t.end) / 2; o.sharedSketchSize = t.shared; o.strand = t.strand;
+      l2[at + k] = o;
+    }
+  }
+}
+
 // the end of a sized L2 stage: the counters as last read back (MM_PC_*) become the number of loci, or the reason there is none
 // (MM_L2F_STREAM is raised by k_l2_locate alone: the literal launcher never sees it)
 static int mm_l2_verdict(mm_ctx* c, const unsigned long long* hc) {
@@ -1051,12 +1213,38 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
   MM_HIP(c, c->dWinHeap.ensure((size_t)totH * 4 + 64)); MM_HIP(c, c->dWinKeys.ensure((size_t)totT * 8 + 64)); MM_HIP(c, c->dWinVals.ensure((size_t)totT * 4 + 64));
   MM_HIP(c, c->dL2Cells.ensure((size_t)nC * (size_t)(s + 1) * sizeof(ExactCell) + 64));
   if (c->l2Cap < c->nL1 * 2 + 1024) c->l2Cap = c->nL1 * 2 + 1024;
+  // MM_OPT_L2_WINDOW_WAVE: k_l2_window_wave takes every candidate first and leaves a list of those it cannot hold; k_l2_window then walks
+  // that list, whose length stays on the device (the launch covers every candidate), so the stage waits for the host as often as without
+  // the option.  A sketch beyond the wave kernel's LDS layout, or a batch without a long fragment (a sketch beyond MM_LDS_MAX_SKETCH comes
+  // here as well), is the literal kernel's alone.
+  const bool wave = c->l2WindowWave && c->windowed && s <= MM_WW_MAX_SKETCH && nC > 0;
+  if (wave) MM_HIP(c, c->dL2Wide.ensure((size_t)nC * 4 + 64));
   unsigned long long hc[MM_PC_READ];
   int locap = MM_LOCAP0;
+  bool waveDone = false;
   for (int attempt = 0; attempt < 24; attempt++) {
     MM_HIP(c, c->dL2.ensure(c->l2Cap * sizeof(mm_l2_locus) + 64));
     MM_HIP(c, c->dL2Tmp.ensure((size_t)nC * locap * sizeof(L2Tmp) + 64));
-    MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow, flags
+    if (!wave || !waveDone) MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow, flags
+    if (wave && !waveDone) {
+      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_WIDE_LEN, 0, 8, c->stream));                 // the hand-over list's length (the L1 stage is done with the word)
+      KernelTimer t(c, MM_K_L2);
+      const size_t lds = mm_ww_lds(s);
+      int blocks = nC; if (blocks > 256 * 32) blocks = 256 * 32;
+      hipLaunchKernelGGL(k_l2_window_wave, dim3((unsigned)blocks), dim3(64), lds, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
+                         c->dFrags.as<DFrag>(), c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
+                         I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.contigOff.as<int64_t>(), c->dWinExt.as<WinExt>(),
+                         c->dWinOffT.as<int64_t>(), c->dWinCntT.as<int32_t>(), c->dWinKeys.as<uint64_t>(), c->dWinVals.as<int32_t>(), c->dL1Off.as<int64_t>(),
+                         c->dL2.as<mm_l2_locus>(), (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt, c->dL2Wide.as<int32_t>());
+      MM_HIP(c, hipGetLastError());
+      // the cursor behind the wave kernel: where a repeated literal sweep (more locus slots) starts again (the word is the exact sweep's
+      // list length in split mode, unused here)
+      MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_EXACT_LEN, cnt + MM_PC_L2_LOCI, 8, hipMemcpyDeviceToDevice, c->stream));
+      waveDone = true;
+    } else if (wave) {
+      MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_LOCI, cnt + MM_PC_L2_EXACT_LEN, 8, hipMemcpyDeviceToDevice, c->stream));
+      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_OVERFLOW, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_OVERFLOW) * 8, c->stream));
+    }
     {
       KernelTimer t(c, MM_K_L2);
       hipLaunchKernelGGL(k_l2_window, dim3((nC + 63) / 64), dim3(64), 0, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
@@ -1064,15 +1252,21 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
                          I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.contigOff.as<int64_t>(), c->dWinExt.as<WinExt>(),
                          c->dWinOffH.as<int64_t>(), c->dWinOffT.as<int64_t>(), c->dWinCntT.as<int32_t>(), c->dWinHeap.as<int32_t>(), c->dWinKeys.as<uint64_t>(),
                          c->dWinVals.as<int32_t>(), c->dL2Cells.as<ExactCell>(), c->dL1Off.as<int64_t>(), c->dL2Tmp.as<L2Tmp>(), locap, c->dL2.as<mm_l2_locus>(),
-                         (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt);
+                         (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt,
+                         wave ? c->dL2Wide.as<int32_t>() : (const int32_t*)nullptr, wave ? cnt + MM_PC_L2_WIDE_LEN : (const unsigned long long*)nullptr);
       MM_HIP(c, hipGetLastError());
     }
     MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipStreamSynchronize(c->stream));
-    if (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) { if ((size_t)nC * (size_t)locap * 2 * sizeof(L2Tmp) > ((size_t)64 << 30)) break; locap *= 2; continue; }
-    if (hc[MM_PC_L2_OVERFLOW]) { const size_t need = mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus)); c->l2Cap = need + need / 8 + 1024; continue; }
+    // without the option the parent's order: slots first.  With it a moved locus buffer has both kernels run again, so that comes first
+    const bool slots = (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) != 0, over = hc[MM_PC_L2_OVERFLOW] != 0;
+    if (slots && !(wave && over)) { if ((size_t)nC * (size_t)locap * 2 * sizeof(L2Tmp) > ((size_t)64 << 30)) break; locap *= 2; continue; }   // (with the option: the literal kernel alone)
+    if (over) { const size_t need = mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus)); c->l2Cap = need + need / 8 + 1024; waveDone = false; continue; }
     break;
   }
+  c->winCands = c->windowed ? (size_t)nC : 0;
+  c->winLit = !c->windowed ? 0 : wave ? (size_t)hc[MM_PC_L2_WIDE_LEN] : (size_t)nC;
+  if (c->env.debug && c->windowed) fprintf(stderr, "[mm] L2: of %d windowed candidates the literal L2 kernel took %zu\n", nC, c->winLit);
   return mm_l2_verdict(c, hc);
 }
 
@@ -1102,6 +1296,7 @@ int mm_scan_i32_to_i64(mm_ctx* c, int64_t n, const int32_t* dIn, int64_t* dOut, 
 #define MM_EXACT_CAP 1024
 
 int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
+  if (!steady) { c->winCands = 0; c->winLit = 0; }                    // mm_pass_l2_window: as of the last sized pass
   if (c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH) return mm_launch_l2_window(c, cnt);   // fragments longer than segLength (--noSplit), or a sketch no LDS state holds: the literal kernel
   const DeviceIndex& I = c->idx;
   const int s = c->P.sketchSize;

@@ -1774,6 +1774,7 @@ static int map_pass(mm_ctx* c, const bool steady) {
     c->nL1 = (size_t)p.hc[MM_PC_L1_CAND];
     c->prevBig = c->lastBig = (size_t)p.nBig; c->prevLit = (size_t)p.nLit;
     c->prevMid = c->lastMid = (size_t)p.hMid; c->midKnown = p.useMid;
+    c->winCands = 0; c->winLit = 0;                        // (mm_launch_l2 counts the windowed candidates of a sized pass)
     if (c->nL1 == 0) { c->nL2 = 0; return MM_OK; }
   }
   return pass_finish(c, p);

@@ -138,6 +138,12 @@ class Sketch {
         std::cerr << "[mashmap_hip::skch::Sketch] ERROR: mm_set_option: " << mm_last_error(c) << std::endl;
         exit(1);
       }
+      // --noSplit: the L2 stage of a batch with a read longer than a segment on the wave-per-candidate kernel; the literal kernel takes
+      // the candidates that one hands over (profiles/NOTES.md: the probe that decided it)
+      if (!p.split && mm_set_option(c, MM_OPT_L2_WINDOW_WAVE, 1) != MM_OK) {
+        std::cerr << "[mashmap_hip::skch::Sketch] ERROR: mm_set_option: " << mm_last_error(c) << std::endl;
+        exit(1);
+      }
       ctxs_.push_back(c);
     }
     ctx_ = ctxs_[0];
