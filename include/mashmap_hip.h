@@ -39,7 +39,9 @@ enum {
   MM_FLAG_SKIP_PREFIX = 4,      /* skip_prefix            (parseCmdArgs.hpp:349): L1 runs once per run of interval points whose contigs share a
                                    reference group (computeMap.hpp:1146-1165).  Every fragment's points go through HBM (gather, sort), every
                                    pass is a sized pass, and the L1 stage is the literal one-thread-per-fragment kernel for every queued
-                                   fragment (mm_pass_l1_literal: literal == queued) unless MM_OPT_L1_GROUP_STREAM. */
+                                   fragment (mm_pass_l1_literal: literal == queued) unless MM_OPT_L1_GROUP_STREAM.  With
+                                   MM_OPT_L1_GROUP_FUSED the queued fragments first go to a wave-per-fragment kernel that keeps their points
+                                   out of HBM; the path above is then left with what that kernel hands over. */
   MM_FLAG_LOWER_TRIANGULAR = 8, /* lower_triangular       (parseCmdArgs.hpp:334) */
   MM_FLAG_NO_SPLIT = 16         /* !split                 (parseCmdArgs.hpp:427): a read longer than segLength is then ONE fragment with
                                    windowLen = len - segLength != 0 (computeMap.hpp:933, :1309); a batch that holds such a read goes through
@@ -309,7 +311,8 @@ int mm_pass_redo_cause(const mm_ctx* ctx, uint64_t* cause);
  * (k_l1_sweep) swept -- every one of them (a batch with a read longer than segLength excepted: 0, k_l1_window takes those) under MM_L1_LITERAL
  * or MM_FLAG_SKIP_PREFIX unless MM_OPT_L1_GROUP_STREAM, otherwise what the wave-per-fragment kernel (k_l1_stream) leaves: a position
  * group across two contigs (of one reference-group extent, in its grouped form) or minimumHits <= 0.  Read back with the words the sized pass reads behind the L1 sweeps anyway: no host wait
- * more.  Either pointer may be NULL.  Purely additive: MM_ABI_VERSION stays 2. */
+ * more.  Either pointer may be NULL.  Purely additive: MM_ABI_VERSION stays 2.  In a pass that ran k_lookup_groups (MM_OPT_L1_GROUP_FUSED)
+ * the HBM point path holds only what that kernel handed over: *queued equals offered - fused of mm_pass_l1_group_fused. */
 int mm_pass_l1_literal(const mm_ctx* ctx, uint64_t* queued, uint64_t* literal);
 /* Which L2 kernel took the candidates of a batch with a read longer than segLength (MM_FLAG_NO_SPLIT, windowLen != 0), as of the context's
  * last SIZED pass: *candidates = L1 candidates the windowed L2 stage took, *literal = those of them the literal one-thread-per-candidate
@@ -318,6 +321,13 @@ int mm_pass_l1_literal(const mm_ctx* ctx, uint64_t* queued, uint64_t* literal);
  * read.  Read back with the words the stage reads anyway: no host wait more.  Either pointer may be NULL.  Purely additive:
  * MM_ABI_VERSION stays 2. */
 int mm_pass_l2_window(const mm_ctx* ctx, uint64_t* candidates, uint64_t* literal);
+/* MM_OPT_L1_GROUP_FUSED, as of the context's last SIZED pass: *offered = fragments the lookup kernel queued under MM_FLAG_SKIP_PREFIX (every
+ * fragment with an interval point), *fused = those of them k_lookup_groups finished without the HBM point path; the rest it handed over
+ * to that path (mm_pass_l1_literal's *queued).  0 / 0 when the kernel was not launched: the option off, no MM_FLAG_SKIP_PREFIX, sketchSize
+ * above 512, a batch with a read longer than segLength, MM_OPT_KEEP_POINTS, or a refGroup array that is not non-decreasing.  Read back
+ * with the words the sized pass reads behind the lookup kernels anyway: no host wait more.  Either pointer may be NULL.  Purely
+ * additive: MM_ABI_VERSION stays 2. */
+int mm_pass_l1_group_fused(const mm_ctx* ctx, uint64_t* offered, uint64_t* fused);
 int mm_result_counts(const mm_ctx* ctx, size_t* nL1, size_t* nL2);
 /* any pointer may be NULL.  l1/l2 are sorted by (frag, emission order of the reference) */
 int mm_results_download(mm_ctx* ctx, mm_frag_stats* stats, mm_l1_candidate* l1, mm_l2_locus* l2);
@@ -348,14 +358,26 @@ int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
  * group across two contigs of one extent, minimumHits <= 0; mm_pass_l1_literal then reports that list's length.  Same candidates, same
  * order.  MM_L1_LITERAL still forces the literal kernel; batches with a read longer than segLength are untouched.  Without
  * MM_FLAG_SKIP_PREFIX the option does nothing.  Purely additive: MM_ABI_VERSION stays 2.
+ * MM_OPT_L1_GROUP_FUSED (default 0): with 1, under MM_FLAG_SKIP_PREFIX the fragments the lookup kernel queued go through k_lookup_groups
+ * first: one wave per fragment lists the interval points of its seeds in LDS, takes them one reference group at a time (the groups
+ * number runs of consecutive contigs, so a group's points are one extent of the sorted list: one computeL1CandidateRegions call of
+ * computeMap.hpp:1146-1165), sorts each group's points in registers and runs the fused L1 on them -- no gather, no sort through HBM.  It
+ * hands a fragment over to the HBM point path (MM_OPT_L1_GROUP_STREAM chooses that path's L1 kernel as before, MM_L1_LITERAL still
+ * forces the literal one) when it has more than 8 192 interval points, more than 64 groups, more than 1 024 kept points in one group or
+ * more than 128 candidates, a position group across two contigs inside one extent, more than 64 candidate runs in one extent, or
+ * minimumHits <= 0; mm_pass_l1_group_fused counts both.  Same candidates, same order.  The kernel is not launched for sketchSize above
+ * 512, a batch with a read longer than segLength, under MM_OPT_KEEP_POINTS, or when refGroup is not non-decreasing.  With the option
+ * set and without MM_OPT_KEEP_POINTS mm_points_download answers MM_ERR_STATE: the points of a fused fragment never reach HBM.  Without
+ * MM_FLAG_SKIP_PREFIX the option does nothing.  Purely additive: MM_ABI_VERSION stays 2.
  * MM_OPT_L2_WINDOW_WAVE (default 0): with 1, the L2 stage of a batch with a read longer than segLength (MM_FLAG_NO_SPLIT) runs on
  * k_l2_window_wave -- one wave per L1 candidate, its query sketch, SlideMapper cells and heap of open records in LDS, 64 events of the contig's
  * stream (inserts and evictions; the inserts are the index records) per step, their records located and gated in parallel -- and the literal k_l2_window sweeps the candidates that kernel hands over (mm_pass_l2_window).  Same loci,
  * same order.  Sketch sizes above 2046 and batches without such a read are untouched.  Purely additive: MM_ABI_VERSION stays 2.
  */
-enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5 };
+enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6 };
 int mm_set_option(mm_ctx* ctx, int option, int value);
-/* sorted interval points of fragment f after the seqId filters of computeMap.hpp:891-896 (needs MM_OPT_KEEP_POINTS; (seqId,pos,side) only, hash = 0) */
+/* sorted interval points of fragment f after the seqId filters of computeMap.hpp:891-896 (needs MM_OPT_KEEP_POINTS; (seqId,pos,side) only, hash = 0).
+ * Under MM_FLAG_SKIP_PREFIX the points are in HBM without that option too -- unless MM_OPT_L1_GROUP_FUSED is set: then MM_ERR_STATE. */
 int mm_points_download(mm_ctx* ctx, size_t frag, mm_interval_point* out, size_t cap, size_t* n);
 /* copies the L2 loci (fragment-major device order, not re-sorted) into caller-owned DEVICE memory, e.g. a torch tensor
  * that is then exchanged with RCCL; *n receives the count, cap is the capacity of dst in records */

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libmashmap_hip.so")
 
 MM_FLAG_HG_FILTER, MM_FLAG_SKIP_SELF, MM_FLAG_SKIP_PREFIX, MM_FLAG_LOWER_TRIANGULAR, MM_FLAG_NO_SPLIT = 1, 2, 4, 8, 16
 MM_OPT_KEEP_POINTS, MM_OPT_KEEP_FULL_INDEX, MM_OPT_RESERVE_FRAGMENTS, MM_OPT_L1_GROUP_STREAM, MM_OPT_L2_WINDOW_WAVE = 1, 2, 3, 4, 5
+MM_OPT_L1_GROUP_FUSED = 6
 # bits of Context.pass_redo_cause() (include/mashmap_hip.h: MM_REDO_*)
 (MM_REDO_POINTS, MM_REDO_L1, MM_REDO_L2_LOCI, MM_REDO_L2_SLOTS, MM_REDO_L2_STREAM, MM_REDO_L2_OPS, MM_REDO_L2_LIST, MM_REDO_L2_CANDS,
  MM_REDO_MAPPINGS, MM_REDO_NO_STREAM_BUFFER) = (1 << i for i in range(10))
@@ -134,6 +135,7 @@ def load():
         "mm_pass_totals": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_redo_cause": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "mm_pass_l1_literal": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_pass_l1_group_fused": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_l2_window": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_reads_exchange": (C.c_int, [vp, C.c_int]),
         "mm_reads_upload_packed_parts": (C.c_int, [vp, vp, sz, C.c_int32]),
@@ -166,7 +168,7 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_reads_upload_packed", "mm_reads_prefetch_packed", "mm_pack_read", "mm_pack_read_portable", "mm_reads_packed_download",
            "mm_index_layout_get", "mm_pass_stats", "mm_comm_info", "mm_pass_totals", "mm_reads_exchange", "mm_reads_upload_packed_parts",
            "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
-           "mm_pass_l1_literal", "mm_pass_l2_window"]
+           "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused"]
 
 
 def stat_sketch_cutoffs(sketchSize, k, hg=True):
@@ -430,6 +432,13 @@ class Context:
         self._ck(self.lib.mm_pass_l1_literal(self.h, C.byref(q), C.byref(l)), "mm_pass_l1_literal")
         return int(q.value), int(l.value)
 
+    def pass_l1_group_fused(self):
+        """(offered, fused) of the last sized pass: fragments the lookup kernel queued under MM_FLAG_SKIP_PREFIX, and those of them
+        k_lookup_groups finished without the HBM point path (MM_OPT_L1_GROUP_FUSED); (0, 0) when that kernel was not launched"""
+        o, f = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.mm_pass_l1_group_fused(self.h, C.byref(o), C.byref(f)), "mm_pass_l1_group_fused")
+        return int(o.value), int(f.value)
+
     def pass_l2_window(self):
         """(candidates, literal) of the last sized pass: L1 candidates the windowed L2 stage took (a batch with a read longer than segLength
         under MM_FLAG_NO_SPLIT; 0 otherwise), and those of them the literal k_l2_window swept"""
@@ -478,6 +487,11 @@ class Context:
         """MM_OPT_L1_GROUP_STREAM: under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped wave-per-fragment L1 kernel; the
         literal kernel takes what it leaves (pass_l1_literal() then reports that list's length)"""
         self._ck(self.lib.mm_set_option(self.h, MM_OPT_L1_GROUP_STREAM, 1 if on else 0), "mm_set_option")
+
+    def l1_group_fused(self, on=True):
+        """MM_OPT_L1_GROUP_FUSED: under MM_FLAG_SKIP_PREFIX the queued fragments go through the wave-per-fragment k_lookup_groups first (a
+        group's points sorted in registers, no HBM point path); that path takes what it hands over (pass_l1_group_fused() counts both)"""
+        self._ck(self.lib.mm_set_option(self.h, MM_OPT_L1_GROUP_FUSED, 1 if on else 0), "mm_set_option")
 
     def l2_window_wave(self, on=True):
         """MM_OPT_L2_WINDOW_WAVE: the L2 stage of a batch with a read longer than segLength goes to the wave-per-candidate kernel; the

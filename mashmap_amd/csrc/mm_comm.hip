@@ -354,6 +354,7 @@ int mm_index_replicate(mm_ctx* dst, mm_ctx* src) {
   D.nRec = S.nRec; D.nKeys = S.nKeys; D.nPoints = S.nPoints; D.nContigs = S.nContigs; D.htCap = S.htCap; D.nOpen = S.nOpen; D.filterMask = S.filterMask; D.tagged = S.tagged;
   D.ready = true;
   dst->freqThreshold = src->freqThreshold;
+  dst->refGroupMonotone = src->refGroupMonotone;
   dst->mapped = false;
   return MM_OK;
 }

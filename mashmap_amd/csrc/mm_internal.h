@@ -98,7 +98,7 @@ enum : int {
   MM_CW_INDEX_BUILD   = 16,   // 16..19 index build only (mm_finalize_index_device): MM_IX_BUILD_*
   MM_CW_INDEX_FLATTEN = 20,   // 20..23 index build only (mm_flatten_device_index): MM_IX_FLAT_*
   MM_CW_INDEX_END     = 24,
-  MM_CW_MID_LEN       = 24,   // 24     mapping pass: fragments on k_lookup_mid's list (MM_PC_MID_LEN from MM_CW_PASS) ...
+  MM_CW_MID_LEN       = 24,   // 24     mapping pass: fragments on k_lookup_mid's list (MM_PC_MID_LEN from MM_CW_PASS), or on k_lookup_groups' hand-over list (MM_PC_GRP_LEN) ...
   MM_CW_SKETCH_PHASES = 24,   // 24..31 ... and, under MM_SKETCH_STATS, the sketch kernel's phase cycles (read and printed by the sketch launcher
   MM_CW_SKETCH_PHASES_END = 32, //      before the pass resets them); word 24 is also the sink of k_hash_only, which never stores to it
   MM_CW_MAP           = 32,   // 32..39 mapping pass: what a steady-state pass reports besides MM_CW_PASS (MM_MC_*); `result` of k_l2_select
@@ -124,7 +124,9 @@ enum : int {
   MM_PC_BIG_LEN        = 7,   // L1 stage: fragments queued for the HBM point path (dBigList)
   MM_PC_L2_WIDE_LEN    = 7,   // L2 sweep: candidates on the list of the 16-bit-cell sweep (dL2Wide)
   MM_PC_READ           = MM_CW_PASS_END - MM_CW_PASS,
-  MM_PC_MID_LEN        = MM_CW_MID_LEN - MM_CW_PASS
+  MM_PC_MID_LEN        = MM_CW_MID_LEN - MM_CW_PASS,
+  MM_PC_GRP_LEN        = MM_PC_MID_LEN // L1 stage under MM_OPT_L1_GROUP_FUSED: fragments k_lookup_groups handed over (dGrpList).  k_lookup_mid never runs in such a
+                              // pass (-Y: useMid is off), and a sized pass reads the word back behind the lookup kernels either way (mm_pass_l1_group_fused)
 };
 constexpr unsigned long long MM_OVERFLOWED = 1ull;   // what the kernels raise an overflow word to
 // bits of MM_PC_L2_FLAGS; any of them set in a steady-state pass has it redone the sized way
@@ -183,6 +185,7 @@ static_assert(MM_CW_SKETCH_PHASES >= MM_CW_INDEX_END && MM_CW_SKETCH_PHASES_END 
 static_assert(MM_PC_POINT_CURSOR == MM_PC_L2_EXACT_LEN && MM_PC_BIG_LEN == MM_PC_L2_WIDE_LEN, "the words shared by the L1 stage and the L2 sweep");
 static_assert(MM_CW_PASS + MM_PC_MID_LEN == MM_CW_SKETCH_PHASES, "k_lookup_mid's list length shares its word with the sketch statistics");
 static_assert(MM_PC_L2_LOCI + 1 == MM_PC_L2_OVERFLOW && MM_PC_L2_OVERFLOW + 1 == MM_PC_L2_FLAGS && MM_PC_L2_FLAGS < MM_PC_READ, "the L2 words are reset as one range");
+static_assert(MM_PC_GRP_LEN == MM_PC_MID_LEN && MM_PC_GRP_LEN != MM_PC_BIG_LEN, "k_lookup_groups counts its hand-overs in the mid list's word, beside the queue it reads");
 static_assert(MM_PC_L1_CAND + 1 == MM_PC_L1_OVERFLOW, "the L1 cursor and its flag are read back as one range");
 
 // The device library's environment switches ("Environment switches"), read once per context by mm_create: a switch
@@ -267,7 +270,7 @@ struct mm_ctx {
   // runs the exchange while the caller maps the next batch
   DevBuf dGatherSrc; hipStream_t commStream = nullptr; std::thread gatherThread; int gatherRc = 0; std::string gatherErr;
   std::vector<DevBuf*> allBufs();
-  DevBuf dL2Info, dL2Cnt, dL2Off, dL2Ops, dScanTmp, dL2Tmp, dL2Wide, dL2Exact, dL2Cells, dListB, dListC, dBigList, dMidList;     // L2 staging: per-candidate stream extents, op counts/offsets, located ops
+  DevBuf dL2Info, dL2Cnt, dL2Off, dL2Ops, dScanTmp, dL2Tmp, dL2Wide, dL2Exact, dL2Cells, dListB, dListC, dBigList, dMidList, dGrpList;     // L2 staging: per-candidate stream extents, op counts/offsets, located ops
   DevBuf dL2InitCells, dL2InitState;                                 // per candidate of a chunk: the SlideMapper state after the pre-load, as k_l2_locate leaves it for the sweeps
   DevBuf dL2Sort[4], dL2Order, dL2OrderPos;                          // candidates of a chunk in order of descending stream length (mm_order_desc)
   bool sketched = false, mapped = false;
@@ -284,6 +287,9 @@ struct mm_ctx {
   bool keepFiltered = false;                            // MM_OPT_KEEP_POINTS = 2: ... and k_filter_points runs on them as it does on a queued fragment's (mm_points_download returns what it leaves)
   bool keepPoints = false;                              // mm_set_option(MM_OPT_KEEP_POINTS): route every fragment through the HBM point list
   bool l1GroupStream = false;                           // mm_set_option(MM_OPT_L1_GROUP_STREAM): under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped k_l1_stream first
+  bool l1GroupFused = false;                            // mm_set_option(MM_OPT_L1_GROUP_FUSED): under MM_FLAG_SKIP_PREFIX the queued fragments go through k_lookup_groups first; the HBM point path takes what it hands over
+  bool refGroupMonotone = true;                         // the index's refGroup array is non-decreasing (checked where it arrives: mm_flatten_device_index; mm_index_replicate carries it)
+  size_t grpOffered = 0, grpFused = 0;                  // last sized pass: fragments offered to k_lookup_groups and those it finished (mm_pass_l1_group_fused); 0 / 0 when it was not launched
   bool l2WindowWave = false;                            // mm_set_option(MM_OPT_L2_WINDOW_WAVE): the windowed L2 stage on k_l2_window_wave first, the literal k_l2_window takes what it hands over
   size_t winCands = 0, winLit = 0;                      // candidates the windowed L2 stage took in the last sized pass, and those k_l2_window swept (mm_pass_l2_window)
   size_t reserveFrags = 0;                              // mm_set_option(MM_OPT_RESERVE_FRAGMENTS): fragments of the largest batch the caller will upload; sized passes size for it

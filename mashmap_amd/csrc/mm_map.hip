@@ -5,6 +5,8 @@
 //                           wave per fragment, up to 128 / 256 / 512 points sorted in registers   computeMap.hpp:818-843, 857-912, 916-1116
 //   k_lookup_mid            the same for the fragments with more points than that (up to MM_MID_MAXPTS): wave per fragment, the
 //                           points that can reach minimumHits picked by position bins in LDS
+//   k_lookup_groups         under -Y reference groups (MM_OPT_L1_GROUP_FUSED): wave per queued fragment, the points of one group at a time
+//                           sorted in registers and swept by the fused L1 -- no HBM point path for the fragments it finishes
 //   k_l1_regions / k_l1_compact / k_l1_fix_offsets / k_l1_gate
 //                           the fused kernels' candidates, written into 64 regions, made one dense array; the steady-state gate
 //   the HBM point path, for what the fused kernels hand over (more points still, -Y groups, position groups spanning contigs), for
@@ -901,6 +903,190 @@ k_lookup_mid(int nList, const unsigned long long* __restrict__ nDev, const int32
   }
 }
 
+// k_lookup_groups (MM_OPT_L1_GROUP_FUSED): the fragments k_lookup_l1 queued under -Y reference groups (MM_FLAG_SKIP_PREFIX) -- every
+// fragment with a point -- WITHOUT the trip through HBM (k_gather_points -> block-wide sort -> k_l1_stream_groups).  Map::doL1Mapping calls
+// computeL1CandidateRegions once per run of sorted points whose contigs share a reference group (computeMap.hpp:1146-1165), and the groups
+// number runs of consecutive contigs (Map::setRefGroups, :144-161; the host has checked that the array is non-decreasing), so one call's
+// points are exactly "the fragment's points of one group": a few hundred, which the register sorters and mm_l1_fused take.  One wave per
+// queued fragment: the seeds are probed once more and their point runs listed in LDS (as k_lookup_mid does); one sweep over the interval
+// pairs applies the seqId filters of :891-896, notes every kept pair's group in a table of distinct groups with counts and leaves a
+// one-byte group slot per pair; the groups are then taken in ascending order (= the order of their extents in the sorted list), each
+// one's pairs copied to the sort list by their tags, sorted in registers and swept by mm_l1_fused with the fragment's minimumHits -- the
+// HG step then works on this extent's own best count, and a position shared by the last point of one group and the first of the next
+// lies in two calls, as in the reference.  The candidates of all extents collect in LDS, are claimed once from the fragment's region
+// cursor and written in extent order, exactly as k_lookup_mid leaves a fragment.
+// Handed over (list `handList`, which stands in for dBigList for the rest of the pass; the point slots are those k_lookup_l1 reserved):
+// more than MM_GRP_MAXPTS points, MM_GRP_MAXGROUPS groups, MM_GRP_MAXKEEP kept points in one group or MM_GRP_MAXCAND candidates;
+// mm_l1_fused's -1 for any extent (a position group across two contigs inside it, more than MM_FUSE_MAXRUNS runs); minimumHits <= 0.
+// LDS per wave: 13 312 (FuseScratch) + 4 096 + 2 052 (seed runs) + 4 096 (tags) + 512 (groups) + 2 048 (candidates), 26 128 bytes with
+// alignment: six waves per CU of 160 KB.  The compiler reports (gfx950, -O3) 148 VGPRs (150 with the tagged seed table), 26 128 bytes of
+// LDS and no scratch; the 16-per-lane tier is in line for that (a call to mm_mid_sort16 brings 12 bytes of register saves).
+#define MM_GRP_MAXSEEDS MM_MID_MAXSKETCH   // seeds with points: every sketch the kernel is launched for fits
+#define MM_GRP_MAXPTS 8192                 // interval points of the fragment's runs, before the filters (4 096 tag bytes)
+#define MM_GRP_MAXGROUPS 64                // distinct groups among the kept points (one per lane when they are ordered)
+#define MM_GRP_MAXKEEP MM_MID_MAXKEEP      // kept points of one group (the 16-per-lane sorter)
+#define MM_GRP_MAXCAND 128                 // candidates of the fragment (2 KB of LDS)
+#define MM_GRP_NOTAG 0xFFu                 // tag of a pair the filters dropped
+template <bool TAGS>
+__global__ void __launch_bounds__(64)
+k_lookup_groups(const unsigned long long* __restrict__ nDev, const int32_t* __restrict__ list, int s, const DFrag* __restrict__ frags,
+                const uint64_t* __restrict__ skHash, const uint32_t* __restrict__ skCount, const SeedTable T, const uint64_t* __restrict__ ptKeys,
+                const int32_t* __restrict__ refGroup, const int32_t* __restrict__ readGroup, const int32_t* __restrict__ readSelf, int seqCounterBase,
+                MapFlags fl, mm_frag_stats* __restrict__ stats, int64_t* __restrict__ ptOff, const int32_t* __restrict__ minHitsTab,
+                const int32_t* __restrict__ cutoffs, int nCutoffs, int segLength, mm_l1_candidate* __restrict__ l1, unsigned long long regionCap,
+                unsigned long long* __restrict__ l1Cursors, int64_t* __restrict__ l1Off, int32_t* __restrict__ handList,
+                unsigned long long* __restrict__ counters) {
+  typedef FuseScratchT<MM_GRP_MAXKEEP> FuseScratch;
+  __shared__ FuseScratch sc;
+  __shared__ uint64_t src[MM_GRP_MAXSEEDS];                        // first point of every surviving seed's run
+  __shared__ uint32_t pre[MM_GRP_MAXSEEDS + 1];                    // intervals (point pairs) of the seeds before it
+  __shared__ uint8_t tag[MM_GRP_MAXPTS / 2];                       // per interval: slot of its group in gKey, MM_GRP_NOTAG when dropped
+  __shared__ int32_t gKey[MM_GRP_MAXGROUPS], gCnt[MM_GRP_MAXGROUPS];   // distinct groups of the kept intervals (-1: free) and their intervals
+  __shared__ L1Run out[MM_GRP_MAXCAND];                            // the fragment's candidates, extent by extent
+  const int lane = (int)mm_lane();
+  const int nList = (int)*nDev;
+  for (int li = blockIdx.x; li < nList; li += gridDim.x) {
+    const int f = list[li];
+    const int cnt = (int)skCount[f];
+    const size_t fo = (size_t)f * s;
+    const int readId = frags[f].readId;
+    const int rg = readGroup[readId], self = readSelf[readId], seqCounter = seqCounterBase + readId;
+    const mm_frag_stats st0 = stats[f];
+    const int outIdx = st0.sketchSize;
+    const int minHits = outIdx > 0 ? minHitsTab[outIdx] : 0;
+    bool hand = minHits <= 0;                                      // wave-uniform: the fragment goes to the HBM point path
+    gKey[lane] = -1; gCnt[lane] = 0;
+    // the seeds once more; those with points are listed densely: run start + intervals before it
+    int nSeeds = 0, nPairs = 0, P = 0; bool giveUp = false;
+    for (int base = 0; base < cnt; base += 256) {
+      uint64_t h[4], val[4]; bool act[4], found[4];
+      mm_probe4<TAGS>(T, skHash, fo, cnt, base, lane, h, act, found, val);
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const bool kf = act[u] && found[u] && !(val[u] & 1ull);
+        const int c = kf ? (int)((val[u] >> 1) & 0x7fffffull) : 0;
+        if (c & 1) giveUp = true;                                  // (never: a hash's points are its intervals' two ends)
+        const uint64_t m = mm_ballot(c > 0);
+        const int at = nSeeds + (int)mm_popc_below(m);
+        const int before = nPairs + mm_wave_excl_scan(c >> 1);
+        if (c > 0 && at < MM_GRP_MAXSEEDS) { src[at] = val[u] >> 24; pre[at] = (uint32_t)before; }
+        nSeeds += (int)__popcll(m); nPairs += mm_wave_sum(c >> 1); P += mm_wave_sum(c);
+      }
+    }
+    if (nSeeds > MM_GRP_MAXSEEDS) { hand = true; nSeeds = MM_GRP_MAXSEEDS; }
+    if (P > MM_GRP_MAXPTS || mm_ballot(giveUp) != 0ull) hand = true;
+    if (lane == 0) pre[nSeeds] = (uint32_t)nPairs;
+    __threadfence_block();
+    // interval g of the fragment = pair (g - pre[j]) of seed j's run, j by binary search
+    auto pairAt = [&](int g, uint64_t& O, uint64_t& C) {
+      int lo = 0, hi = nSeeds - 1;
+      while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if ((int)pre[mid] <= g) lo = mid; else hi = mid - 1; }
+      const ulonglong2 oc = *(const ulonglong2*)(ptKeys + src[lo] + 2 * (uint64_t)(g - (int)pre[lo]));
+      O = oc.x; C = oc.y;
+    };
+    // the one sweep over the intervals: filters, the group table, the tags
+    int nValid = 0;
+    giveUp = false;
+    for (int g0 = 0; g0 < nPairs && !hand; g0 += 64) {
+      const int g = g0 + lane;
+      if (g < nPairs) {
+        uint64_t O, C; pairAt(g, O, C);
+        const int seqId = (int)(O >> 33);
+        const int grp = refGroup[seqId];
+        uint32_t t = MM_GRP_NOTAG;
+        const bool drop = (fl.skipSelf && seqId == self) || (fl.skipPrefix && grp == rg) || (fl.lowerTri && !(seqCounter > seqId));
+        if ((int)(C >> 33) != seqId || grp < 0) giveUp = true;
+        else if (!drop) {
+          uint32_t sl = ((uint32_t)grp * 0x9E3779B1u) >> 26;       // 6 bits
+          int tries = 0;
+          for (; tries < MM_GRP_MAXGROUPS; tries++) {
+            const int32_t prev = atomicCAS(&gKey[sl], -1, grp);
+            if (prev == -1 || prev == grp) { atomicAdd(&gCnt[sl], 1); t = sl; nValid += 2; break; }
+            sl = (sl + 1u) & (MM_GRP_MAXGROUPS - 1);
+          }
+          if (tries == MM_GRP_MAXGROUPS) giveUp = true;            // a 65th group
+        }
+        tag[g] = (uint8_t)t;                                       // g < nPairs <= MM_GRP_MAXPTS / 2: checked above (P)
+      }
+    }
+    __threadfence_block();
+    if (mm_ballot(giveUp) != 0ull) hand = true;
+    nValid = mm_wave_sum(nValid);
+    // the groups in ascending order: (group, slot) sorted across the lanes
+    int total = 0;                                                 // candidates in out[] so far (wave-uniform)
+    if (!hand) {
+      const int32_t myKey = gKey[lane];
+      uint64_t ord[1] = {myKey >= 0 ? (((uint64_t)(uint32_t)myKey << 8) | (uint64_t)lane) : MM_EMPTY};
+      mm_wave_bitonic<1>(ord, lane);
+      const int nG = (int)__popcll(mm_ballot(ord[0] != MM_EMPTY));
+      for (int gi = 0; gi < nG && !hand; gi++) {
+        const int slot = __shfl((int)(uint32_t)ord[0], gi) & 0xff;
+        const int K = 2 * gCnt[slot];
+        if (K > MM_GRP_MAXKEEP) { hand = true; break; }
+        int cursor = 0;                                            // pairs of this group copied so far (wave-uniform)
+        for (int g0 = 0; g0 < nPairs; g0 += 64) {
+          const int g = g0 + lane;
+          const bool mine = g < nPairs && (int)tag[g] == slot;
+          const uint64_t m = mm_ballot(mine);
+          if (!m) continue;
+          const int at = cursor + (int)mm_popc_below(m);
+          if (mine && at < MM_GRP_MAXKEEP / 2) { uint64_t O, C; pairAt(g, O, C); sc.a[2 * at] = O; sc.a[2 * at + 1] = C; }
+          cursor += (int)__popcll(m);
+        }
+        const int padTo = K <= 64 ? 64 : K <= 128 ? 128 : K <= 256 ? 256 : K <= 512 ? 512 : 1024;
+        for (int j = K + lane; j < padTo; j += 64) sc.a[j] = MM_EMPTY;
+        __threadfence_block();
+        int nOut;
+        if (K > 512) {                                             // mm_mid_sort16's form, in line: a call would bring the callee's register saves (scratch) with it
+          uint64_t k[16];
+#pragma unroll
+          for (int e = 0; e < 16; e++) k[e] = sc.a[lane * 16 + e];
+          mm_wave_bitonic<16>(k, lane); nOut = mm_l1_fused<16>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
+        }
+        else if (K <= 64) { uint64_t k[1] = {sc.a[lane]}; mm_wave_bitonic<1>(k, lane); nOut = mm_l1_fused<1>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane); }
+        else if (K <= 128) { uint64_t k[2] = {sc.a[lane * 2], sc.a[lane * 2 + 1]}; mm_wave_bitonic<2>(k, lane); nOut = mm_l1_fused<2>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane); }
+        else if (K <= 256) {
+          uint64_t k[4] = {sc.a[lane * 4], sc.a[lane * 4 + 1], sc.a[lane * 4 + 2], sc.a[lane * 4 + 3]};
+          mm_wave_bitonic<4>(k, lane); nOut = mm_l1_fused<4>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
+        } else {
+          uint64_t k[8];
+#pragma unroll
+          for (int e = 0; e < 8; e++) k[e] = sc.a[lane * 8 + e];
+          mm_wave_bitonic<8>(k, lane); nOut = mm_l1_fused<8>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
+        }
+        if (nOut < 0 || total + nOut > MM_GRP_MAXCAND) { hand = true; break; }
+        for (int i = lane; i < nOut; i += 64) out[total + i] = sc.run[i];
+        total += nOut;
+        __threadfence_block();
+      }
+    }
+    if (hand) {                                                    // the HBM point path takes it, in the slots k_lookup_l1 reserved
+      if (lane == 0) handList[atomicAdd(&counters[MM_PC_GRP_LEN], 1ull)] = f;
+    } else {
+      int nOut = total;
+      const int region = f & (MM_L1_REGIONS - 1);
+      unsigned long long at = 0;
+      if (nOut > 0) {
+        if (lane == 0) at = atomicAdd(&l1Cursors[(size_t)region * MM_L1_CURSOR_STRIDE], (unsigned long long)nOut);
+        at = ((unsigned long long)(uint32_t)__shfl((int)(at >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)at, 0);
+        if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
+      }
+      const unsigned long long base = (unsigned long long)region * regionCap + at;
+      for (int i = lane; i < nOut; i += 64) {
+        const L1Run x = out[i];
+        mm_l1_candidate o; o.frag = f; o.seqId = x.seq; o.rangeStartPos = x.start; o.rangeEndPos = x.end; o.intersectionSize = x.isize;
+        l1[base + i] = o;
+      }
+      if (lane == 0) {
+        mm_frag_stats st = st0;
+        st.nPoints = nValid; st.nL1 = nOut; stats[f] = st;
+        ptOff[2 * f] = 0; ptOff[2 * f + 1] = 0; l1Off[f] = (int64_t)base;
+      }
+    }
+    __threadfence_block();
+  }
+}
+
 // closes the gaps between the 64 regions of the L1 buffer: region r moves to its prefix position (into a second buffer), and
 // the fragments' first-candidate offsets follow
 struct L1Regions { unsigned long long prefix[MM_L1_REGIONS]; unsigned long long count[MM_L1_REGIONS]; };
@@ -1491,6 +1677,9 @@ k_l1_window(int nList, const int32_t* __restrict__ list, const DFrag* __restrict
 // What the stages of a pass hand on (map_pass calls them in order; each one is a sequence of operations on c->stream).
 struct MapPass {
   bool steady, windowed, allSlow, useMid;
+  bool useGroups = false;                  // k_lookup_groups runs behind k_lookup_l1 (MM_OPT_L1_GROUP_FUSED under -Y): bigList is what it handed over
+  const int32_t* bigList = nullptr;        // the fragments of the HBM point path: dBigList, or dGrpList behind k_lookup_groups
+  unsigned long long nOffered = 0;         // sized pass with useGroups: fragments k_lookup_l1 queued (all of them offered to k_lookup_groups)
   int nF, s;
   MapFlags fl;
   SeedTable seedTab;
@@ -1523,6 +1712,12 @@ static int pass_prepare(mm_ctx* c, MapPass& p) {
   // fragments with more interval points than k_lookup_l1 sorts go through k_lookup_mid first
   p.useMid = !p.allSlow && p.s <= MM_MID_MAXSKETCH;
   if (p.useMid) MM_HIP(c, c->dMidList.ensure(cF * 4 + 16));
+  // -Y reference groups with MM_OPT_L1_GROUP_FUSED: the queued fragments go through k_lookup_groups first.  Not for a windowed batch, not
+  // when the points are to stay in HBM, not for a sketch its seed list does not hold, and only where an extent of the sorted points is
+  // a whole group (refGroup non-decreasing).  Such a pass is never a steady-state one (mm_launch_map: allSlow)
+  p.useGroups = c->l1GroupFused && p.fl.skipPrefix && !p.steady && !p.windowed && !c->keepPoints && p.s <= MM_GRP_MAXSEEDS && c->refGroupMonotone;
+  if (p.useGroups) MM_HIP(c, c->dGrpList.ensure(cF * 4 + 16));
+  p.bigList = p.useGroups ? c->dGrpList.as<int32_t>() : c->dBigList.as<int32_t>();
   MM_HIP(c, c->dL1Regions.ensure(sizeof(L1Regions)));
   p.cnt = c->dCounters.as<unsigned long long>() + MM_CW_PASS;
   p.lens = (unsigned int*)(c->dCounters.as<unsigned long long>() + MM_CW_SORT_LENS);
@@ -1580,6 +1775,19 @@ static int pass_lookup(mm_ctx* c, MapPass& p) {
                          c->dL1.as<mm_l1_candidate>(), p.regionCap, c->dL1Cursors.as<unsigned long long>(), c->dL1Off.as<int64_t>(), c->dBigList.as<int32_t>(), cnt);
       MM_HIP(c, hipGetLastError());
     }
+    if (p.useGroups) {
+      // a wave per fragment k_lookup_l1 queued (their number stays on the device: MM_PC_BIG_LEN); what it hands over is counted in
+      // MM_PC_GRP_LEN, the word k_lookup_mid's list would use and the read-back below fetches anyway (hMid)
+      KernelTimer t(c, MM_K_SORT);
+      const unsigned grid = (unsigned)std::max(1, std::min(nF, 1 << 16));
+      auto gk = I.tagged ? k_lookup_groups<true> : k_lookup_groups<false>;
+      hipLaunchKernelGGL(gk, dim3(grid), dim3(64), 0, c->stream, cnt + MM_PC_BIG_LEN, c->dBigList.as<int32_t>(), s, c->dFrags.as<DFrag>(), c->dSkHash.as<uint64_t>(),
+                         c->dSkCount.as<uint32_t>(), p.seedTab, I.ptKeys.as<uint64_t>(), I.refGroup.as<int32_t>(), c->dReadGroup.as<int32_t>(), c->dReadSelf.as<int32_t>(),
+                         c->seqCounterBase, p.fl, c->dStats.as<mm_frag_stats>(), c->dPtOff.as<int64_t>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
+                         (int)c->nCutoffs, c->P.segLength, c->dL1.as<mm_l1_candidate>(), p.regionCap, c->dL1Cursors.as<unsigned long long>(), c->dL1Off.as<int64_t>(),
+                         c->dGrpList.as<int32_t>(), cnt);
+      MM_HIP(c, hipGetLastError());
+    }
     if (p.steady) return MM_OK;                               // the overflow flags are looked at when the pass is over
     MM_HIP(c, hipMemcpyAsync(p.hc, cnt, sizeof p.hc, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipMemcpyAsync(&p.hMid, cnt + MM_PC_MID_LEN, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1618,6 +1826,10 @@ static int pass_compact(mm_ctx* c, MapPass& p) {
   std::swap(c->dL1, c->dL1b);                               // dL1 is the dense buffer from here on
   p.denseCap = c->dL1.bytes / sizeof(mm_l1_candidate) - 4;  // room behind the fused candidates for the sweep path's
   p.nBig = (int)p.hc[MM_PC_BIG_LEN];
+  if (p.useGroups) {                                        // the point path is left with what k_lookup_groups handed over (MM_PC_GRP_LEN, read back as hMid)
+    p.nOffered = p.hc[MM_PC_BIG_LEN]; p.nBig = (int)p.hMid; p.hMid = 0;
+    if (c->env.debug) fprintf(stderr, "[mm] reference groups: %llu fragments offered to k_lookup_groups, %llu fused, %d handed over\n", p.nOffered, p.nOffered - (unsigned long long)p.nBig, p.nBig);
+  }
   if (c->env.debug) {
     if (p.steady) fprintf(stderr, "[mm] lookup+L1: %d fragments, steady-state pass (the counts stay on the device)\n", p.nF);
     else fprintf(stderr, "[mm] lookup+L1: %d fragments, %llu through k_lookup_mid, %d to the sort+sweep path, %llu fused candidates\n", p.nF, p.hMid, p.nBig, p.hc[MM_PC_L1_CAND]);
@@ -1636,19 +1848,19 @@ static int pass_point_path(mm_ctx* c, MapPass& p) {
   KernelTimer t(c, MM_K_SORT);
   uint16_t* sortIds = p.windowed ? c->dPtIds.as<uint16_t>() : (uint16_t*)nullptr;
   auto gk = I.tagged ? k_gather_points<true> : k_gather_points<false>;
-  hipLaunchKernelGGL(gk, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), s, c->dFrags.as<DFrag>(), c->dSkHash.as<uint64_t>(),
+  hipLaunchKernelGGL(gk, dim3(p.gWave), dim3(256), 0, c->stream, nBig, p.bigList, s, c->dFrags.as<DFrag>(), c->dSkHash.as<uint64_t>(),
                      c->dSkCount.as<uint32_t>(), p.seedTab, I.ptKeys.as<uint64_t>(), I.refGroup.as<int32_t>(),
                      c->dReadGroup.as<int32_t>(), c->dReadSelf.as<int32_t>(), c->seqCounterBase, p.fl, c->dStats.as<mm_frag_stats>(), c->dPtOff.as<int64_t>(),
                      c->dPts.as<uint64_t>(), sortIds, c->dPtKept.as<int32_t>(), p.nBigDev);
   MM_HIP(c, hipGetLastError());
   // split mode, plain L1: the points that cannot reach minimumHits go before the sort (k_filter_points)
   if (!p.windowed && (!c->keepPoints || c->keepFiltered) && !p.fl.skipPrefix) {
-    hipLaunchKernelGGL(k_filter_points, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(),
+    hipLaunchKernelGGL(k_filter_points, dim3(p.gWave), dim3(256), 0, c->stream, nBig, p.bigList, c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(),
                        c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), c->dPtKept.as<int32_t>(), p.nBigDev);
     MM_HIP(c, hipGetLastError());
   }
-  if (!p.windowed) hipLaunchKernelGGL(k_sort_points_wave, dim3(p.gWave), dim3(256), 0, c->stream, nBig, p.nBigDev, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>());
-  hipLaunchKernelGGL(k_classify_sort, dim3(p.gThread), dim3(256), 0, c->stream, nBig, p.nBigDev, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
+  if (!p.windowed) hipLaunchKernelGGL(k_sort_points_wave, dim3(p.gWave), dim3(256), 0, c->stream, nBig, p.nBigDev, p.bigList, c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>());
+  hipLaunchKernelGGL(k_classify_sort, dim3(p.gThread), dim3(256), 0, c->stream, nBig, p.nBigDev, p.bigList, c->dPtOff.as<int64_t>(),
                      c->dListB.as<int32_t>(), c->dListC.as<int32_t>(), p.lens, p.windowed ? 1 : MM_SORT_WAVECAP);
   MM_HIP(c, hipGetLastError());
   unsigned int hLens[MM_SL_LITERAL] = {1024u, 16u};         // the two sorter lists (the words before MM_SL_LITERAL).  steady: fixed grids over the two lists (their lengths stay on the device)
@@ -1681,11 +1893,11 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
     }
     {
       KernelTimer t(c, MM_K_L1);
-      const int32_t* sweepList = c->dBigList.as<int32_t>(); const unsigned int* sweepCount = nullptr;
+      const int32_t* sweepList = p.bigList; const unsigned int* sweepCount = nullptr;
       if (p.windowed) {
         const int nFreq = s > 256 ? s : 256;                                     // seeds are numbered by their index in the raw sketch
         MM_HIP(c, c->dWinFreq.ensure((size_t)nBig * nFreq * 4 + 64));
-        hipLaunchKernelGGL(k_l1_window, dim3((nBig + 63) / 64), dim3(64), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dFrags.as<DFrag>(), c->dPtOff.as<int64_t>(),
+        hipLaunchKernelGGL(k_l1_window, dim3((nBig + 63) / 64), dim3(64), 0, c->stream, nBig, p.bigList, c->dFrags.as<DFrag>(), c->dPtOff.as<int64_t>(),
                            c->dPts.as<uint64_t>(), c->dPtIds.as<uint16_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
                            (int)c->nCutoffs, s, c->P.segLength, p.fl, I.refGroup.as<int32_t>(), c->dWinFreq.as<int32_t>(), nFreq, c->dL1.as<mm_l1_candidate>(),
                            (unsigned long long)p.denseCap, c->dL1Off.as<int64_t>(), cnt);
@@ -1694,11 +1906,11 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
         unsigned int* lit = p.lens + MM_SL_LITERAL;
         if (stream) {
           MM_HIP(c, hipMemsetAsync(lit, 0, (size_t)(MM_SL_END - MM_SL_LITERAL) * 4, c->stream));
-          if (p.fl.skipPrefix) hipLaunchKernelGGL(k_l1_stream_groups, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
+          if (p.fl.skipPrefix) hipLaunchKernelGGL(k_l1_stream_groups, dim3(p.gWave), dim3(256), 0, c->stream, nBig, p.bigList, c->dPtOff.as<int64_t>(),
                              c->dPts.as<uint64_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
                              (int)c->nCutoffs, s, c->P.segLength, p.fl.hg, c->dL1.as<mm_l1_candidate>(), (unsigned long long)p.denseCap,
                              c->dL1Off.as<int64_t>(), c->dListB.as<int32_t>(), lit, cnt, p.nBigDev, c->dPtKept.as<int32_t>(), I.refGroup.as<int32_t>());
-          else hipLaunchKernelGGL(k_l1_stream, dim3(p.gWave), dim3(256), 0, c->stream, nBig, c->dBigList.as<int32_t>(), c->dPtOff.as<int64_t>(),
+          else hipLaunchKernelGGL(k_l1_stream, dim3(p.gWave), dim3(256), 0, c->stream, nBig, p.bigList, c->dPtOff.as<int64_t>(),
                              c->dPts.as<uint64_t>(), c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(),
                              (int)c->nCutoffs, s, c->P.segLength, p.fl.hg, c->dL1.as<mm_l1_candidate>(), (unsigned long long)p.denseCap,
                              c->dL1Off.as<int64_t>(), c->dListB.as<int32_t>(), lit, cnt, p.nBigDev, c->dPtKept.as<int32_t>());
@@ -1774,6 +1986,7 @@ static int map_pass(mm_ctx* c, const bool steady) {
     c->nL1 = (size_t)p.hc[MM_PC_L1_CAND];
     c->prevBig = c->lastBig = (size_t)p.nBig; c->prevLit = (size_t)p.nLit;
     c->prevMid = c->lastMid = (size_t)p.hMid; c->midKnown = p.useMid;
+    c->grpOffered = (size_t)p.nOffered; c->grpFused = p.useGroups ? (size_t)p.nOffered - (size_t)p.nBig : 0;
     c->winCands = 0; c->winLit = 0;                        // (mm_launch_l2 counts the windowed candidates of a sized pass)
     if (c->nL1 == 0) { c->nL2 = 0; return MM_OK; }
   }
@@ -1870,6 +2083,7 @@ int mm_query_sketch_download(mm_ctx* c, mm_minmer* out) {
 int mm_points_download(mm_ctx* c, size_t frag, mm_interval_point* out, size_t cap, size_t* n) {
   if (!c->mapped || frag >= c->nFrags) { c->err = "mm_points_download: bad state / fragment"; return MM_ERR_STATE; }
   if (!c->keepPoints && !(c->P.flags & MM_FLAG_SKIP_PREFIX)) { c->err = "mm_points_download: interval points are not kept in HBM (mm_set_option MM_OPT_KEEP_POINTS)"; return MM_ERR_STATE; }
+  if (!c->keepPoints && c->l1GroupFused) { c->err = "mm_points_download: with MM_OPT_L1_GROUP_FUSED the interval points of a fused fragment never reach HBM (mm_set_option MM_OPT_KEEP_POINTS keeps them)"; return MM_ERR_STATE; }
   MM_HIP(c, hipSetDevice(c->device));
   int64_t po[2]; mm_frag_stats fs;
   MM_HIP(c, hipMemcpy(po, c->dPtOff.as<int64_t>() + 2 * frag, 16, hipMemcpyDeviceToHost));
