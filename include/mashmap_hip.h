@@ -55,7 +55,8 @@ typedef struct {
   int32_t segLength;      /* Parameters::segLength  */
   int32_t sketchSize;     /* Parameters::sketchSize (1 .. 65535.  Up to 8190 the sketch and L2 kernels keep their state in a CU's 160 KB of LDS -- mm_create
                              checks the combination with segLength and says what does not fit --; beyond, every fragment takes a global-memory sketch
-                             kernel and the literal L2 kernels, and the index build keeps a window's sketch in HBM from 4097 on: exact, not tuned) */
+                             kernel and the literal L2 kernels, and the index build keeps a window's sketch in HBM from 4097 on: exact, not tuned;
+                             MM_OPT_L2_LARGE_WAVE puts the L2 stage of such a batch on a wave per candidate first, up to 20460) */
   int32_t flags;          /* MM_FLAG_* */
 } mm_params;
 
@@ -321,6 +322,13 @@ int mm_pass_l1_literal(const mm_ctx* ctx, uint64_t* queued, uint64_t* literal);
  * read.  Read back with the words the stage reads anyway: no host wait more.  Either pointer may be NULL.  Purely additive:
  * MM_ABI_VERSION stays 2. */
 int mm_pass_l2_window(const mm_ctx* ctx, uint64_t* candidates, uint64_t* literal);
+/* Which L2 kernel took the candidates of a SPLIT batch (no read longer than segLength) that went the literal L2 route -- sketchSize above
+ * 8190, or bit 1 of MM_OPT_L2_LARGE_WAVE --, as of the context's last SIZED pass: *candidates = L1 candidates the route took, *literal =
+ * those of them the literal one-thread-per-candidate kernel (k_l2_window) swept -- every one without bit 0 of the option or with sketchSize
+ * above 20460, otherwise the ones k_l2_large_wave handed over: more than 9 tied loci at the best shared count.  0 / 0 for a batch with a read
+ * longer than segLength or one that took the fast kernels.  Read back with the words the stage reads anyway: no host wait more.  Either
+ * pointer may be NULL.  Purely additive: MM_ABI_VERSION stays 2. */
+int mm_pass_l2_large(const mm_ctx* ctx, uint64_t* candidates, uint64_t* literal);
 /* MM_OPT_L1_GROUP_FUSED, as of the context's last SIZED pass: *offered = fragments the lookup kernel queued under MM_FLAG_SKIP_PREFIX (every
  * fragment with an interval point), *fused = those of them k_lookup_groups finished without the HBM point path; the rest it handed over
  * to that path (mm_pass_l1_literal's *queued).  0 / 0 when the kernel was not launched: the option off, no MM_FLAG_SKIP_PREFIX, sketchSize
@@ -373,8 +381,15 @@ int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
  * k_l2_window_wave -- one wave per L1 candidate, its query sketch, SlideMapper cells and heap of open records in LDS, 64 events of the contig's
  * stream (inserts and evictions; the inserts are the index records) per step, their records located and gated in parallel -- and the literal k_l2_window sweeps the candidates that kernel hands over (mm_pass_l2_window).  Same loci,
  * same order.  Sketch sizes above 2046 and batches without such a read are untouched.  Purely additive: MM_ABI_VERSION stays 2.
+ * MM_OPT_L2_LARGE_WAVE (default 0), two bits.  Bit 0 (value 1, what a caller sets): a split batch on the literal L2 route -- sketchSize
+ * above 8190 -- goes to k_l2_large_wave first when sketchSize <= 20460: one wave per L1 candidate, its SlideMapper cells (32-bit counts,
+ * boolean `active`, accumulated vote) in LDS, 64 events of the candidate's slice of the index stream per step located in the query sketch in
+ * parallel and then applied in event order; the literal k_l2_window sweeps the candidates that kernel hands over (mm_pass_l2_large).  Same
+ * loci, same order.  Bit 1 (value 2; 3 with bit 0): split batches take the literal L2 route at ANY sketch size, so that both kernels can be
+ * checked at small sketches; such a context runs sized passes only.  Batches with a read longer than segLength are untouched at every
+ * value.  Purely additive: MM_ABI_VERSION stays 2.
  */
-enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6 };
+enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6, MM_OPT_L2_LARGE_WAVE = 7 };
 int mm_set_option(mm_ctx* ctx, int option, int value);
 /* sorted interval points of fragment f after the seqId filters of computeMap.hpp:891-896 (needs MM_OPT_KEEP_POINTS; (seqId,pos,side) only, hash = 0).
  * Under MM_FLAG_SKIP_PREFIX the points are in HBM without that option too -- unless MM_OPT_L1_GROUP_FUSED is set: then MM_ERR_STATE. */

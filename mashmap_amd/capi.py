@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libmashmap_hip.so")
 MM_FLAG_HG_FILTER, MM_FLAG_SKIP_SELF, MM_FLAG_SKIP_PREFIX, MM_FLAG_LOWER_TRIANGULAR, MM_FLAG_NO_SPLIT = 1, 2, 4, 8, 16
 MM_OPT_KEEP_POINTS, MM_OPT_KEEP_FULL_INDEX, MM_OPT_RESERVE_FRAGMENTS, MM_OPT_L1_GROUP_STREAM, MM_OPT_L2_WINDOW_WAVE = 1, 2, 3, 4, 5
 MM_OPT_L1_GROUP_FUSED = 6
+MM_OPT_L2_LARGE_WAVE = 7
 # bits of Context.pass_redo_cause() (include/mashmap_hip.h: MM_REDO_*)
 (MM_REDO_POINTS, MM_REDO_L1, MM_REDO_L2_LOCI, MM_REDO_L2_SLOTS, MM_REDO_L2_STREAM, MM_REDO_L2_OPS, MM_REDO_L2_LIST, MM_REDO_L2_CANDS,
  MM_REDO_MAPPINGS, MM_REDO_NO_STREAM_BUFFER) = (1 << i for i in range(10))
@@ -137,6 +138,7 @@ def load():
         "mm_pass_l1_literal": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_l1_group_fused": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_l2_window": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_pass_l2_large": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_reads_exchange": (C.c_int, [vp, C.c_int]),
         "mm_reads_upload_packed_parts": (C.c_int, [vp, vp, sz, C.c_int32]),
         "mm_reads_prefetch_packed_append": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_int)]),
@@ -168,7 +170,7 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_reads_upload_packed", "mm_reads_prefetch_packed", "mm_pack_read", "mm_pack_read_portable", "mm_reads_packed_download",
            "mm_index_layout_get", "mm_pass_stats", "mm_comm_info", "mm_pass_totals", "mm_reads_exchange", "mm_reads_upload_packed_parts",
            "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
-           "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused"]
+           "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large"]
 
 
 def stat_sketch_cutoffs(sketchSize, k, hg=True):
@@ -487,6 +489,19 @@ class Context:
         """MM_OPT_L1_GROUP_STREAM: under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped wave-per-fragment L1 kernel; the
         literal kernel takes what it leaves (pass_l1_literal() then reports that list's length)"""
         self._ck(self.lib.mm_set_option(self.h, MM_OPT_L1_GROUP_STREAM, 1 if on else 0), "mm_set_option")
+
+    def l2_large_wave(self, value=1):
+        """MM_OPT_L2_LARGE_WAVE.  1: a split batch on the literal L2 route (sketchSize above 8190) goes to the wave-per-candidate
+        k_l2_large_wave first, the literal k_l2_window takes what it hands over (pass_l2_large() then reports that list's length); 2: split
+        batches take the literal route at any sketch size; 3: both; 0: off"""
+        self._ck(self.lib.mm_set_option(self.h, MM_OPT_L2_LARGE_WAVE, int(value)), "mm_set_option")
+
+    def pass_l2_large(self):
+        """(candidates, literal) of the last sized pass: L1 candidates of a split batch that took the literal L2 route (0 for a batch with a
+        read longer than segLength or one on the fast kernels), and those of them the literal k_l2_window swept"""
+        n, l = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.mm_pass_l2_large(self.h, C.byref(n), C.byref(l)), "mm_pass_l2_large")
+        return int(n.value), int(l.value)
 
     def l1_group_fused(self, on=True):
         """MM_OPT_L1_GROUP_FUSED: under MM_FLAG_SKIP_PREFIX the queued fragments go through the wave-per-fragment k_lookup_groups first (a

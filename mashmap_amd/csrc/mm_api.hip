@@ -107,6 +107,7 @@ int mm_set_option(mm_ctx* c, int option, int value) {
   if (option == MM_OPT_L1_GROUP_STREAM) { c->l1GroupStream = value != 0; return MM_OK; }
   if (option == MM_OPT_L1_GROUP_FUSED) { c->l1GroupFused = value != 0; return MM_OK; }
   if (option == MM_OPT_L2_WINDOW_WAVE) { c->l2WindowWave = value != 0; return MM_OK; }
+  if (option == MM_OPT_L2_LARGE_WAVE) { c->l2LargeWave = value & 3; return MM_OK; }
   c->err = "mm_set_option: unknown option"; return MM_ERR_ARG;
 }
 
@@ -604,6 +605,11 @@ int mm_pass_l1_group_fused(const mm_ctx* c, uint64_t* offered, uint64_t* fused) 
   return MM_OK;
 }
 
+int mm_pass_l2_large(const mm_ctx* c, uint64_t* candidates, uint64_t* literal) {
+  if (candidates) *candidates = c->lwCands;
+  if (literal) *literal = c->lwLit;
+  return MM_OK;
+}
 int mm_pass_l2_window(const mm_ctx* c, uint64_t* candidates, uint64_t* literal) {
   if (candidates) *candidates = c->winCands;
   if (literal) *literal = c->winLit;

@@ -123,6 +123,7 @@ enum : int {
   MM_PC_L2_FLAGS       = 6,   // MM_L2F_* bits
   MM_PC_BIG_LEN        = 7,   // L1 stage: fragments queued for the HBM point path (dBigList)
   MM_PC_L2_WIDE_LEN    = 7,   // L2 sweep: candidates on the list of the 16-bit-cell sweep (dL2Wide)
+  MM_PC_L2_LARGE_LEN   = 7,   // literal L2 route, split batch under MM_OPT_L2_LARGE_WAVE: candidates k_l2_large_wave handed over to k_l2_window (dL2Wide; no 16-bit sweep runs there)
   MM_PC_READ           = MM_CW_PASS_END - MM_CW_PASS,
   MM_PC_MID_LEN        = MM_CW_MID_LEN - MM_CW_PASS,
   MM_PC_GRP_LEN        = MM_PC_MID_LEN // L1 stage under MM_OPT_L1_GROUP_FUSED: fragments k_lookup_groups handed over (dGrpList).  k_lookup_mid never runs in such a
@@ -184,6 +185,7 @@ static_assert(MM_CW_INDEX_BUILD + 4 == MM_CW_INDEX_FLATTEN && MM_CW_INDEX_FLATTE
 static_assert(MM_CW_SKETCH_PHASES >= MM_CW_INDEX_END && MM_CW_SKETCH_PHASES_END <= MM_CW_MAP, "the sketch statistics must stay clear of the words that outlive the sketch launcher");
 static_assert(MM_PC_POINT_CURSOR == MM_PC_L2_EXACT_LEN && MM_PC_BIG_LEN == MM_PC_L2_WIDE_LEN, "the words shared by the L1 stage and the L2 sweep");
 static_assert(MM_CW_PASS + MM_PC_MID_LEN == MM_CW_SKETCH_PHASES, "k_lookup_mid's list length shares its word with the sketch statistics");
+static_assert(MM_PC_L2_LARGE_LEN == MM_PC_L2_WIDE_LEN, "k_l2_large_wave and k_l2_window_wave count their hand-overs in one word: a batch is split or windowed");
 static_assert(MM_PC_L2_LOCI + 1 == MM_PC_L2_OVERFLOW && MM_PC_L2_OVERFLOW + 1 == MM_PC_L2_FLAGS && MM_PC_L2_FLAGS < MM_PC_READ, "the L2 words are reset as one range");
 static_assert(MM_PC_GRP_LEN == MM_PC_MID_LEN && MM_PC_GRP_LEN != MM_PC_BIG_LEN, "k_lookup_groups counts its hand-overs in the mid list's word, beside the queue it reads");
 static_assert(MM_PC_L1_CAND + 1 == MM_PC_L1_OVERFLOW, "the L1 cursor and its flag are read back as one range");
@@ -291,6 +293,8 @@ struct mm_ctx {
   bool refGroupMonotone = true;                         // the index's refGroup array is non-decreasing (checked where it arrives: mm_flatten_device_index; mm_index_replicate carries it)
   size_t grpOffered = 0, grpFused = 0;                  // last sized pass: fragments offered to k_lookup_groups and those it finished (mm_pass_l1_group_fused); 0 / 0 when it was not launched
   bool l2WindowWave = false;                            // mm_set_option(MM_OPT_L2_WINDOW_WAVE): the windowed L2 stage on k_l2_window_wave first, the literal k_l2_window takes what it hands over
+  int l2LargeWave = 0;                                  // mm_set_option(MM_OPT_L2_LARGE_WAVE): bit 0: split batches on the literal L2 route go to k_l2_large_wave first; bit 1: split batches take that route at any sketch size
+  size_t lwCands = 0, lwLit = 0;                        // candidates of a split batch the literal L2 route took in the last sized pass, and those k_l2_window swept (mm_pass_l2_large)
   size_t winCands = 0, winLit = 0;                      // candidates the windowed L2 stage took in the last sized pass, and those k_l2_window swept (mm_pass_l2_window)
   size_t reserveFrags = 0;                              // mm_set_option(MM_OPT_RESERVE_FRAGMENTS): fragments of the largest batch the caller will upload; sized passes size for it
 

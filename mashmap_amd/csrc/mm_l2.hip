@@ -1182,6 +1182,153 @@ k_l2_window_wave(int nCand, int s, int segLength, const mm_l1_candidate* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_l2_large_wave (MM_OPT_L2_LARGE_WAVE): the L2 stage of a SPLIT batch (windowLen == 0 for every fragment) on the literal route -- a
+// sketch beyond MM_LDS_MAX_SKETCH, which neither k_l2_locate's LDS tables nor the located stream's 13-bit position field hold -- with one
+// WAVE per candidate.  The candidate's slice of the index is k_l2_extents' (L2Info): the block's open records, the events before rangeStart,
+// the slide.  The wave takes 64 consecutive events of one of the three ranges per step, as k_l2_locate's chunk loop does (the next chunk's
+// three loads in flight):
+//   - per lane: k_l2_locate's keep rule, and the hash located in the fragment's query sketch with mm_win_locate.  The sketch is read
+//     where it lies in HBM -- 160 KB of hashes at s = 20 000 would leave no LDS for the cells --: 64 searches at a time against one array
+//     that stays cache-resident, instead of one chain per candidate;
+//   - then, in event order, the whole wave applies the located events to WinSlide (mm_l2_window_core.h: 32-bit counts, boolean `active`,
+//     accumulated vote, the literal insert_minmer / delete_minmer) in LDS.  Evictions come from the stream -- at windowLen == 0 its order is
+//     the heap's order, which k_l2_sweep and k_l2_sweep_exact rely on as well -- and a lane whose hash lies beyond the sketch is skipped by
+//     the ballot mask, unless it is an insert: its position is still evaluated.
+// The pre-load is applied the same way, serially (its inserts commute, so LDS atomics and a wave scan would do; not done here).  The
+// evaluation is k_l2_sweep_exact's, stated by WinRuns with W = 0: an insert is evaluated when the next insert's wpos is known, the strand of
+// a closing run comes from the votes as they stood after the previous insert, the last insert uses k_l2_locate's nextW.  Every loop is
+// bounded by the slice's length (the two tail scans by the contig's); no wave waits for another.  Loci, l2First / l2Num and the cursor as
+// k_l2_window_wave writes them.  Handed over to k_l2_window through handList (length in MM_PC_L2_LARGE_LEN), each checked before the write
+// it guards: more tied loci at the best count than MM_LOCAP0 slots and the pending one (WinRuns::overflow); a fragment sketch larger than
+// the launch's LDS layout (cannot happen: Q.sketchSize <= sketchSize).
+// LDS per wave: (s + 2) cells of 8 B and MM_LOCAP0 loci -- 160 112 B of a CU's 163 840 at s = 19 998: one wave per CU there.
+// ---------------------------------------------------------------------------------------------
+#define MM_LW_MAX_SKETCH 20460     // the largest sketchSize whose cells and locus slots fit a CU's 160 KB of LDS
+__host__ __device__ static inline size_t mm_lw_lds(int s) { return (size_t)(s + 2) * sizeof(WinCell) + (size_t)MM_LOCAP0 * sizeof(WinLocus); }
+static_assert((size_t)(MM_LW_MAX_SKETCH + 2) * sizeof(WinCell) + (size_t)MM_LOCAP0 * sizeof(WinLocus) <= 160 * 1024, "k_l2_large_wave's state in one CU's LDS");
+__global__ void __launch_bounds__(64)
+k_l2_large_wave(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__ l1, const L2Info* __restrict__ info,
+                const uint64_t* __restrict__ qHash, const int8_t* __restrict__ qStrand, const uint64_t* __restrict__ skHash, const int8_t* __restrict__ skStrand,
+                const uint32_t* __restrict__ evKey, const uint32_t* __restrict__ evAux, const uint64_t* __restrict__ evHash,
+                const uint32_t* __restrict__ opKey, const uint32_t* __restrict__ opAux, const uint64_t* __restrict__ opHash, const int64_t* __restrict__ contigOff,
+                const int64_t* __restrict__ l1Off, mm_l2_locus* __restrict__ l2, unsigned long long l2Cap, int64_t* __restrict__ l2First, int32_t* __restrict__ l2Num,
+                unsigned long long* __restrict__ counters, int32_t* __restrict__ handList) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lwsm[];
+  WinCell* cells = (WinCell*)lwsm;                                 // cells 0 .. S (+ one unused)
+  WinLocus* slots = (WinLocus*)(cells + (s + 2));
+  const int lane = (int)threadIdx.x;
+  for (int c = blockIdx.x; c < nCand; c += gridDim.x) {
+    const mm_l1_candidate cand = l1[c];
+    const int f = cand.frag;
+    const L2Info in = info[c];
+    const int S = in.sketch & 0x7fffffff;
+    const int nOpen = in.nOpen, nPre = in.nPre, nAll = in.nAll;
+    const int64_t ce = contigOff[cand.seqId + 1];
+    bool hand = S > s;
+    __threadfence_block();                                         // the previous candidate's LDS reads are done
+    if (!hand) for (int p = lane; p <= S; p += 64) cells[p] = WinCell{p ? 1 : 0, 0, 0};      // SlideMapper::init (slidingMap.hpp:103-121)
+    __threadfence_block();
+    // a fragment that lost no frequent seed has no copy in qHash/qStrand: its sketch is the raw one (k_lookup_l1)
+    const bool raw = in.sketch < 0;
+    const uint64_t* q = (raw ? skHash : qHash) + (size_t)f * s;
+    const int8_t* qs = (raw ? skStrand : qStrand) + (size_t)f * s;
+    const uint64_t qmax = S > 0 && !hand ? q[S - 1] : 0ull;
+    // the slide ends with the last insert at or before rangeEnd; nextW: the wpos of the record behind it in the same contig, else its own
+    // (k_l2_locate's rule, a slice that ends in 64 evictions included)
+    int lastRel = -1, nextW = 0;
+    if (!hand) {
+      const int iT = nAll - 64 + lane;
+      const uint32_t tailKey = (iT >= nPre && iT < nAll) ? evKey[in.e0 + iT] : 0u;
+      const uint32_t behindKey = in.e0 + nAll + lane < ce ? evKey[in.e0 + nAll + lane] : 0u;
+      const uint64_t m = mm_ballot((tailKey & 1u) != 0);
+      if (m) { const int l = 63 - (int)__builtin_clzll(m); lastRel = nAll - 64 + l; nextW = (int)((uint32_t)mm_rl((int)tailKey, l) >> 1); }
+      for (int hiEnd = nAll - 64; hiEnd > nPre && lastRel < 0; hiEnd -= 64) {
+        const int i = hiEnd - 64 + lane;
+        const uint32_t k2 = (i >= nPre && i < hiEnd) ? evKey[in.e0 + i] : 0u;
+        const uint64_t m2 = mm_ballot((k2 & 1u) != 0);
+        if (m2) { const int l = 63 - (int)__builtin_clzll(m2); lastRel = hiEnd - 64 + l; nextW = (int)((uint32_t)mm_rl((int)k2, l) >> 1); }
+      }
+      if (lastRel >= 0) {
+        const uint64_t m0 = mm_ballot((behindKey & 1u) != 0);
+        if (m0) nextW = (int)((uint32_t)mm_rl((int)behindKey, (int)__builtin_ctzll(m0)) >> 1);
+        else for (int64_t e = in.e0 + nAll + 64; e < ce; e += 64) {
+          const uint32_t k2 = e + lane < ce ? evKey[e + lane] : 0u;
+          const uint64_t m2 = mm_ballot((k2 & 1u) != 0);
+          if (m2) { nextW = (int)((uint32_t)mm_rl((int)k2, (int)__builtin_ctzll(m2)) >> 1); break; }
+        }
+      }
+    }
+    const int nEv = lastRel + 1;                                   // events [0, nEv) of the slice are walked
+    const int nChO = (nOpen + 63) >> 6, nChPre = nChO + ((nPre + 63) >> 6);
+    const int nCh = hand ? 0 : nChPre + ((nEv > nPre ? nEv - nPre : 0) + 63) / 64;
+    auto loadChunk = [&](int ch, uint32_t& key, uint32_t& aux, uint64_t& h) {
+      key = 0; aux = 0; h = 0;                                       // a lane without a record: no insert flag, nothing kept
+      if (ch < nChO) { const int i = ch * 64 + lane; if (i < nOpen) { key = opKey[in.open0 + i]; aux = opAux[in.open0 + i]; h = opHash[in.open0 + i]; } }
+      else {
+        const int i = ch < nChPre ? (ch - nChO) * 64 + lane : nPre + (ch - nChPre) * 64 + lane;
+        if (i < (ch < nChPre ? nPre : nEv)) { key = evKey[in.e0 + i]; aux = evAux[in.e0 + i]; h = evHash[in.e0 + i]; }
+      }
+    };
+    WinSlide sm; sm.start(cells, S);
+    WinRuns rn; rn.start(segLength, 0, slots, MM_LOCAP0);
+    bool evalPending = false; int evW = 0, evShared = 0, evPrevVotes = 0, lastVotes = 0;
+    uint32_t nKey = 0, nAux = 0; uint64_t nHash = 0;
+    if (nCh > 0) loadChunk(0, nKey, nAux, nHash);
+    for (int ch = 0; ch < nCh; ch++) {
+      const uint32_t key = nKey, aux = nAux; const uint64_t h = nHash;
+      if (ch + 1 < nCh) loadChunk(ch + 1, nKey, nAux, nHash);       // in flight while this chunk is located and applied
+      const bool isIns = (key & 1u) != 0;
+      const int pos = (int)(key >> 1);
+      const bool slide = ch >= nChPre;                               // wave-uniform
+      bool keep, evalIns = false;
+      if (!slide) keep = isIns && (int)(aux & 0x7fffffffu) > cand.rangeStartPos && pos >= in.target;   // still open at rangeStart (:1323-1338)
+      else {
+        const bool live = nPre + (ch - nChPre) * 64 + lane < nEv;
+        keep = live && (isIns || h <= qmax);                         // an eviction outside the sketch's range changes nothing
+        evalIns = live && isIns;
+      }
+      const uint32_t loc = keep ? mm_win_locate(q, qs, S, h, (aux >> 31) != 0) : 0u;
+      uint64_t todo = mm_ballot(evalIns || (keep && mm_win_loc_j(loc) != 0));
+      while (todo) {
+        const int l = (int)__builtin_ctzll(todo); todo &= todo - 1ull;
+        const uint32_t locL = (uint32_t)mm_rl((int)loc, l);
+        if (!slide) sm.insert(locL);
+        else if (mm_rl(isIns ? 1 : 0, l) != 0) {
+          const int posL = mm_rl(pos, l);
+          if (evalPending) rn.evaluate(evShared, evW, posL, evPrevVotes);       // the insert before this one: its nextW is this wpos
+          evPrevVotes = lastVotes;
+          sm.insert(locL);
+          lastVotes = sm.votes; evW = posL; evShared = sm.shared; evalPending = true;
+        } else sm.remove(locL);
+      }
+      if (!slide) lastVotes = sm.votes;                              // (votes right after the last pre-load insert)
+    }
+    if (!hand) {
+      if (evalPending) rn.evaluate(evShared, evW, nextW, evPrevVotes);
+      if (rn.inRun) rn.close_run(sm.votes >= 0 ? 1 : -1);
+      hand = rn.overflow;
+    }
+    if (hand) { if (lane == 0) handList[atomicAdd(&counters[MM_PC_L2_LARGE_LEN], 1ull)] = c; continue; }
+    const int total = rn.total();
+    unsigned long long at = 0;
+    if (total > 0) {
+      if (lane == 0) at = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
+      at = ((unsigned long long)(uint32_t)mm_rl((int)(uint32_t)(at >> 32), 0) << 32) | (uint32_t)mm_rl((int)(uint32_t)at, 0);
+      if (at + (unsigned long long)total > l2Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); continue; }
+    }
+    if (lane == 0) { l2First[c] = (int64_t)at; l2Num[c] = total; }
+    const int candLocal = (int)(c - l1Off[f]);
+    for (int k = lane; k < total; k += 64) {
+      const WinLocus t = rn.locus(k);
+      mm_l2_locus o;
+      o.frag = f; o.cand = candLocal; o.seqId = cand.seqId; o.optimalStart = t.start; o.optimalEnd = t.end;
+      o.meanOptimalPos = (t.start + t.end) / 2; o.sharedSketchSize = t.shared; o.strand = t.strand;
+      l2[at + k] = o;
+    }
+  }
+}
+
 // the end of a sized L2 stage: the counters as last read back (MM_PC_*) become the number of loci, or the reason there is none
 // (MM_L2F_STREAM is raised by k_l2_locate alone: the literal launcher never sees it)
 static int mm_l2_verdict(mm_ctx* c, const unsigned long long* hc) {
@@ -1217,8 +1364,20 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
   // that list, whose length stays on the device (the launch covers every candidate), so the stage waits for the host as often as without
   // the option.  A sketch beyond the wave kernel's LDS layout, or a batch without a long fragment (a sketch beyond MM_LDS_MAX_SKETCH comes
   // here as well), is the literal kernel's alone.
-  const bool wave = c->l2WindowWave && c->windowed && s <= MM_WW_MAX_SKETCH && nC > 0;
+  // MM_OPT_L2_LARGE_WAVE, bit 0: a split batch (it is here for its sketch size, or for bit 1 of the option) goes to k_l2_large_wave first, in
+  // the same place and with the same hand-over, from the slices k_l2_extents computes; beyond MM_LW_MAX_SKETCH the literal kernel alone.
+  const bool winWave = c->l2WindowWave && c->windowed && s <= MM_WW_MAX_SKETCH && nC > 0;
+  const bool large = (c->l2LargeWave & 1) && !c->windowed && s <= MM_LW_MAX_SKETCH && nC > 0;
+  const bool wave = winWave || large;
   if (wave) MM_HIP(c, c->dL2Wide.ensure((size_t)nC * 4 + 64));
+  if (large) {
+    MM_HIP(c, c->dL2Info.ensure((size_t)nC * sizeof(L2Info) + 64)); MM_HIP(c, c->dL2Cnt.ensure((size_t)nC * 4 + 64));
+    KernelTimer t(c, MM_K_L2_LOCATE);
+    hipLaunchKernelGGL(k_l2_extents, dim3((nC + 255) / 256), dim3(256), 0, c->stream, nC, c->P.segLength, EF<13>::DELTA_BITS, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
+                       I.evKey.as<uint32_t>(), I.contigBlock.as<int64_t>(), I.blockOff.as<int64_t>(), I.evBlock.as<int64_t>(),
+                       c->dL2Info.as<L2Info>(), c->dL2Cnt.as<int32_t>(), (const unsigned long long*)nullptr, cnt);
+    MM_HIP(c, hipGetLastError());
+  }
   unsigned long long hc[MM_PC_READ];
   int locap = MM_LOCAP0;
   bool waveDone = false;
@@ -1226,7 +1385,21 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
     MM_HIP(c, c->dL2.ensure(c->l2Cap * sizeof(mm_l2_locus) + 64));
     MM_HIP(c, c->dL2Tmp.ensure((size_t)nC * locap * sizeof(L2Tmp) + 64));
     if (!wave || !waveDone) MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow, flags
-    if (wave && !waveDone) {
+    if (large && !waveDone) {
+      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LARGE_LEN, 0, 8, c->stream));                // the hand-over list's length (the L1 stage is done with the word)
+      KernelTimer t(c, MM_K_L2);
+      const size_t lds = mm_lw_lds(s);
+      int blocks = nC; if (blocks > 256 * 32) blocks = 256 * 32;
+      (void)hipFuncSetAttribute((const void*)k_l2_large_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(k_l2_large_wave, dim3((unsigned)blocks), dim3(64), lds, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dL2Info.as<L2Info>(),
+                         c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
+                         I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>(),
+                         I.contigOff.as<int64_t>(), c->dL1Off.as<int64_t>(), c->dL2.as<mm_l2_locus>(), (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(),
+                         c->dL2Num.as<int32_t>(), cnt, c->dL2Wide.as<int32_t>());
+      MM_HIP(c, hipGetLastError());
+      MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_EXACT_LEN, cnt + MM_PC_L2_LOCI, 8, hipMemcpyDeviceToDevice, c->stream));   // the cursor behind the wave kernel, as below
+      waveDone = true;
+    } else if (wave && !waveDone) {
       MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_WIDE_LEN, 0, 8, c->stream));                 // the hand-over list's length (the L1 stage is done with the word)
       KernelTimer t(c, MM_K_L2);
       const size_t lds = mm_ww_lds(s);
@@ -1267,6 +1440,9 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
   c->winCands = c->windowed ? (size_t)nC : 0;
   c->winLit = !c->windowed ? 0 : wave ? (size_t)hc[MM_PC_L2_WIDE_LEN] : (size_t)nC;
   if (c->env.debug && c->windowed) fprintf(stderr, "[mm] L2: of %d windowed candidates the literal L2 kernel took %zu\n", nC, c->winLit);
+  c->lwCands = c->windowed ? 0 : (size_t)nC;
+  c->lwLit = c->windowed ? 0 : large ? (size_t)hc[MM_PC_L2_LARGE_LEN] : (size_t)nC;
+  if (c->env.debug && !c->windowed) fprintf(stderr, "[mm] L2: of %d candidates of a split batch on the literal route k_l2_window took %zu\n", nC, c->lwLit);
   return mm_l2_verdict(c, hc);
 }
 
@@ -1296,8 +1472,8 @@ int mm_scan_i32_to_i64(mm_ctx* c, int64_t n, const int32_t* dIn, int64_t* dOut, 
 #define MM_EXACT_CAP 1024
 
 int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
-  if (!steady) { c->winCands = 0; c->winLit = 0; }                    // mm_pass_l2_window: as of the last sized pass
-  if (c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH) return mm_launch_l2_window(c, cnt);   // fragments longer than segLength (--noSplit), or a sketch no LDS state holds: the literal kernel
+  if (!steady) { c->winCands = 0; c->winLit = 0; c->lwCands = 0; c->lwLit = 0; }   // mm_pass_l2_window, mm_pass_l2_large: as of the last sized pass
+  if (c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH || (c->l2LargeWave & 2)) return mm_launch_l2_window(c, cnt);   // fragments longer than segLength (--noSplit), a sketch no LDS state holds, or bit 1 of MM_OPT_L2_LARGE_WAVE: the literal route
   const DeviceIndex& I = c->idx;
   const int s = c->P.sketchSize;
   // sized pass: the candidates are counted (c->nL1) and the candidate-indexed buffers get an eighth of head room, which is what a

@@ -1988,6 +1988,7 @@ static int map_pass(mm_ctx* c, const bool steady) {
     c->prevMid = c->lastMid = (size_t)p.hMid; c->midKnown = p.useMid;
     c->grpOffered = (size_t)p.nOffered; c->grpFused = p.useGroups ? (size_t)p.nOffered - (size_t)p.nBig : 0;
     c->winCands = 0; c->winLit = 0;                        // (mm_launch_l2 counts the windowed candidates of a sized pass)
+    c->lwCands = 0; c->lwLit = 0;
     if (c->nL1 == 0) { c->nL2 = 0; return MM_OK; }
   }
   return pass_finish(c, p);
@@ -2003,7 +2004,7 @@ int mm_launch_map(mm_ctx* c) {
   if (!c->hPass) { MM_HIP(c, hipHostMalloc((void**)&c->hPass, MM_COUNTER_BYTES, hipHostMallocDefault)); }
   c->nL1 = c->nL2 = 0; c->nMappings = 0; c->nSyncs = 0; c->lastSteady = false; c->redoCause = 0;
   if (nF == 0) return MM_OK;
-  const bool allSlow = c->keepPoints || (c->P.flags & MM_FLAG_SKIP_PREFIX) || c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH;
+  const bool allSlow = c->keepPoints || (c->P.flags & MM_FLAG_SKIP_PREFIX) || c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH || (c->l2LargeWave & 2);
   // (a batch with a tenth more fragments than the one the buffers were sized for would only fail and be redone: it is sized right away)
   if (c->steadyOk && c->steadyFails < 3 && !allSlow && (size_t)nF <= c->sizedFrags + c->sizedFrags / 10) {
     const int rc = map_pass(c, true);

@@ -144,6 +144,12 @@ class Sketch {
         std::cerr << "[mashmap_hip::skch::Sketch] ERROR: mm_set_option: " << mm_last_error(c) << std::endl;
         exit(1);
       }
+      // a sketch beyond 8190 (--dense at long segments): the L2 stage of a split batch on the wave-per-candidate kernel; the literal kernel
+      // takes the candidates that one hands over (profiles/NOTES.md: the probe that decided it).  Bit 0 only: bit 1 is a test switch
+      if (p.sketchSize > 8190 && mm_set_option(c, MM_OPT_L2_LARGE_WAVE, 1) != MM_OK) {
+        std::cerr << "[mashmap_hip::skch::Sketch] ERROR: mm_set_option: " << mm_last_error(c) << std::endl;
+        exit(1);
+      }
       ctxs_.push_back(c);
     }
     ctx_ = ctxs_[0];
