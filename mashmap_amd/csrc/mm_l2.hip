@@ -26,6 +26,7 @@
 #include "mm_device.h"
 #include "mm_heap.h"
 #include "mm_l2_window_core.h"
+#include "mm_l2_plan.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -68,7 +69,6 @@ template <int JB> struct EF {
   static constexpr int MATCH_BIT = JB, VOTE_SHIFT = JB + 1, DELTA_SHIFT = JB + 3, DELTA_BITS = 27 - (JB + 3);
   static constexpr uint32_t MAXDELTA = (1u << DELTA_BITS) - 1u;
 };
-static inline int mm_l2_jb(int s) { return s > 2046 ? 13 : 11; }
 
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -191,11 +191,6 @@ k_l2_pos_keys(int c0, int n, int shift, const L2Info* __restrict__ info, uint32_
 // k_l2_locate: one wave per candidate (4 per workgroup, no workgroup barrier).  LDS per wave: the fragment's query sketch
 // (hash + strand) and a table of NB >= s equal-width buckets over [0, qmax] that turns the lower_bound of a hash into one table read
 // plus a walk of ~1 entry (the hashes of a sketch are uniform, so equal-width buckets are balanced).
-// LDS of one wave of k_l2_locate: sketch + sentinel (8 B each), their high words (4 B), NB + 1 bucket starts (2 B), strands (1 B)
-__host__ __device__ static inline size_t mm_locate_lds_per_wave(int s, int NB) {
-  const size_t b = (size_t)(s + 1) * 8 + (size_t)(s + 2) / 2 * 8 + (size_t)(NB + 4) * 2 + (((size_t)s + 15) & ~(size_t)15) + (((size_t)(s + 4) / 2 * 4 + 15) & ~(size_t)15);
-  return (b + 15) & ~(size_t)15;
-}
 // ---------------------------------------------------------------------------------------------
 template <int JB>
 __global__ void __launch_bounds__(256)
@@ -1339,10 +1334,37 @@ static int mm_l2_verdict(mm_ctx* c, const unsigned long long* hc) {
   return MM_OK;
 }
 
-static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
+// What a sized L2 stage does about the counters it has just read back.  MoreSlots: a candidate tied in more loci than it has staging slots
+// (tandem repeats), locap is doubled -- unless twice the slots would need more than 64 GiB (GiveUp: mm_l2_verdict names the reason).
+// MoreLoci: the locus buffer is full, l2Cap follows the demand the cursor ran up to.  Slots come first, except (lociFirst) on the literal
+// route behind a wave kernel: a moved locus buffer has both kernels run again there, more slots the literal kernel alone.
+enum class L2Retry { Done, MoreSlots, MoreLoci, GiveUp };
+static L2Retry l2_after_readback(mm_ctx* c, const unsigned long long* hc, int nC, int& locap, bool lociFirst) {
+  const bool slots = (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) != 0, over = hc[MM_PC_L2_OVERFLOW] != 0;
+  if (slots && !(lociFirst && over)) {
+    if ((size_t)nC * (size_t)locap * 2 * sizeof(L2Tmp) > ((size_t)64 << 30)) return L2Retry::GiveUp;
+    locap *= 2;
+    return L2Retry::MoreSlots;
+  }
+  if (!over) return L2Retry::Done;
+  const size_t need = mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus));
+  c->l2Cap = need + need / 8 + 1024;
+  return L2Retry::MoreLoci;
+}
+
+// k_l2_extents over nC candidates (nDev: their number on the device, steady-state pass); the caller holds the timer
+static void l2_launch_extents(mm_ctx* c, unsigned long long* cnt, int nC, int deltaBits, const unsigned long long* nDev) {
   const DeviceIndex& I = c->idx;
-  const int s = c->P.sketchSize;
-  const int nC = (int)c->nL1;
+  hipLaunchKernelGGL(k_l2_extents, dim3((nC + 255) / 256), dim3(256), 0, c->stream, nC, c->P.segLength, deltaBits, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
+                     I.evKey.as<uint32_t>(), I.contigBlock.as<int64_t>(), I.blockOff.as<int64_t>(), I.evBlock.as<int64_t>(),
+                     c->dL2Info.as<L2Info>(), c->dL2Cnt.as<int32_t>(), nDev, cnt);
+}
+
+// ---- the literal route: mm_launch_l2_window and its stages ----------------------------------------------------------------------------------
+// stage 1: the per-candidate buffers, every candidate's window of the event stream (k_l2_window_extents), the scans of the two counts it
+// leaves and the scratch they size
+static int l2w_extents(mm_ctx* c, int nC) {
+  const DeviceIndex& I = c->idx;
   MM_HIP(c, c->dWinExt.ensure((size_t)nC * sizeof(WinExt) + 64));
   MM_HIP(c, c->dWinCntH.ensure((size_t)nC * 4 + 64)); MM_HIP(c, c->dWinCntT.ensure((size_t)nC * 4 + 64));
   MM_HIP(c, c->dWinOffH.ensure((size_t)nC * 8 + 64)); MM_HIP(c, c->dWinOffT.ensure((size_t)nC * 8 + 64));
@@ -1358,8 +1380,62 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
   }
   if ((size_t)totT * 12 + (size_t)totH * 4 > ((size_t)96 << 30)) { c->err = "windowLen != 0: the candidates of this batch need more than 96 GiB of scratch; use smaller batches (MASHMAP_HIP_BATCH_MBP)"; return MM_ERR_CAPACITY; }
   MM_HIP(c, c->dWinHeap.ensure((size_t)totH * 4 + 64)); MM_HIP(c, c->dWinKeys.ensure((size_t)totT * 8 + 64)); MM_HIP(c, c->dWinVals.ensure((size_t)totT * 4 + 64));
-  MM_HIP(c, c->dL2Cells.ensure((size_t)nC * (size_t)(s + 1) * sizeof(ExactCell) + 64));
+  MM_HIP(c, c->dL2Cells.ensure((size_t)nC * (size_t)(c->P.sketchSize + 1) * sizeof(ExactCell) + 64));
   if (c->l2Cap < c->nL1 * 2 + 1024) c->l2Cap = c->nL1 * 2 + 1024;
+  return MM_OK;
+}
+
+static void l2w_launch_large_wave(mm_ctx* c, unsigned long long* cnt, int nC, int blocks) {
+  const DeviceIndex& I = c->idx;
+  const int s = c->P.sketchSize; const size_t lds = mm_lw_lds(s);
+  (void)hipFuncSetAttribute((const void*)k_l2_large_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(k_l2_large_wave, dim3((unsigned)blocks), dim3(64), lds, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dL2Info.as<L2Info>(),
+                     c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
+                     I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>(),
+                     I.contigOff.as<int64_t>(), c->dL1Off.as<int64_t>(), c->dL2.as<mm_l2_locus>(), (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(),
+                     c->dL2Num.as<int32_t>(), cnt, c->dL2Wide.as<int32_t>());
+}
+
+static void l2w_launch_window_wave(mm_ctx* c, unsigned long long* cnt, int nC, int blocks) {
+  const DeviceIndex& I = c->idx;
+  const int s = c->P.sketchSize;
+  hipLaunchKernelGGL(k_l2_window_wave, dim3((unsigned)blocks), dim3(64), mm_ww_lds(s), c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
+                     c->dFrags.as<DFrag>(), c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
+                     I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.contigOff.as<int64_t>(), c->dWinExt.as<WinExt>(),
+                     c->dWinOffT.as<int64_t>(), c->dWinCntT.as<int32_t>(), c->dWinKeys.as<uint64_t>(), c->dWinVals.as<int32_t>(), c->dL1Off.as<int64_t>(),
+                     c->dL2.as<mm_l2_locus>(), (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt, c->dL2Wide.as<int32_t>());
+}
+
+// the wave kernel that takes every candidate first and leaves a list (dL2Wide) of those it cannot hold: its list-length word, the kernel,
+// and the cursor behind it -- where a repeated literal sweep (more locus slots) starts again (MM_PC_L2_EXACT_LEN: the exact sweep's list
+// length on the split route, unused here)
+static int l2w_first_kernel(mm_ctx* c, unsigned long long* cnt, int nC, bool large) {
+  MM_HIP(c, hipMemsetAsync(cnt + (large ? MM_PC_L2_LARGE_LEN : MM_PC_L2_WIDE_LEN), 0, 8, c->stream));   // (the L1 stage is done with the word)
+  KernelTimer t(c, MM_K_L2);
+  const int blocks = std::min(nC, 256 * 32);
+  if (large) l2w_launch_large_wave(c, cnt, nC, blocks); else l2w_launch_window_wave(c, cnt, nC, blocks);
+  MM_HIP(c, hipGetLastError());
+  MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_EXACT_LEN, cnt + MM_PC_L2_LOCI, 8, hipMemcpyDeviceToDevice, c->stream));
+  return MM_OK;
+}
+
+// the literal kernel: every candidate, or (list) the ones the wave kernel handed over
+static void l2w_launch_window(mm_ctx* c, unsigned long long* cnt, int nC, int locap, bool list) {
+  const DeviceIndex& I = c->idx;
+  const int s = c->P.sketchSize;
+  hipLaunchKernelGGL(k_l2_window, dim3((nC + 63) / 64), dim3(64), 0, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
+                     c->dFrags.as<DFrag>(), c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
+                     I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.contigOff.as<int64_t>(), c->dWinExt.as<WinExt>(),
+                     c->dWinOffH.as<int64_t>(), c->dWinOffT.as<int64_t>(), c->dWinCntT.as<int32_t>(), c->dWinHeap.as<int32_t>(), c->dWinKeys.as<uint64_t>(),
+                     c->dWinVals.as<int32_t>(), c->dL2Cells.as<ExactCell>(), c->dL1Off.as<int64_t>(), c->dL2Tmp.as<L2Tmp>(), locap, c->dL2.as<mm_l2_locus>(),
+                     (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt,
+                     list ? c->dL2Wide.as<int32_t>() : (const int32_t*)nullptr, list ? cnt + MM_PC_L2_WIDE_LEN : (const unsigned long long*)nullptr);
+}
+
+static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
+  const int s = c->P.sketchSize;
+  const int nC = (int)c->nL1;
+  { const int rc = l2w_extents(c, nC); if (rc != MM_OK) return rc; }
   // MM_OPT_L2_WINDOW_WAVE: k_l2_window_wave takes every candidate first and leaves a list of those it cannot hold; k_l2_window then walks
   // that list, whose length stays on the device (the launch covers every candidate), so the stage waits for the host as often as without
   // the option.  A sketch beyond the wave kernel's LDS layout, or a batch without a long fragment (a sketch beyond MM_LDS_MAX_SKETCH comes
@@ -1373,9 +1449,7 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
   if (large) {
     MM_HIP(c, c->dL2Info.ensure((size_t)nC * sizeof(L2Info) + 64)); MM_HIP(c, c->dL2Cnt.ensure((size_t)nC * 4 + 64));
     KernelTimer t(c, MM_K_L2_LOCATE);
-    hipLaunchKernelGGL(k_l2_extents, dim3((nC + 255) / 256), dim3(256), 0, c->stream, nC, c->P.segLength, EF<13>::DELTA_BITS, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
-                       I.evKey.as<uint32_t>(), I.contigBlock.as<int64_t>(), I.blockOff.as<int64_t>(), I.evBlock.as<int64_t>(),
-                       c->dL2Info.as<L2Info>(), c->dL2Cnt.as<int32_t>(), (const unsigned long long*)nullptr, cnt);
+    l2_launch_extents(c, cnt, nC, EF<13>::DELTA_BITS, nullptr);
     MM_HIP(c, hipGetLastError());
   }
   unsigned long long hc[MM_PC_READ];
@@ -1385,57 +1459,23 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
     MM_HIP(c, c->dL2.ensure(c->l2Cap * sizeof(mm_l2_locus) + 64));
     MM_HIP(c, c->dL2Tmp.ensure((size_t)nC * locap * sizeof(L2Tmp) + 64));
     if (!wave || !waveDone) MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow, flags
-    if (large && !waveDone) {
-      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LARGE_LEN, 0, 8, c->stream));                // the hand-over list's length (the L1 stage is done with the word)
-      KernelTimer t(c, MM_K_L2);
-      const size_t lds = mm_lw_lds(s);
-      int blocks = nC; if (blocks > 256 * 32) blocks = 256 * 32;
-      (void)hipFuncSetAttribute((const void*)k_l2_large_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(k_l2_large_wave, dim3((unsigned)blocks), dim3(64), lds, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dL2Info.as<L2Info>(),
-                         c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
-                         I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>(),
-                         I.contigOff.as<int64_t>(), c->dL1Off.as<int64_t>(), c->dL2.as<mm_l2_locus>(), (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(),
-                         c->dL2Num.as<int32_t>(), cnt, c->dL2Wide.as<int32_t>());
-      MM_HIP(c, hipGetLastError());
-      MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_EXACT_LEN, cnt + MM_PC_L2_LOCI, 8, hipMemcpyDeviceToDevice, c->stream));   // the cursor behind the wave kernel, as below
+    if (wave && !waveDone) {
+      const int rc = l2w_first_kernel(c, cnt, nC, large); if (rc != MM_OK) return rc;
       waveDone = true;
-    } else if (wave && !waveDone) {
-      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_WIDE_LEN, 0, 8, c->stream));                 // the hand-over list's length (the L1 stage is done with the word)
-      KernelTimer t(c, MM_K_L2);
-      const size_t lds = mm_ww_lds(s);
-      int blocks = nC; if (blocks > 256 * 32) blocks = 256 * 32;
-      hipLaunchKernelGGL(k_l2_window_wave, dim3((unsigned)blocks), dim3(64), lds, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
-                         c->dFrags.as<DFrag>(), c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
-                         I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.contigOff.as<int64_t>(), c->dWinExt.as<WinExt>(),
-                         c->dWinOffT.as<int64_t>(), c->dWinCntT.as<int32_t>(), c->dWinKeys.as<uint64_t>(), c->dWinVals.as<int32_t>(), c->dL1Off.as<int64_t>(),
-                         c->dL2.as<mm_l2_locus>(), (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt, c->dL2Wide.as<int32_t>());
-      MM_HIP(c, hipGetLastError());
-      // the cursor behind the wave kernel: where a repeated literal sweep (more locus slots) starts again (the word is the exact sweep's
-      // list length in split mode, unused here)
-      MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_EXACT_LEN, cnt + MM_PC_L2_LOCI, 8, hipMemcpyDeviceToDevice, c->stream));
-      waveDone = true;
-    } else if (wave) {
+    } else if (wave) {                                                     // again with more slots, the literal kernel alone: from the cursor behind the wave kernel
       MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_LOCI, cnt + MM_PC_L2_EXACT_LEN, 8, hipMemcpyDeviceToDevice, c->stream));
       MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_OVERFLOW, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_OVERFLOW) * 8, c->stream));
     }
     {
       KernelTimer t(c, MM_K_L2);
-      hipLaunchKernelGGL(k_l2_window, dim3((nC + 63) / 64), dim3(64), 0, c->stream, nC, s, c->P.segLength, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
-                         c->dFrags.as<DFrag>(), c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
-                         I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.contigOff.as<int64_t>(), c->dWinExt.as<WinExt>(),
-                         c->dWinOffH.as<int64_t>(), c->dWinOffT.as<int64_t>(), c->dWinCntT.as<int32_t>(), c->dWinHeap.as<int32_t>(), c->dWinKeys.as<uint64_t>(),
-                         c->dWinVals.as<int32_t>(), c->dL2Cells.as<ExactCell>(), c->dL1Off.as<int64_t>(), c->dL2Tmp.as<L2Tmp>(), locap, c->dL2.as<mm_l2_locus>(),
-                         (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt,
-                         wave ? c->dL2Wide.as<int32_t>() : (const int32_t*)nullptr, wave ? cnt + MM_PC_L2_WIDE_LEN : (const unsigned long long*)nullptr);
+      l2w_launch_window(c, cnt, nC, locap, wave);
       MM_HIP(c, hipGetLastError());
     }
     MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipStreamSynchronize(c->stream));
-    // without the option the parent's order: slots first.  With it a moved locus buffer has both kernels run again, so that comes first
-    const bool slots = (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) != 0, over = hc[MM_PC_L2_OVERFLOW] != 0;
-    if (slots && !(wave && over)) { if ((size_t)nC * (size_t)locap * 2 * sizeof(L2Tmp) > ((size_t)64 << 30)) break; locap *= 2; continue; }   // (with the option: the literal kernel alone)
-    if (over) { const size_t need = mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus)); c->l2Cap = need + need / 8 + 1024; waveDone = false; continue; }
-    break;
+    const L2Retry r = l2_after_readback(c, hc, nC, locap, /*lociFirst=*/wave);
+    if (r == L2Retry::MoreLoci) waveDone = false;                          // the locus buffer moves: the wave kernel runs again as well
+    if (r == L2Retry::Done || r == L2Retry::GiveUp) break;
   }
   c->winCands = c->windowed ? (size_t)nC : 0;
   c->winLit = !c->windowed ? 0 : wave ? (size_t)hc[MM_PC_L2_WIDE_LEN] : (size_t)nC;
@@ -1471,252 +1511,256 @@ int mm_scan_i32_to_i64(mm_ctx* c, int64_t n, const int32_t* dIn, int64_t* dOut, 
 #define MM_WIDE_CAP 4096     // steady-state passes: candidates the 16-bit re-run / the exact kernel are launched for without knowing their number
 #define MM_EXACT_CAP 1024
 
+// ---- the split route: what the stages of mm_launch_l2 hand on (it calls them in order; each one is a sequence of operations on c->stream)
+struct L2Pass {
+  bool steady;
+  unsigned long long* cnt;                 // dCounters + MM_CW_PASS (MM_PC_*)
+  L2Geom geom;                             // LDS geometry of the locate and sweep kernels at this sketch size (mm_l2_plan.h)
+  int nC = 0, nCbuf = 0;                   // candidates the launches cover; candidates the candidate-indexed buffers hold (candCap)
+  const unsigned long long* nDev = nullptr;   // steady-state pass: the number of candidates, where the kernels read it
+  int64_t totalOps = 0;                    // sized pass: stream entries of all candidates
+  std::vector<L2Chunk> chunks;             // consecutive candidates whose located streams share dL2Ops
+  bool oneChunk = true;                    // ... all of them: located once, the streams stay put over the retries
+  int posShift = 0;                        // event number -> the 16 bits of key the reference-order sort of k_l2_locate's candidates takes
+  int preLimit = 0;                        // pre-loads of this many records or more go to the exact kernel (MM_L2_PRE_LIMIT)
+  int locap = MM_LOCAP0;                   // staging slots per candidate
+  unsigned long long hc[MM_PC_READ] = {0}; // the counters as a sized pass last read them back
+};
+
+// stage 1: the candidate-indexed buffers, every candidate's slice of the event stream (k_l2_extents) and the scan of the stream lengths --
+// read back by a sized pass, left on the device (and checked against dL2Ops by k_l2_gate) by a steady-state one
+static int l2_extents(mm_ctx* c, L2Pass& p) {
+  // sized pass: the candidates are counted (c->nL1) and the candidate-indexed buffers get an eighth of head room, which is what a
+  // steady-state pass (count on the device: MM_PC_L1_CAND) launches against
+  if (!p.steady) { const size_t n1 = mm_scaled(c, c->nL1, 96 + 2 * (size_t)((c->P.sketchSize + 3) & ~1)); c->candCap = n1 + n1 / 8 + 1024; }
+  p.nC = p.steady ? (int)c->candCap : (int)c->nL1;
+  p.nCbuf = (int)c->candCap;
+  p.nDev = p.steady ? p.cnt + MM_PC_L1_CAND : nullptr;
+  MM_HIP(c, c->dL2Info.ensure((size_t)p.nCbuf * sizeof(L2Info) + 64));
+  MM_HIP(c, c->dL2Cnt.ensure((size_t)p.nCbuf * 4 + 64));
+  MM_HIP(c, c->dL2Off.ensure((size_t)p.nCbuf * 8 + 64));
+  MM_HIP(c, hipMemsetAsync(p.cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow, flags
+  KernelTimer t(c, MM_K_L2_LOCATE);
+  l2_launch_extents(c, p.cnt, p.nC, p.geom.JB == 13 ? EF<13>::DELTA_BITS : EF<11>::DELTA_BITS, p.nDev);
+  MM_HIP(c, hipGetLastError());
+  if (p.steady) {
+    const int64_t* dTotal = nullptr;
+    const int rc = mm_scan_i32_to_i64_dev(c, p.nC, c->dL2Cnt.as<int32_t>(), c->dL2Off.as<int64_t>(), &dTotal); if (rc != MM_OK) return rc;
+    MM_HIP(c, hipMemcpyAsync(c->dCounters.as<unsigned long long>() + MM_CW_MAP + MM_MC_L2_OPS, dTotal, 8, hipMemcpyDeviceToDevice, c->stream));   // read back with the pass's counters
+    hipLaunchKernelGGL(k_l2_gate, dim3(1), dim3(1), 0, c->stream, dTotal, (int64_t)(c->dL2Ops.bytes / 4) - 64, p.cnt);
+    MM_HIP(c, hipGetLastError());
+    return MM_OK;
+  }
+  const int rc = mm_scan_i32_to_i64(c, p.nC, c->dL2Cnt.as<int32_t>(), c->dL2Off.as<int64_t>(), &p.totalOps); c->nSyncs++; if (rc != MM_OK) return rc;
+  c->lastOps = (size_t)p.totalOps;
+  return MM_OK;
+}
+
+// stream entries (4 bytes each) a chunk may hold: 24 GiB, MM_L2_STREAM_MIB where it is set
+static int64_t l2_stream_budget(const mm_ctx* c) {
+  if (c->env.l2StreamMiB > 0) return (int64_t)(c->env.l2StreamMiB * 262144.0);
+  int64_t budget = (int64_t)24 << 28;
+  // ... or half of the device memory that is free (counting what the stream buffer already holds), up to 128 GiB: on a 288 GB part the
+  // streams of a configs[4] batch (57 GB: 2.7 M candidates at s = 498) then stay in one chunk, and the passes behind this one are
+  // steady-state passes instead of being sized, chunk by chunk, every time
+  size_t freeB = 0, totalB = 0;
+  if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+    const size_t half = (freeB + c->dL2Ops.bytes) / 2;
+    budget = std::max<int64_t>(budget, (int64_t)(std::min<size_t>(half, (size_t)128 << 30) / 4));
+  }
+  return budget;
+}
+
+// stage 2: the chunks, and the buffers sized by them.  The located streams (4 bytes per event a candidate touches: ~5 KB per candidate at
+// s = 130) live in HBM only between the locate and the sweep kernels; a batch with very many candidates -- reads out of repeat families --
+// is taken through the two in chunks, so the buffer does not grow with the repeat content.  A steady-state pass is one chunk: its streams
+// must fit the buffer as it is (k_l2_gate flags it otherwise).
+static int l2_plan(mm_ctx* c, L2Pass& p) {
+  const int s = c->P.sketchSize;
+  if (p.steady) p.chunks.push_back(L2Chunk{0, p.nC, 0});
+  else {
+    const int64_t* dOff = c->dL2Off.as<int64_t>();
+    const int nC = p.nC; const int64_t totalOps = p.totalOps;
+    auto offAt = [c, dOff, nC, totalOps](int i, int64_t& v) -> int {         // opOff[i], opOff[nC] = totalOps
+      if (i >= nC) { v = totalOps; return MM_OK; }
+      MM_HIP(c, hipMemcpy(&v, dOff + i, 8, hipMemcpyDeviceToHost));
+      return MM_OK;
+    };
+    int64_t maxChunkOps = 0;
+    const int rc = mm_l2_plan_chunks(nC, totalOps, l2_stream_budget(c), offAt, p.chunks, maxChunkOps); if (rc != MM_OK) return rc;
+    if (c->env.debug && p.chunks.size() > 1) fprintf(stderr, "[mm] L2: %lld stream entries of %d candidates in %zu chunks of at most %lld\n", (long long)totalOps, nC, p.chunks.size(), (long long)maxChunkOps);
+    const size_t opsFor = p.chunks.size() == 1 ? mm_scaled(c, (size_t)maxChunkOps, 4) : (size_t)maxChunkOps;
+    MM_HIP(c, c->dL2Ops.ensure((opsFor + opsFor / 16) * 4 + 256));   // a sixteenth of head room for the steady-state passes behind this one
+    c->l2Chunks = p.chunks.size();                                                        // a batch that needs several chunks stays with the sized passes
+  }
+  if (p.steady && c->dL2Ops.bytes == 0) { c->redoCause = MM_REDO_NO_STREAM_BUFFER; return MM_PASS_REDO; }
+  p.oneChunk = p.chunks.size() == 1;
+  // the pre-load states k_l2_locate leaves for the sweeps: a row of s + 2 cells and four integers per candidate of a chunk
+  size_t rows = 0;
+  for (const L2Chunk& ch : p.chunks) rows = std::max(rows, (size_t)ch.n);
+  if (p.oneChunk) rows = std::max(rows, (size_t)p.nCbuf);
+  MM_HIP(c, c->dL2InitCells.ensure(rows * (size_t)((s + 3) & ~1) * 2 + 64));
+  MM_HIP(c, c->dL2InitState.ensure(rows * sizeof(L2Init) + 64));
+  // total events of the index -> a shift that leaves 16 bits of key (two radix passes)
+  { const int64_t nEv = (int64_t)(c->idx.evKey.bytes / 4); while ((nEv >> p.posShift) > 0xFFFF) p.posShift++; }
+  p.preLimit = c->env.l2PreLimit;
+  return MM_OK;
+}
+
+// k_l2_locate over a chunk; above 4096 candidates they are taken in reference order (k_l2_pos_keys)
+static int l2_locate(mm_ctx* c, L2Pass& p, const L2Chunk& ch) {
+  const DeviceIndex& I = c->idx;
+  const L2Geom& g = p.geom;
+  KernelTimer t(c, MM_K_L2_LOCATE);
+  const int32_t* order = nullptr;
+  if (ch.n > 4096) {
+    MM_HIP(c, c->dL2OrderPos.ensure((size_t)p.nCbuf * 4 + 64));
+    MM_HIP(c, c->dL2Sort[0].ensure((size_t)p.nCbuf * 4 + 64)); MM_HIP(c, c->dL2Sort[2].ensure((size_t)p.nCbuf * 4 + 64));
+    hipLaunchKernelGGL(k_l2_pos_keys, dim3((unsigned)((ch.n + 255) / 256)), dim3(256), 0, c->stream, ch.c0, ch.n, p.posShift, c->dL2Info.as<L2Info>(),
+                       c->dL2Sort[0].as<uint32_t>(), c->dL2Sort[2].as<int32_t>(), p.nDev);
+    MM_HIP(c, hipGetLastError());
+    const int rc = mm_order_pairs(c, ch.n, 16u, c->dL2OrderPos.as<int32_t>());
+    if (rc != MM_OK) return rc;
+    order = c->dL2OrderPos.as<int32_t>();
+  }
+  const int blocks = std::min((ch.n + g.wpb - 1) / g.wpb, 256 * 32);
+  auto kern = k_l2_locate<13>; if (g.JB != 13) kern = k_l2_locate<11>;
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.ldsLoc);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(g.wpb * 64), g.ldsLoc, c->stream, ch.c0, ch.n, ch.base, c->P.sketchSize, g.NB, c->dL1.as<mm_l1_candidate>(),
+                     c->dStats.as<mm_frag_stats>(), c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
+                     I.evKey.as<uint32_t>(),
+                     I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>(),
+                     I.contigOff.as<int64_t>(),
+                     c->dL2Info.as<L2Info>(), c->dL2Off.as<int64_t>(), c->dL2Cnt.as<int32_t>(), c->dL2Ops.as<uint32_t>(), order, p.cnt, p.nDev,
+                     c->dL2InitCells.as<uint16_t>(), c->dL2InitState.as<L2Init>(), g.initStride, p.preLimit);
+  MM_HIP(c, hipGetLastError());
+  return MM_OK;
+}
+
+// one launch of a sweep kernel (8-bit cells, or 16-bit cells: wide): n candidates starting at c0, or the n listed ones (countDev: their
+// number lives on the device, the launch covers listCap of them); the caller holds the timer
+static void l2_sweep(mm_ctx* c, const L2Pass& p, bool wide, int c0, int n, int64_t opsBase, const int32_t* list, const unsigned long long* countDev, int listCap, int initBase) {
+  const L2Geom& g = p.geom;
+  const int lpw = wide ? g.lpwW : g.lpwN;
+  const size_t lds = wide ? g.ldsWide : g.ldsNarrow;
+  auto kern = k_l2_sweep<false, 11, 64>;                                  // (named in this order, the instantiations keep their places in the code object)
+  if (!wide && g.JB == 13) { if (lpw == 32) kern = k_l2_sweep<false, 13, 32>; else kern = k_l2_sweep<false, 13, 16>; }
+  if (wide && g.JB == 11) { if (lpw == 64) kern = k_l2_sweep<true, 11, 64>; else kern = k_l2_sweep<true, 11, 32>; }
+  if (wide && g.JB == 13) { if (lpw == 16) kern = k_l2_sweep<true, 13, 16>; else kern = k_l2_sweep<true, 13, 8>; }
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n + lpw - 1) / lpw)), dim3(64), lds, c->stream, c0, n, opsBase, list, c->P.segLength,
+                     c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(), c->dL2Off.as<int64_t>(), c->dL2Cnt.as<int32_t>(), c->dL2Ops.as<uint32_t>(),
+                     c->dL1Off.as<int64_t>(), c->dL2Tmp.as<L2Tmp>(), p.locap, c->dL2.as<mm_l2_locus>(), (unsigned long long)c->l2Cap,
+                     c->dL2Wide.as<int32_t>(), c->dL2Exact.as<int32_t>(), c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), p.cnt, countDev, listCap,
+                     c->dL2InitCells.as<uint16_t>(), c->dL2InitState.as<L2Init>(), g.initStride, initBase);
+}
+
+// k_l2_sweep_exact over the first n candidates of its list (countDev: their number lives on the device); dL2Cells holds n rows, the
+// caller holds the timer
+static void l2_sweep_exact(mm_ctx* c, const L2Pass& p, int n, int64_t opsBase, const unsigned long long* countDev) {
+  const DeviceIndex& I = c->idx;
+  const int s = c->P.sketchSize;
+  hipLaunchKernelGGL(k_l2_sweep_exact, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, p.geom.JB, n, opsBase, c->dL2Exact.as<int32_t>(), c->P.segLength,
+                     c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(), c->dL2Off.as<int64_t>(), c->dL2Cnt.as<int32_t>(), c->dL2Ops.as<uint32_t>(),
+                     c->dL1Off.as<int64_t>(), c->dL2Cells.as<ExactCell>(), s + 1, c->dL2Tmp.as<L2Tmp>(), p.locap, c->dL2.as<mm_l2_locus>(),
+                     (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), p.cnt, countDev,
+                     c->dL2Info.as<L2Info>(), s, c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
+                     I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>());
+}
+
+// a chunk's narrow sweep, behind its locate where the chunks take turns in dL2Ops, with the two lists it may queue candidates on emptied
+static int l2_chunk_narrow(mm_ctx* c, L2Pass& p, const L2Chunk& ch) {
+  if (!p.oneChunk) { const int rc = l2_locate(c, p, ch); if (rc != MM_OK) return rc; }
+  MM_HIP(c, hipMemsetAsync(p.cnt + MM_PC_L2_WIDE_LEN, 0, 8, c->stream));
+  MM_HIP(c, hipMemsetAsync(p.cnt + MM_PC_L2_EXACT_LEN, 0, 8, c->stream));   // (the L1 stage is done with both words)
+  KernelTimer t(c, MM_K_L2);
+  // lane-per-candidate sweep: candidates in order of descending stream length, so that the 64 streams of a wave end together
+  // (a wave runs as long as its longest; lengths spread ~ +-10 % around 45 steps: max of 64 is ~15 % above the mean)
+  const int32_t* order = nullptr;
+  if (ch.n > 64) {
+    MM_HIP(c, c->dL2Order.ensure((size_t)p.nCbuf * 4 + 64));
+    const int rc = mm_order_desc(c, c->dL2Cnt.as<int32_t>(), ch.c0, ch.n, 4, c->dL2Order.as<int32_t>());
+    if (rc != MM_OK) return rc;
+    order = c->dL2Order.as<int32_t>();
+  }
+  l2_sweep(c, p, false, ch.c0, ch.n, ch.base, order, p.nDev, 0, ch.c0);
+  MM_HIP(c, hipGetLastError());
+  return MM_OK;
+}
+
+// steady-state pass: the 16-bit re-run and the exact kernel for however many candidates the narrow sweep has queued (usually none),
+// launched for a fixed number of them; the lists' lengths are read on the device
+static int l2_chunk_steady(mm_ctx* c, L2Pass& p, const L2Chunk& ch) {
+  { const int rc = l2_chunk_narrow(c, p, ch); if (rc != MM_OK) return rc; }
+  KernelTimer t(c, MM_K_L2);
+  l2_sweep(c, p, true, 0, MM_WIDE_CAP, ch.base, c->dL2Wide.as<int32_t>(), p.cnt + MM_PC_L2_WIDE_LEN, MM_WIDE_CAP, ch.c0);
+  MM_HIP(c, hipGetLastError());
+  MM_HIP(c, c->dL2Cells.ensure((size_t)MM_EXACT_CAP * (size_t)(c->P.sketchSize + 1) * sizeof(ExactCell) + 64));
+  l2_sweep_exact(c, p, MM_EXACT_CAP, ch.base, p.cnt + MM_PC_L2_EXACT_LEN);
+  MM_HIP(c, hipGetLastError());
+  return MM_OK;
+}
+
+// sized pass: the counters are read back behind the narrow sweep, and behind each of the two re-runs that its lists ask for (neither runs
+// once the slots or the locus buffer have run out: the attempt is repeated anyway)
+static int l2_chunk_sized(mm_ctx* c, L2Pass& p, const L2Chunk& ch) {
+  { const int rc = l2_chunk_narrow(c, p, ch); if (rc != MM_OK) return rc; }
+  const unsigned long long* const hc = p.hc;
+  const auto spent = [hc]() { return (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) || hc[MM_PC_L2_OVERFLOW]; };
+  MM_HIP(c, hipMemcpyAsync(p.hc, p.cnt, sizeof p.hc, hipMemcpyDeviceToHost, c->stream));
+  MM_SYNC(c);
+  if (hc[MM_PC_L2_WIDE_LEN] && !spent()) {                                  // the few candidates whose 5-bit counters overflowed
+    const int nWide = (int)hc[MM_PC_L2_WIDE_LEN];
+    if (c->env.debug) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone with 16-bit cells\n", nWide, ch.n);
+    KernelTimer t(c, MM_K_L2);
+    l2_sweep(c, p, true, 0, nWide, ch.base, c->dL2Wide.as<int32_t>(), nullptr, 0, ch.c0);
+    MM_HIP(c, hipGetLastError());
+    MM_HIP(c, hipMemcpyAsync(p.hc, p.cnt, sizeof p.hc, hipMemcpyDeviceToHost, c->stream));
+    MM_SYNC(c);
+  }
+  if (hc[MM_PC_L2_EXACT_LEN] && !spent()) {                                 // candidates with a doubly open query hash: the literal sweep
+    const int nExact = (int)hc[MM_PC_L2_EXACT_LEN];
+    if (c->env.debug) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone by the exact kernel (overlapping windows of one hash)\n", nExact, ch.n);
+    MM_HIP(c, c->dL2Cells.ensure((size_t)nExact * (size_t)(c->P.sketchSize + 1) * sizeof(ExactCell) + 64));
+    KernelTimer t(c, MM_K_L2);
+    l2_sweep_exact(c, p, nExact, ch.base, nullptr);
+    MM_HIP(c, hipGetLastError());
+    MM_HIP(c, hipMemcpyAsync(p.hc, p.cnt, sizeof p.hc, hipMemcpyDeviceToHost, c->stream));
+    MM_SYNC(c);
+  }
+  return MM_OK;
+}
+
 int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
   if (!steady) { c->winCands = 0; c->winLit = 0; c->lwCands = 0; c->lwLit = 0; }   // mm_pass_l2_window, mm_pass_l2_large: as of the last sized pass
   if (c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH || (c->l2LargeWave & 2)) return mm_launch_l2_window(c, cnt);   // fragments longer than segLength (--noSplit), a sketch no LDS state holds, or bit 1 of MM_OPT_L2_LARGE_WAVE: the literal route
-  const DeviceIndex& I = c->idx;
-  const int s = c->P.sketchSize;
-  // sized pass: the candidates are counted (c->nL1) and the candidate-indexed buffers get an eighth of head room, which is what a
-  // steady-state pass (count on the device: MM_PC_L1_CAND) launches against
-  if (!steady) { const size_t n1 = mm_scaled(c, c->nL1, 96 + 2 * (size_t)((c->P.sketchSize + 3) & ~1)); c->candCap = n1 + n1 / 8 + 1024; }
-  const int nC = steady ? (int)c->candCap : (int)c->nL1;              // candidates the launches cover
-  const int nCbuf = (int)c->candCap;
-  const unsigned long long* nDev = steady ? cnt + MM_PC_L1_CAND : nullptr;
-  const int JB = mm_l2_jb(s);                                              // width of the stream entries' sketch-position field
-  MM_HIP(c, c->dL2Info.ensure((size_t)nCbuf * sizeof(L2Info) + 64));
-  MM_HIP(c, c->dL2Cnt.ensure((size_t)nCbuf * 4 + 64));
-  MM_HIP(c, c->dL2Off.ensure((size_t)nCbuf * 8 + 64));
-  MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS + 1 - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow, flags
-  int64_t totalOps = 0;
-  {
-    KernelTimer t(c, MM_K_L2_LOCATE);
-    hipLaunchKernelGGL(k_l2_extents, dim3((nC + 255) / 256), dim3(256), 0, c->stream, nC, c->P.segLength, JB == 13 ? EF<13>::DELTA_BITS : EF<11>::DELTA_BITS, c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(),
-                       I.evKey.as<uint32_t>(), I.contigBlock.as<int64_t>(), I.blockOff.as<int64_t>(), I.evBlock.as<int64_t>(),
-                       c->dL2Info.as<L2Info>(), c->dL2Cnt.as<int32_t>(), nDev, cnt);
-    MM_HIP(c, hipGetLastError());
-    if (steady) {
-      const int64_t* dTotal = nullptr;
-      const int rc = mm_scan_i32_to_i64_dev(c, nC, c->dL2Cnt.as<int32_t>(), c->dL2Off.as<int64_t>(), &dTotal); if (rc != MM_OK) return rc;
-      MM_HIP(c, hipMemcpyAsync(c->dCounters.as<unsigned long long>() + MM_CW_MAP + MM_MC_L2_OPS, dTotal, 8, hipMemcpyDeviceToDevice, c->stream));   // read back with the pass's counters
-      hipLaunchKernelGGL(k_l2_gate, dim3(1), dim3(1), 0, c->stream, dTotal, (int64_t)(c->dL2Ops.bytes / 4) - 64, cnt);
-      MM_HIP(c, hipGetLastError());
-    } else { const int rc = mm_scan_i32_to_i64(c, nC, c->dL2Cnt.as<int32_t>(), c->dL2Off.as<int64_t>(), &totalOps); c->nSyncs++; if (rc != MM_OK) return rc; c->lastOps = (size_t)totalOps; }
-  }
-  // The located streams (4 bytes per event a candidate touches: ~5 KB per candidate at s = 130) live in HBM only between the locate and
-  // the sweep kernels.  A batch with very many candidates -- reads out of repeat families -- is taken through the two in chunks of
-  // consecutive candidates whose streams fit MM_L2_STREAM_MIB (default 24 GiB), so the buffer does not grow with the repeat content.
-  struct Chunk { int c0, n; int64_t base; };
-  std::vector<Chunk> chunks;
-  int64_t maxChunkOps = totalOps;
-  if (steady) chunks.push_back(Chunk{0, nC, 0});                           // one chunk: the streams must fit the buffer as it is (k_l2_locate flags it otherwise)
-  else {
-    int64_t budget = (int64_t)24 << 28;                                    // in 4-byte entries: 24 GiB ...
-    {
-      // ... or half of the device memory that is free (counting what the stream buffer already holds), up to 128 GiB: on a 288 GB part the
-      // streams of a configs[4] batch (57 GB: 2.7 M candidates at s = 498) then stay in one chunk, and the passes behind this one are
-      // steady-state passes instead of being sized, chunk by chunk, every time
-      size_t freeB = 0, totalB = 0;
-      if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-        const size_t half = (freeB + c->dL2Ops.bytes) / 2;
-        budget = std::max<int64_t>(budget, (int64_t)(std::min<size_t>(half, (size_t)128 << 30) / 4));
-      }
-    }
-    if (c->env.l2StreamMiB > 0) budget = (int64_t)(c->env.l2StreamMiB * 262144.0);
-    if (totalOps <= budget || nC <= 1) chunks.push_back(Chunk{0, nC, 0});
-    else {
-      const int64_t* dOff = c->dL2Off.as<int64_t>();
-      auto offAt = [&](int i, int64_t& v) -> int {                          // opOff[i], opOff[nC] = totalOps
-        if (i >= nC) { v = totalOps; return MM_OK; }
-        MM_HIP(c, hipMemcpy(&v, dOff + i, 8, hipMemcpyDeviceToHost));
-        return MM_OK;
-      };
-      maxChunkOps = 0;
-      int c0 = 0; int64_t base = 0;
-      while (c0 < nC) {
-        int lo = c0 + 1, hi = nC;                                          // largest c1 with opOff[c1] - base <= budget, at least one candidate
-        while (lo < hi) {
-          const int mid = lo + (hi - lo + 1) / 2;
-          int64_t v; const int rc = offAt(mid, v); if (rc != MM_OK) return rc;
-          if (v - base <= budget) lo = mid; else hi = mid - 1;
-        }
-        int64_t end; { const int rc = offAt(lo, end); if (rc != MM_OK) return rc; }
-        chunks.push_back(Chunk{c0, lo - c0, base});
-        if (end - base > maxChunkOps) maxChunkOps = end - base;
-        c0 = lo; base = end;
-      }
-      if (c->env.debug) fprintf(stderr, "[mm] L2: %lld stream entries of %d candidates in %zu chunks of at most %lld\n", (long long)totalOps, nC, chunks.size(), (long long)maxChunkOps);
-    }
-  }
-  if (!steady) {
-    const size_t opsFor = chunks.size() == 1 ? mm_scaled(c, (size_t)maxChunkOps, 4) : (size_t)maxChunkOps;
-    MM_HIP(c, c->dL2Ops.ensure((opsFor + opsFor / 16) * 4 + 256));   // a sixteenth of head room for the steady-state passes behind this one
-    c->l2Chunks = chunks.size();                                                          // a batch that needs several chunks stays with the sized passes
-  }
-  if (steady && c->dL2Ops.bytes == 0) { c->redoCause = MM_REDO_NO_STREAM_BUFFER; return MM_PASS_REDO; }
-  // the pre-load states k_l2_locate leaves for the sweeps: a row of s + 2 cells and four integers per candidate of a chunk
-  {
-    size_t rows = 0;
-    for (const Chunk& ch : chunks) rows = std::max(rows, (size_t)ch.n);
-    if (chunks.size() == 1) rows = std::max(rows, (size_t)nCbuf);
-    MM_HIP(c, c->dL2InitCells.ensure(rows * (size_t)((s + 3) & ~1) * 2 + 64));
-    MM_HIP(c, c->dL2InitState.ensure(rows * sizeof(L2Init) + 64));
-  }
-  const int initStride = (s + 3) & ~1;                                       // cells per row: s + 2, rounded up to whole dwords
-  // buckets of the query-sketch search: at least one per sketch entry (more buckets cost more to fill per candidate than the shorter
-  // walks save: profiles/r02z_locate_buckets.txt)
-  int NB = 256; while (NB < s) NB <<= 1;
-  // waves per workgroup: 4, fewer when four sketches + bucket tables would not fit a CU's LDS
-  int wpb = 4; while (wpb > 1 && mm_locate_lds_per_wave(s, NB) * wpb > 160 * 1024) wpb >>= 1;
-  const size_t ldsLoc = mm_locate_lds_per_wave(s, NB) * wpb;
-  if (ldsLoc > 160 * 1024) { c->err = "sketchSize too large for the LDS-resident query sketch of k_l2_locate"; return MM_ERR_ARG; }
-  // total events of the index -> a shift that leaves 16 bits of key (two radix passes)
-  int posShift = 0; { const int64_t nEv = (int64_t)(I.evKey.bytes / 4); while ((nEv >> posShift) > 0xFFFF) posShift++; }
-  // pre-loads of this many records or more go to the exact kernel (12-bit cell counts); MM_L2_PRE_LIMIT lowers it so that tests can send
-  // every candidate there
-  const int preLimit = c->env.l2PreLimit;
-  auto locate = [&](const Chunk& ch) -> int {
-    KernelTimer t(c, MM_K_L2_LOCATE);
-    const int32_t* order = nullptr;
-    if (ch.n > 4096) {
-      MM_HIP(c, c->dL2OrderPos.ensure((size_t)nCbuf * 4 + 64));
-      MM_HIP(c, c->dL2Sort[0].ensure((size_t)nCbuf * 4 + 64)); MM_HIP(c, c->dL2Sort[2].ensure((size_t)nCbuf * 4 + 64));
-      hipLaunchKernelGGL(k_l2_pos_keys, dim3((unsigned)((ch.n + 255) / 256)), dim3(256), 0, c->stream, ch.c0, ch.n, posShift, c->dL2Info.as<L2Info>(),
-                         c->dL2Sort[0].as<uint32_t>(), c->dL2Sort[2].as<int32_t>(), nDev);
-      MM_HIP(c, hipGetLastError());
-      const int rc = mm_order_pairs(c, ch.n, 16u, c->dL2OrderPos.as<int32_t>());
-      if (rc != MM_OK) return rc;
-      order = c->dL2OrderPos.as<int32_t>();
-    }
-    int blocks = (ch.n + wpb - 1) / wpb; if (blocks > 256 * 32) blocks = 256 * 32;
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsLoc);
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(wpb * 64), ldsLoc, c->stream, ch.c0, ch.n, ch.base, s, NB, c->dL1.as<mm_l1_candidate>(),
-                         c->dStats.as<mm_frag_stats>(), c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
-                         I.evKey.as<uint32_t>(),
-                         I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>(),
-                         I.contigOff.as<int64_t>(),
-                         c->dL2Info.as<L2Info>(), c->dL2Off.as<int64_t>(), c->dL2Cnt.as<int32_t>(), c->dL2Ops.as<uint32_t>(), order, cnt, nDev,
-                         c->dL2InitCells.as<uint16_t>(), c->dL2InitState.as<L2Init>(), initStride, preLimit);
-    };
-    if (JB == 13) go(k_l2_locate<13>); else go(k_l2_locate<11>);
-    MM_HIP(c, hipGetLastError());
-    return MM_OK;
-  };
-  const bool oneChunk = chunks.size() == 1;
-  if (oneChunk) { const int rc = locate(chunks[0]); if (rc != MM_OK) return rc; }      // its streams stay put over the retries below
-  // candidates per wave of the sweeps (LPW): 64, fewer when the LDS state of 64 does not fit a CU -- 8-bit cells first, 16-bit cells
-  // for the rare candidate whose 5-bit counters overflow
-  // (JB == 11: always 64 lanes.  At s = 498 the state of 64 candidates is 32 KB, five waves per CU; 32 lanes per wave double the waves and
-  // were measured slower all the same -- sweep 40.1 -> 55.7 ms at configs[4], profiles/NOTES.md round 5: the kernel is issue-bound even there)
-  const int lpwN = JB == 11 ? 64 : ((size_t)(s + 2) * 32 <= 160 * 1024 ? 32 : 16);
-  const int lpwW = JB == 11 ? ((size_t)(s + 2) * 128 <= 160 * 1024 ? 64 : 32) : ((size_t)(s + 2) * 32 <= 160 * 1024 ? 16 : 8);
-  const size_t ldsWide = (size_t)(s + 2) * lpwW * 2;                       // cells 0..S + one of padding, 16 bit
-  const size_t ldsNarrow = (((size_t)(s + 2) * lpwN) + 15) & ~(size_t)15;  // 8 bit
-  if (ldsWide > 160 * 1024 || ldsNarrow > 160 * 1024) { c->err = "sketchSize too large for the LDS-resident L2 state"; return MM_ERR_ARG; }
-  // one launch of a sweep kernel: n candidates starting at c0, or the n listed ones (countDev: their number lives on the device, the
-  // launch covers listCap of them)
-  auto sweep = [&](bool wide, int c0, int n, int64_t opsBase, const int32_t* list, int locap_, const unsigned long long* countDev, int listCap, int initBase) {
-    auto go = [&](auto kern, int lpw, size_t lds) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kern, dim3((unsigned)((n + lpw - 1) / lpw)), dim3(64), lds, c->stream, c0, n, opsBase, list, c->P.segLength,
-                         c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(), c->dL2Off.as<int64_t>(), c->dL2Cnt.as<int32_t>(), c->dL2Ops.as<uint32_t>(),
-                         c->dL1Off.as<int64_t>(), c->dL2Tmp.as<L2Tmp>(), locap_, c->dL2.as<mm_l2_locus>(), (unsigned long long)c->l2Cap,
-                         c->dL2Wide.as<int32_t>(), c->dL2Exact.as<int32_t>(), c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt, countDev, listCap,
-                         c->dL2InitCells.as<uint16_t>(), c->dL2InitState.as<L2Init>(), initStride, initBase);
-    };
-    if (!wide) {
-      if (JB == 11) go(k_l2_sweep<false, 11, 64>, 64, ldsNarrow);
-      else if (lpwN == 32) go(k_l2_sweep<false, 13, 32>, 32, ldsNarrow);
-      else go(k_l2_sweep<false, 13, 16>, 16, ldsNarrow);
-    } else {
-      if (JB == 11) { if (lpwW == 64) go(k_l2_sweep<true, 11, 64>, 64, ldsWide); else go(k_l2_sweep<true, 11, 32>, 32, ldsWide); }
-      else { if (lpwW == 16) go(k_l2_sweep<true, 13, 16>, 16, ldsWide); else go(k_l2_sweep<true, 13, 8>, 8, ldsWide); }
-    }
-  };
-  MM_HIP(c, c->dL2Wide.ensure((size_t)nCbuf * 4 + 64)); MM_HIP(c, c->dL2Exact.ensure((size_t)nCbuf * 4 + 64));
-  MM_HIP(c, c->dL2First.ensure((size_t)nCbuf * 8 + 64)); MM_HIP(c, c->dL2Num.ensure((size_t)nCbuf * 4 + 64));
-  if (c->l2Cap < (size_t)nCbuf * 2 + 1024) c->l2Cap = (size_t)nCbuf * 2 + 1024;
-  unsigned long long hc[MM_PC_READ] = {0};
-  int locap = steady && c->prevLocap ? c->prevLocap : MM_LOCAP0;
+  L2Pass p;
+  p.steady = steady; p.cnt = cnt; p.geom = mm_l2_geom(c->P.sketchSize);
+  int rc = l2_extents(c, p); if (rc != MM_OK) return rc;
+  rc = l2_plan(c, p); if (rc != MM_OK) return rc;
+  if (p.oneChunk) { rc = l2_locate(c, p, p.chunks[0]); if (rc != MM_OK) return rc; }      // its streams stay put over the retries below
+  MM_HIP(c, c->dL2Wide.ensure((size_t)p.nCbuf * 4 + 64)); MM_HIP(c, c->dL2Exact.ensure((size_t)p.nCbuf * 4 + 64));
+  MM_HIP(c, c->dL2First.ensure((size_t)p.nCbuf * 8 + 64)); MM_HIP(c, c->dL2Num.ensure((size_t)p.nCbuf * 4 + 64));
+  if (c->l2Cap < (size_t)p.nCbuf * 2 + 1024) c->l2Cap = (size_t)p.nCbuf * 2 + 1024;
+  if (steady && c->prevLocap) p.locap = c->prevLocap;
   for (int attempt = 0; attempt < 24; attempt++) {
     MM_HIP(c, c->dL2.ensure(c->l2Cap * sizeof(mm_l2_locus) + 64));
-    MM_HIP(c, c->dL2Tmp.ensure((size_t)nCbuf * locap * sizeof(L2Tmp) + 64));
+    MM_HIP(c, c->dL2Tmp.ensure((size_t)p.nCbuf * p.locap * sizeof(L2Tmp) + 64));
     MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_LOCI, 0, (size_t)(MM_PC_L2_FLAGS - MM_PC_L2_LOCI) * 8, c->stream));   // cursor, overflow; MM_PC_L2_FLAGS keeps the locate kernel's
-    for (const Chunk& ch : chunks) {
-      if (!oneChunk) { const int rc = locate(ch); if (rc != MM_OK) return rc; }
-      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_WIDE_LEN, 0, 8, c->stream));
-      MM_HIP(c, hipMemsetAsync(cnt + MM_PC_L2_EXACT_LEN, 0, 8, c->stream));   // (the L1 stage is done with both words)
-      {
-        KernelTimer t(c, MM_K_L2);
-        // lane-per-candidate sweep: candidates in order of descending stream length, so that the 64 streams of a wave end together
-        // (a wave runs as long as its longest; lengths spread ~ +-10 % around 45 steps: max of 64 is ~15 % above the mean)
-        const int32_t* order = nullptr;
-        if (ch.n > 64) {
-          MM_HIP(c, c->dL2Order.ensure((size_t)nCbuf * 4 + 64));
-          const int rc = mm_order_desc(c, c->dL2Cnt.as<int32_t>(), ch.c0, ch.n, 4, c->dL2Order.as<int32_t>());
-          if (rc != MM_OK) return rc;
-          order = c->dL2Order.as<int32_t>();
-        }
-        sweep(false, ch.c0, ch.n, ch.base, order, locap, nDev, 0, ch.c0);
-        MM_HIP(c, hipGetLastError());
-      }
-      if (steady) {
-        // the 16-bit re-run and the exact kernel for however many candidates the narrow sweep has queued (usually none): launched for
-        // a fixed number of them, the lists' lengths are read on the device
-        KernelTimer t(c, MM_K_L2);
-        sweep(true, 0, MM_WIDE_CAP, ch.base, c->dL2Wide.as<int32_t>(), locap, cnt + MM_PC_L2_WIDE_LEN, MM_WIDE_CAP, ch.c0);
-        MM_HIP(c, hipGetLastError());
-        MM_HIP(c, c->dL2Cells.ensure((size_t)MM_EXACT_CAP * (size_t)(s + 1) * sizeof(ExactCell) + 64));
-        hipLaunchKernelGGL(k_l2_sweep_exact, dim3((unsigned)((MM_EXACT_CAP + 63) / 64)), dim3(64), 0, c->stream, JB, MM_EXACT_CAP, ch.base, c->dL2Exact.as<int32_t>(), c->P.segLength,
-                           c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(), c->dL2Off.as<int64_t>(), c->dL2Cnt.as<int32_t>(), c->dL2Ops.as<uint32_t>(),
-                           c->dL1Off.as<int64_t>(), c->dL2Cells.as<ExactCell>(), s + 1, c->dL2Tmp.as<L2Tmp>(), locap, c->dL2.as<mm_l2_locus>(),
-                           (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt, cnt + MM_PC_L2_EXACT_LEN,
-                           c->dL2Info.as<L2Info>(), s, c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
-                           I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>());
-        MM_HIP(c, hipGetLastError());
-        continue;
-      }
-      MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
-      MM_SYNC(c);
-      if (hc[MM_PC_L2_WIDE_LEN] && !(hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) && !hc[MM_PC_L2_OVERFLOW]) {                            // the few candidates whose 5-bit counters overflowed
-        const int nWide = (int)hc[MM_PC_L2_WIDE_LEN];
-        if (c->env.debug) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone with 16-bit cells\n", nWide, ch.n);
-        KernelTimer t(c, MM_K_L2);
-        sweep(true, 0, nWide, ch.base, c->dL2Wide.as<int32_t>(), locap, nullptr, 0, ch.c0);
-        MM_HIP(c, hipGetLastError());
-        MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
-        MM_SYNC(c);
-      }
-      if (hc[MM_PC_L2_EXACT_LEN] && !(hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) && !hc[MM_PC_L2_OVERFLOW]) {                            // candidates with a doubly open query hash: the literal sweep
-        const int nExact = (int)hc[MM_PC_L2_EXACT_LEN];
-        if (c->env.debug) fprintf(stderr, "[mm] L2 sweep: %d of %d candidates redone by the exact kernel (overlapping windows of one hash)\n", nExact, ch.n);
-        MM_HIP(c, c->dL2Cells.ensure((size_t)nExact * (size_t)(s + 1) * sizeof(ExactCell) + 64));
-        KernelTimer t(c, MM_K_L2);
-        hipLaunchKernelGGL(k_l2_sweep_exact, dim3((unsigned)((nExact + 63) / 64)), dim3(64), 0, c->stream, JB, nExact, ch.base, c->dL2Exact.as<int32_t>(), c->P.segLength,
-                           c->dL1.as<mm_l1_candidate>(), c->dStats.as<mm_frag_stats>(), c->dL2Off.as<int64_t>(), c->dL2Cnt.as<int32_t>(), c->dL2Ops.as<uint32_t>(),
-                           c->dL1Off.as<int64_t>(), c->dL2Cells.as<ExactCell>(), s + 1, c->dL2Tmp.as<L2Tmp>(), locap, c->dL2.as<mm_l2_locus>(),
-                           (unsigned long long)c->l2Cap, c->dL2First.as<int64_t>(), c->dL2Num.as<int32_t>(), cnt, (const unsigned long long*)nullptr,
-                           c->dL2Info.as<L2Info>(), s, c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(), c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(),
-                           I.evKey.as<uint32_t>(), I.evAux.as<uint32_t>(), I.evHash.as<uint64_t>(), I.opKey.as<uint32_t>(), I.opAux.as<uint32_t>(), I.opHash.as<uint64_t>());
-        MM_HIP(c, hipGetLastError());
-        MM_HIP(c, hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, c->stream));
-        MM_SYNC(c);
-      }
-      if (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) break;                                             // slots ran out: everything is redone below with more of them (a full locus
+    for (const L2Chunk& ch : p.chunks) {
+      rc = steady ? l2_chunk_steady(c, p, ch) : l2_chunk_sized(c, p, ch); if (rc != MM_OK) return rc;
+      if (p.hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) break;                       // slots ran out: everything is redone below with more of them (a full locus
                                                                            // buffer lets the other chunks run on, so that the cursor ends at the total demand)
     }
     if (steady) return MM_OK;                                              // the flags and the count are read when the pass is over
-    if (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) {                                                    // a candidate with more tied loci than slots (tandem repeats): more slots, again
-      if ((size_t)nC * (size_t)locap * 2 * sizeof(L2Tmp) > ((size_t)64 << 30)) break;
-      locap *= 2;
-      const unsigned long long flags = hc[MM_PC_L2_FLAGS] & ~MM_L2F_SLOTS;
+    const L2Retry r = l2_after_readback(c, p.hc, p.nC, p.locap, /*lociFirst=*/false);
+    if (r == L2Retry::MoreSlots) {                                         // the flag comes down on the device as well; the locate kernel's stay
+      const unsigned long long flags = p.hc[MM_PC_L2_FLAGS] & ~MM_L2F_SLOTS;
       MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L2_FLAGS, &flags, 8, hipMemcpyHostToDevice, c->stream));
-      continue;
     }
-    if (hc[MM_PC_L2_OVERFLOW]) { const size_t need = mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus)); c->l2Cap = need + need / 8 + 1024; continue; }
-    break;
+    if (r == L2Retry::Done || r == L2Retry::GiveUp) break;
   }
-  const int rc = mm_l2_verdict(c, hc);
-  if (rc == MM_OK) c->prevLocap = locap;
+  rc = mm_l2_verdict(c, p.hc);
+  if (rc == MM_OK) c->prevLocap = p.locap;
   return rc;
 }

@@ -772,17 +772,13 @@ static SketchPlan sketch_plan(int K, int s, int maxLen, size_t tabBytes, bool sl
 }
 
 // Parameter combinations the LDS-resident kernels cannot hold are refused when the context is created (not after the reference
-// index has been built): the sketch tables + a staged fragment of segLength bases, and the 16-bit L2 state cells of k_l2_sweep.
+// index has been built): the sketch tables + a staged fragment of segLength bases.  (The L2 kernels hold every sketch of up to
+// MM_LDS_MAX_SKETCH entries in LDS, whatever the other parameters: mm_l2_plan.h asserts it.)
 int mm_check_params(const mm_params* p, std::string& err) {
   const int s = p->sketchSize, L = p->segLength;
   const size_t tabBytes = (p->kmerSize >= 16 && p->kmerSize <= 32) ? sizeof(MMProdTables) : sizeof(MMTables);
   const SketchPlan P = sketch_plan(p->kmerSize, s, L, tabBytes, false);
   const size_t lim = 160 * 1024;
-  // L2: the 16-bit state cells of as few as 8 candidates per wave, the query sketch + bucket table of one wave of k_l2_locate, and the
-  // 13-bit sketch-position field of the located stream (mm_l2.hip)
-  const size_t ldsL2 = (size_t)(s + 1) * 8 * 2;
-  int NB = 256; while (NB < s) NB <<= 1;
-  const size_t ldsLoc = (size_t)(s + 1) * 8 + (size_t)(s + 2) / 2 * 8 + (size_t)(NB + 4) * 2 + (size_t)s + 32 + (size_t)(s + 4) / 2 * 4 + 16;   // (one wave of k_l2_locate: mm_locate_lds_per_wave)
   if (s > MM_LDS_MAX_SKETCH) {
     // no LDS kernel holds this sketch: the global-memory sketch kernel (mm_sketch_global.hip) and the literal L2 kernels take every
     // fragment -- exact, slow; the stock binary runs these sizes (--dense at segments of 100 kbp), so they run here too
@@ -794,11 +790,10 @@ int mm_check_params(const mm_params* p, std::string& err) {
     }
     return MM_OK;
   }
-  if (!P.ok || ldsL2 > lim || ldsLoc > lim) {
+  if (!P.ok) {
     char b[400];
-    snprintf(b, sizeof b, "mm_create: segLength %d with sketchSize %d needs %zu bytes of LDS in the sketch kernel (table of the exact path, spilled form), %zu in the L2 "
-             "sweep and %zu in the L2 locate kernel; a CU has %zu (sketchSize up to ~5000)",
-             L, s, P.ldsHard, ldsL2, ldsLoc, lim);
+    snprintf(b, sizeof b, "mm_create: segLength %d with sketchSize %d needs %zu bytes of LDS in the sketch kernel (table of the exact path, spilled form); a CU has %zu",
+             L, s, P.ldsHard, lim);
     err = b; return MM_ERR_ARG;
   }
   return MM_OK;

@@ -442,6 +442,52 @@ def test_l2_in_chunks_of_candidates(oracle, monkeypatch):
         assert run(budget)[:4] == whole[:4], budget
 
 
+@pytest.mark.parametrize("cause", ["slots", "loci", "loci8"])
+def test_l2_in_chunks_is_repeated_for_more_slots_or_loci(oracle, monkeypatch, cause):
+    """the chunk loop crossed with the retry loop of mm_launch_l2: a batch in chunks is located again chunk by chunk on every attempt, the
+    chunk loop ends early once a candidate has run out of locus slots (the flag then comes down on the device as well), and a full locus
+    buffer lets the other chunks run on so that the cursor ends at the demand.  The B batches of tests/test_gpu_steady.py that run out of
+    slots (twelve exact copies of a unit: eleven or twelve tied loci in a candidate) and of locus buffer (six exact copies, 1 500 reads), by
+    a fresh context in one chunk and in four or more: the same bytes; and the oracle's integers on the reduced read set.
+    FINDING: the six-copy batch has more loci than 2 n1 + 1 024 (7 811 against 5 290, at 2 133 candidates), which is what it outgrows behind
+    a context sized on another batch; a FRESH context starts its locus buffer at 2 candCap + 1 024 = 7 870 (candCap = n1 + n1 / 8 + 1 024),
+    which holds them, so "loci" crosses the chunk loop without a repeat.  "loci8" is the same batch over eight exact copies -- up to eight
+    tied loci, which the slots still hold -- and is held to the buffer a fresh context starts with: that one is repeated for more loci"""
+    import test_gpu_steady as S
+    if cause == "slots":
+        ua, ub = U.random_dna(9061, 1100), U.random_dna(9062, 1100)
+        contigs = [S.UNIQ[:300000], S.arrayed(9063, ua, 12, 0.03), S.arrayed(9064, ub, 12, 0)]
+        B = S.unit_reads(ub, 9067, 100) + [U.random_dna(9700 + i, S.L) for i in range(300)]
+        few = S.named("b", B[:12]) + S.named("r", B[100:104])
+    else:
+        ua, ub = U.random_dna(9051, 1100), U.random_dna(9052, 1300)
+        contigs = [S.UNIQ[:200000], S.arrayed(9053, ua, 6, 0.03), S.arrayed(9054, ub, 8 if cause == "loci8" else 6, 0)]
+        B = S.unit_reads(ub, 9056, 1500)
+        few = S.named("a", S.unit_reads(ua, 9055, 1500)[:12]) + S.named("b", B[:12])
+    make = S.built(contigs, 32)
+    monkeypatch.delenv("MM_L2_STREAM_MIB", raising=False)
+    whole = S.Fresh(make, B)
+    per = S.loci_per_candidate(make, B)
+    print("%s: %r, at most %d loci in a candidate" % (cause, whole, per.max()))
+    if cause == "slots":
+        assert per.max() > S.LOCAP0 + 1, "no candidate ties in more loci than %d slots and the pending one hold" % S.LOCAP0
+    else:
+        assert per.max() <= S.LOCAP0, "a candidate has more loci than slots"
+        assert whole.n2 > 2 * whole.n1 + 1024, "no more loci than 2 n1 + 1024"
+        if cause == "loci8":
+            assert whole.n2 > 2 * S.cand_cap(whole.n1) + 1024, "the loci fit the buffer a fresh context starts with"
+    budget = "%.6f" % (whole.ops / 4.0 / 262144.0)                              # MiB: a quarter of the batch's stream entries
+    entries = int(float(budget) * 262144.0)                                       # (env_read, l2_stream_budget)
+    assert entries > 0 and whole.ops > 3 * entries, "fewer than three chunks"
+    monkeypatch.setenv("MM_L2_STREAM_MIB", budget)
+    chunked = S.Fresh(make, B)
+    monkeypatch.delenv("MM_L2_STREAM_MIB")
+    for a, b, what in zip(chunked.bytes, whole.bytes, ("stats", "l1", "l2", "mappings", "query sketches")):
+        assert a == b, "in chunks the pass disagrees with the pass in one chunk on " + what
+    assert chunked.counts == whole.counts
+    run_and_compare(oracle, S.named("c", contigs), few, k=S.K, L=S.L, s=32, kmerPct=0.0, pi=S.PI, device_index=True, verbose=False)
+
+
 @pytest.mark.parametrize("limit", ["0", "150"])
 def test_l2_exact_kernel_takes_candidates_with_a_long_preload(oracle, monkeypatch, limit):
     """k_l2_locate hands candidates whose pre-load (the records open at rangeStart) is too long for its 12-bit cell counts to

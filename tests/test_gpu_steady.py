@@ -386,7 +386,7 @@ EXEMPT_IN_TEST_GPU_MAP = {
     "test_map_no_split_window_with_many_candidates[False]": ["nosplit"],
     "test_map_no_split_window_with_many_candidates[True]": ["skip_prefix"],
 }
-CALLS_IN_TEST_GPU_MAP = 48
+CALLS_IN_TEST_GPU_MAP = 51
 
 
 def test_every_parity_case_the_rule_does_not_exempt_took_the_steady_leg(oracle, request):
