@@ -113,6 +113,20 @@ __device__ __forceinline__ uint32_t mm_popc_below(uint64_t mask) {    // set bit
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// A 64-bit value of one lane for the whole wave, as two 32-bit broadcasts: one form per intrinsic.  __shfl goes through the LDS crossbar and
+// takes any lane index; readlane wants a wave-uniform one (mm_rl makes it so for the compiler) and leaves the result in scalar registers, as
+// readfirstlane does for the first active lane.
+__device__ __forceinline__ int mm_rl(int v, int l) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(l)); }
+__device__ __forceinline__ uint64_t mm_bcast64_shfl(uint64_t v, int l) {
+  return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), l) << 32) | (uint32_t)__shfl((int)(uint32_t)v, l);
+}
+__device__ __forceinline__ uint64_t mm_bcast64_readlane(uint64_t v, int l) {
+  return ((uint64_t)(uint32_t)mm_rl((int)(uint32_t)(v >> 32), l) << 32) | (uint32_t)mm_rl((int)(uint32_t)v, l);
+}
+__device__ __forceinline__ uint64_t mm_bcast64_readfirstlane(uint64_t v) {
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+
 // Wave reductions / scans on the VALU's DPP lanes (no LDS round trip per step as with ds_bpermute shuffles).  All 64 lanes
 // must be active.  quad_perm / row_half_mirror / row_mirror leave every lane with the result of its row of 16; the four
 // rows are combined through v_readlane, so the result is wave-uniform (an SGPR).

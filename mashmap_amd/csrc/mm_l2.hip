@@ -458,6 +458,13 @@ template <int B> __device__ __forceinline__ int mm_bit_mask(uint32_t x) { int m;
 // bank, byte p & 3 of dword (p >> 2) * 64 + l, at five more VALU instructions per cell access).  One cell of padding behind position S
 // lets the neighbour be read without clamping (its value is masked when the pivot is at S).
 // ---------------------------------------------------------------------------------------------
+// one locus of candidate `candLocal` of fragment f as the record the selection reads
+__device__ __forceinline__ mm_l2_locus mm_l2_record(int f, int candLocal, int seqId, int start, int end, int shared, int strand) {
+  mm_l2_locus o;
+  o.frag = f; o.cand = candLocal; o.seqId = seqId; o.optimalStart = start; o.optimalEnd = end;
+  o.meanOptimalPos = (start + end) / 2; o.sharedSketchSize = shared; o.strand = strand;
+  return o;
+}
 // LPW lanes of a wave carry a candidate (64; fewer for sketches whose 64 states would not fit a CU's LDS: 32, 16 or 8 -- the other
 // lanes leave at once); JB: width of the stream entries' sketch-position field.
 template <bool WIDE, int JB, int LPW>
@@ -664,7 +671,7 @@ k_l2_sweep(int cBase, int nCand, int64_t opsBase, const int32_t* __restrict__ ca
   const int waveTotal = __shfl(incl, lastLane);
   unsigned long long wbase = 0;
   if (lane == lastLane && waveTotal > 0) wbase = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)waveTotal);
-  wbase = ((unsigned long long)(uint32_t)__shfl((int)(wbase >> 32), lastLane) << 32) | (uint32_t)__shfl((int)(uint32_t)wbase, lastLane);
+  wbase = mm_bcast64_shfl(wbase, lastLane);
   if (waveTotal > 0 && wbase + (unsigned long long)waveTotal > l2Cap) { if (lane == lastLane) atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); return; }
   l2First[cIdx] = (int64_t)(wbase + (unsigned long long)(incl - total)); l2Num[cIdx] = total;   // where k_l2_select finds this candidate's loci
   if (total > 0) {
@@ -672,10 +679,7 @@ k_l2_sweep(int cBase, int nCand, int64_t opsBase, const int32_t* __restrict__ ca
     const int candLocal = (int)(cIdx - l1Off[f]);
     for (int k = 0; k < total; k++) {
       const L2Tmp t = (k < nFlushed) ? mySlots[k] : pend;
-      mm_l2_locus o;
-      o.frag = f; o.cand = candLocal; o.seqId = cand.seqId; o.optimalStart = t.start; o.optimalEnd = t.end;
-      o.meanOptimalPos = (t.start + t.end) / 2; o.sharedSketchSize = t.shared; o.strand = t.strand;
-      l2[base + k] = o;                                // a candidate's loci are contiguous and in emission order
+      l2[base + k] = mm_l2_record(f, candLocal, cand.seqId, t.start, t.end, t.shared, t.strand);   // a candidate's loci are contiguous and in emission order
     }
   }
 }
@@ -689,6 +693,24 @@ k_l2_sweep(int cBase, int nCand, int64_t opsBase, const int32_t* __restrict__ ca
 // Rare by construction, so nothing here is tuned.
 // ---------------------------------------------------------------------------------------------
 struct ExactCell { int32_t cnt; int16_t vote; int16_t active; };
+// The end of candidate c for a kernel that gives it one THREAD: its `total` loci (the first nFlushed in mySlots, then the pending one) are
+// claimed from the pass's cursor and written, l2First / l2Num say where k_l2_select finds them.  Where they do not fit the buffer,
+// MM_PC_L2_OVERFLOW is raised and nothing is written.
+__device__ __forceinline__ void mm_l2_emit_thread(int c, const mm_l1_candidate& cand, int total, int nFlushed, const L2Tmp* __restrict__ mySlots, const L2Tmp& pend,
+                                                  const int64_t* __restrict__ l1Off, mm_l2_locus* __restrict__ l2, unsigned long long l2Cap,
+                                                  int64_t* __restrict__ l2First, int32_t* __restrict__ l2Num, unsigned long long* __restrict__ counters) {
+  unsigned long long base = 0;
+  if (total > 0) {
+    base = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
+    if (base + (unsigned long long)total > l2Cap) { atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); return; }
+  }
+  l2First[c] = (int64_t)base; l2Num[c] = total;
+  const int candLocal = (int)(c - l1Off[cand.frag]);
+  for (int k = 0; k < total; k++) {
+    const L2Tmp t = (k < nFlushed) ? mySlots[k] : pend;
+    l2[base + k] = mm_l2_record(cand.frag, candLocal, cand.seqId, t.start, t.end, t.shared, t.strand);
+  }
+}
 __global__ void __launch_bounds__(64)
 k_l2_sweep_exact(int jb, int nList, int64_t opsBase, const int32_t* __restrict__ list, int segLength, const mm_l1_candidate* __restrict__ l1, const mm_frag_stats* __restrict__ stats,
                  const int64_t* __restrict__ opOff, const int32_t* __restrict__ opCnt, const uint32_t* __restrict__ ops,
@@ -819,20 +841,7 @@ k_l2_sweep_exact(int jb, int nList, int64_t opsBase, const int32_t* __restrict__
   if (inRun) close_run(votes >= 0 ? 1 : -1);
   int total = nFlushed + (havePend ? 1 : 0);
   if (slotOverflow) { atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_SLOTS); total = 0; }
-  unsigned long long base = 0;
-  if (total > 0) {
-    base = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
-    if (base + (unsigned long long)total > l2Cap) { atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); return; }
-  }
-  l2First[cIdx] = (int64_t)base; l2Num[cIdx] = total;
-  const int candLocal = (int)(cIdx - l1Off[f]);
-  for (int k = 0; k < total; k++) {
-    const L2Tmp t = (k < nFlushed) ? mySlots[k] : pend;
-    mm_l2_locus o;
-    o.frag = f; o.cand = candLocal; o.seqId = cand.seqId; o.optimalStart = t.start; o.optimalEnd = t.end;
-    o.meanOptimalPos = (t.start + t.end) / 2; o.sharedSketchSize = t.shared; o.strand = t.strand;
-    l2[base + k] = o;
-  }
+  mm_l2_emit_thread(cIdx, cand, total, nFlushed, mySlots, pend, l1Off, l2, l2Cap, l2First, l2Num, counters);
 }
 
 
@@ -1003,20 +1012,7 @@ k_l2_window(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__
   if (inRun) close_run(votes >= 0 ? 1 : -1);
   int total = nFlushed + (havePend ? 1 : 0);
   if (slotOverflow) { atomicOr(&counters[MM_PC_L2_FLAGS], MM_L2F_SLOTS); total = 0; }
-  unsigned long long base = 0;
-  if (total > 0) {
-    base = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
-    if (base + (unsigned long long)total > l2Cap) { atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); return; }
-  }
-  l2First[c] = (int64_t)base; l2Num[c] = total;
-  const int candLocal = (int)(c - l1Off[f]);
-  for (int k = 0; k < total; k++) {
-    const L2Tmp t = (k < nFlushed) ? mySlots[k] : pend;
-    mm_l2_locus o;
-    o.frag = f; o.cand = candLocal; o.seqId = cand.seqId; o.optimalStart = t.start; o.optimalEnd = t.end;
-    o.meanOptimalPos = (t.start + t.end) / 2; o.sharedSketchSize = t.shared; o.strand = t.strand;
-    l2[base + k] = o;
-  }
+  mm_l2_emit_thread(c, cand, total, nFlushed, mySlots, pend, l1Off, l2, l2Cap, l2First, l2Num, counters);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1049,7 +1045,26 @@ k_l2_window(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__
 __host__ __device__ static inline size_t mm_ww_lds(int s) {
   return (size_t)MM_WW_HEAP * 8 + (size_t)(s + 1) * 8 + (size_t)(s + 2) * sizeof(WinCell) + (size_t)MM_LOCAP0 * sizeof(WinLocus) + (((size_t)s + 15) & ~(size_t)15);
 }
-__device__ __forceinline__ int mm_rl(int v, int l) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(l)); }
+// The end of candidate c for a kernel that gives it one WAVE: the loci rn holds are claimed from the pass's cursor by lane 0 and written
+// 64 at a time, l2First / l2Num say where k_l2_select finds them.  Where they do not fit the buffer, MM_PC_L2_OVERFLOW is raised and
+// nothing is written.
+__device__ __forceinline__ void mm_l2_emit_wave(int c, const mm_l1_candidate& cand, const WinRuns& rn, const int64_t* __restrict__ l1Off, mm_l2_locus* __restrict__ l2,
+                                                unsigned long long l2Cap, int64_t* __restrict__ l2First, int32_t* __restrict__ l2Num,
+                                                unsigned long long* __restrict__ counters, int lane) {
+  const int total = rn.total();
+  unsigned long long at = 0;
+  if (total > 0) {
+    if (lane == 0) at = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
+    at = mm_bcast64_readlane(at, 0);
+    if (at + (unsigned long long)total > l2Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); return; }
+  }
+  if (lane == 0) { l2First[c] = (int64_t)at; l2Num[c] = total; }
+  const int candLocal = (int)(c - l1Off[cand.frag]);
+  for (int k = lane; k < total; k += 64) {
+    const WinLocus t = rn.locus(k);
+    l2[at + k] = mm_l2_record(cand.frag, candLocal, cand.seqId, t.start, t.end, t.shared, t.strand);
+  }
+}
 __global__ void __launch_bounds__(64)
 k_l2_window_wave(int nCand, int s, int segLength, const mm_l1_candidate* __restrict__ l1, const mm_frag_stats* __restrict__ stats, const DFrag* __restrict__ frags,
                  const uint64_t* __restrict__ qHash, const int8_t* __restrict__ qStrand, const uint64_t* __restrict__ skHash, const int8_t* __restrict__ skStrand,
@@ -1140,7 +1155,7 @@ k_l2_window_wave(int nCand, int s, int segLength, const mm_l1_candidate* __restr
         if (W > 0 && mm_win_present(mm_rl(exists ? 1 : 0, l) != 0, mm_rl(entryEnd, l), setupL, posL, W)) continue;   // a record of this step entered with its hash
         if (!mm_win_enter(sm, heap, nHeap, MM_WW_HEAP, rn, setupL, posL, wendL, (uint32_t)mm_rl((int)loc, l), mm_rl(nextW, l), mm_rl(prevSlideW, l))) { hand = true; break; }
         if (W > 0) {
-          const uint64_t hL = ((uint64_t)(uint32_t)mm_rl((int)(uint32_t)(h >> 32), l) << 32) | (uint32_t)mm_rl((int)(uint32_t)h, l);
+          const uint64_t hL = mm_bcast64_readlane(h, l);
           if (cons && h == hL) { writer = lane == l; if (lane > l) { exists = true; entryEnd = wendL; } }
         }
       }
@@ -1158,22 +1173,7 @@ k_l2_window_wave(int nCand, int s, int segLength, const mm_l1_candidate* __restr
     }
     if (!hand) { mm_win_finish(sm, heap, nHeap, rn, lastSlideW); hand = rn.overflow; }
     if (hand) { if (lane == 0) handList[atomicAdd(&counters[MM_PC_L2_WIDE_LEN], 1ull)] = c; continue; }
-    const int total = rn.total();
-    unsigned long long at = 0;
-    if (total > 0) {
-      if (lane == 0) at = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
-      at = ((unsigned long long)(uint32_t)mm_rl((int)(uint32_t)(at >> 32), 0) << 32) | (uint32_t)mm_rl((int)(uint32_t)at, 0);
-      if (at + (unsigned long long)total > l2Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); continue; }
-    }
-    if (lane == 0) { l2First[c] = (int64_t)at; l2Num[c] = total; }
-    const int candLocal = (int)(c - l1Off[f]);
-    for (int k = lane; k < total; k += 64) {
-      const WinLocus t = rn.locus(k);
-      mm_l2_locus o;
-      o.frag = f; o.cand = candLocal; o.seqId = cand.seqId; o.optimalStart = t.start; o.optimalEnd = t.end;
-      o.meanOptimalPos = (t.start + t.end) / 2; o.sharedSketchSize = t.shared; o.strand = t.strand;
-      l2[at + k] = o;
-    }
+    mm_l2_emit_wave(c, cand, rn, l1Off, l2, l2Cap, l2First, l2Num, counters, lane);
   }
 }
 
@@ -1305,22 +1305,7 @@ k_l2_large_wave(int nCand, int s, int segLength, const mm_l1_candidate* __restri
       hand = rn.overflow;
     }
     if (hand) { if (lane == 0) handList[atomicAdd(&counters[MM_PC_L2_LARGE_LEN], 1ull)] = c; continue; }
-    const int total = rn.total();
-    unsigned long long at = 0;
-    if (total > 0) {
-      if (lane == 0) at = atomicAdd(&counters[MM_PC_L2_LOCI], (unsigned long long)total);
-      at = ((unsigned long long)(uint32_t)mm_rl((int)(uint32_t)(at >> 32), 0) << 32) | (uint32_t)mm_rl((int)(uint32_t)at, 0);
-      if (at + (unsigned long long)total > l2Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L2_OVERFLOW], MM_OVERFLOWED); continue; }
-    }
-    if (lane == 0) { l2First[c] = (int64_t)at; l2Num[c] = total; }
-    const int candLocal = (int)(c - l1Off[f]);
-    for (int k = lane; k < total; k += 64) {
-      const WinLocus t = rn.locus(k);
-      mm_l2_locus o;
-      o.frag = f; o.cand = candLocal; o.seqId = cand.seqId; o.optimalStart = t.start; o.optimalEnd = t.end;
-      o.meanOptimalPos = (t.start + t.end) / 2; o.sharedSketchSize = t.shared; o.strand = t.strand;
-      l2[at + k] = o;
-    }
+    mm_l2_emit_wave(c, cand, rn, l1Off, l2, l2Cap, l2First, l2Num, counters, lane);
   }
 }
 

@@ -188,7 +188,7 @@ __device__ __forceinline__ int mm_gather_points(Dst dst, int& done, int rdBase, 
     while (mLong) {
       const int l = (int)__builtin_ctzll(mLong); mLong &= mLong - 1ull;
       const int cL = __shfl(c, l), myL = __shfl(my, l);
-      const uint64_t srcL = ((uint64_t)(uint32_t)__shfl((int)(src >> 32), l) << 32) | (uint32_t)__shfl((int)(uint32_t)src, l);
+      const uint64_t srcL = mm_bcast64_shfl(src, l);
       for (int j = lane; j < cL; j += 64) one(ptKeys[srcL + j], myL + j, (rdBase + rd) * 64 + l);
     }
     done += mm_wave_sum(c);
@@ -392,7 +392,7 @@ __device__ __noinline__ int mm_fused_long_runs(uint64_t mLong, int c, int my, ui
   while (mLong) {
     const int l = (int)__builtin_ctzll(mLong); mLong &= mLong - 1ull;
     const int cL = __shfl(c, l), myL = __shfl(my, l);
-    const uint64_t srcL = ((uint64_t)(uint32_t)__shfl((int)(src >> 32), l) << 32) | (uint32_t)__shfl((int)(uint32_t)src, l);
+    const uint64_t srcL = mm_bcast64_shfl(src, l);
     for (int j = 2 + lane; j < cL; j += 64) {
       uint64_t key = ptKeys[srcL + j];
       const int seqId = (int)(key >> 33);
@@ -412,6 +412,27 @@ __device__ __noinline__ int mm_fused_long_runs(uint64_t mLong, int c, int my, ui
 #define MM_MID_MAXPTS 16384         // and interval points of a fragment it takes (8 192 intervals: its 16-bit bin counters cannot overflow)
 #define MM_L1_REGIONS 64            // L1 output cursors: a same-address atomic costs ~10 ns, so fragments spread over 64 of them
 #define MM_L1_CURSOR_STRIDE 32      // u64 words between cursors (256 bytes)
+// a joined run of fragment f as the L1 candidate the L2 stage reads
+__device__ __forceinline__ void mm_store_candidate(mm_l1_candidate* __restrict__ l1, long long at, int f, const L1Run& x) {
+  mm_l1_candidate o; o.frag = f; o.seqId = x.seq; o.rangeStartPos = x.start; o.rangeEndPos = x.end; o.intersectionSize = x.isize;
+  l1[at] = o;
+}
+// The end of a fragment a lookup kernel finishes itself: its nOut candidates runs[0..nOut) go to region f mod 64 of the L1 buffer, filled
+// from its own cursor (k_l1_compact closes the gaps afterwards).  Where they no longer fit, MM_PC_L1_OVERFLOW is raised and nOut becomes 0.
+// Returns the position of the first one in the buffer (what l1Off[f] takes).
+__device__ __forceinline__ unsigned long long mm_region_emit(int f, int& nOut, const L1Run* runs, mm_l1_candidate* __restrict__ l1, unsigned long long regionCap,
+                                                             unsigned long long* __restrict__ l1Cursors, unsigned long long* __restrict__ counters, int lane) {
+  const int region = f & (MM_L1_REGIONS - 1);
+  unsigned long long at = 0;
+  if (nOut > 0) {
+    if (lane == 0) at = atomicAdd(&l1Cursors[(size_t)region * MM_L1_CURSOR_STRIDE], (unsigned long long)nOut);
+    at = mm_bcast64_shfl(at, 0);
+    if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
+  }
+  const unsigned long long base = (unsigned long long)region * regionCap + at;
+  for (int i = lane; i < nOut; i += 64) mm_store_candidate(l1, (long long)(base + i), f, runs[i]);
+  return base;
+}
 template <int MAXPTS, bool TAGS>
 __global__ void __launch_bounds__(MM_LOOKUP_WPB * 64, MAXPTS <= 128 ? 8 : MAXPTS <= 256 ? 6 : 5)
 k_lookup_l1(int nFrags, int s, const DFrag* __restrict__ frags,
@@ -569,20 +590,7 @@ k_lookup_l1(int nFrags, int s, const DFrag* __restrict__ frags,
   }
   }  // live
   if (live && nOut >= 0) {                                         // fast path complete: emit the candidates
-    // region f mod 64 of the L1 buffer, filled from its own cursor; k_l1_compact closes the gaps afterwards
-    const int region = f & (MM_L1_REGIONS - 1);
-    unsigned long long at = 0;
-    if (nOut > 0) {
-      if (lane == 0) at = atomicAdd(&l1Cursors[(size_t)region * MM_L1_CURSOR_STRIDE], (unsigned long long)nOut);
-      at = ((unsigned long long)(uint32_t)__shfl((int)(at >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)at, 0);
-      if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
-    }
-    const unsigned long long base = (unsigned long long)region * regionCap + at;
-    for (int i = lane; i < nOut; i += 64) {
-      const L1Run x = sc.run[i];
-      mm_l1_candidate o; o.frag = f; o.seqId = x.seq; o.rangeStartPos = x.start; o.rangeEndPos = x.end; o.intersectionSize = x.isize;
-      l1[base + i] = o;
-    }
+    const unsigned long long base = mm_region_emit(f, nOut, sc.run, l1, regionCap, l1Cursors, counters, lane);
     if (lane == 0) {
       mm_frag_stats st;
       st.rawSketchSize = cnt; st.sketchSize = outIdx; st.maxHash = lastHash; st.nPoints = nValid; st.nL1 = nOut; stats[f] = st;
@@ -728,6 +736,26 @@ __device__ __noinline__ int mm_mid_sort16(FuseScratchT<MM_MID_MAXKEEP>& sc, int 
   mm_wave_bitonic<16>(k, lane);
   return mm_l1_fused<16>(k, sc, sketchSizeQ, minHits, hg, cutoffs, nCutoffs, sParam, segLength, lane);
 }
+// one tier of the register sorters: the padded LDS list sc.a[0 .. 64 R), R points per lane, sorted and swept by the fused L1
+template <int R, class FuseScratch>
+__device__ __forceinline__ int mm_sort_fuse_tier(FuseScratch& sc, int sketchSizeQ, int minHits, int hg, const int32_t* __restrict__ cutoffs, int nCutoffs,
+                                                 int sParam, int segLength, int lane) {
+  uint64_t k[R];
+#pragma unroll
+  for (int e = 0; e < R; e++) k[e] = sc.a[lane * R + e];
+  mm_wave_bitonic<R>(k, lane);
+  return mm_l1_fused<R>(k, sc, sketchSizeQ, minHits, hg, cutoffs, nCutoffs, sParam, segLength, lane);
+}
+// the ladder of the register sorters for K <= 512 points at the head of sc.a, padded to a tier: the tier that holds them.  (The sixteen-per-lane
+// tier stays with its kernel: mm_mid_sort16's call here, the same steps in line in k_lookup_groups.)
+template <class FuseScratch>
+__device__ __forceinline__ int mm_sort_fuse(FuseScratch& sc, int K, int sketchSizeQ, int minHits, int hg, const int32_t* __restrict__ cutoffs, int nCutoffs,
+                                            int sParam, int segLength, int lane) {
+  if (K <= 64) return mm_sort_fuse_tier<1>(sc, sketchSizeQ, minHits, hg, cutoffs, nCutoffs, sParam, segLength, lane);
+  if (K <= 128) return mm_sort_fuse_tier<2>(sc, sketchSizeQ, minHits, hg, cutoffs, nCutoffs, sParam, segLength, lane);
+  if (K <= 256) return mm_sort_fuse_tier<4>(sc, sketchSizeQ, minHits, hg, cutoffs, nCutoffs, sParam, segLength, lane);
+  return mm_sort_fuse_tier<8>(sc, sketchSizeQ, minHits, hg, cutoffs, nCutoffs, sParam, segLength, lane);
+}
 
 template <bool TAGS>
 __global__ void __launch_bounds__(64)
@@ -857,17 +885,7 @@ k_lookup_mid(int nList, const unsigned long long* __restrict__ nDev, const int32
         for (int j = K + lane; j < padTo; j += 64) sc.a[j] = MM_EMPTY;
         __threadfence_block();
         if (K > 512) nOut = mm_mid_sort16(sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
-        else if (K <= 64) { uint64_t k[1] = {sc.a[lane]}; mm_wave_bitonic<1>(k, lane); nOut = mm_l1_fused<1>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane); }
-        else if (K <= 128) { uint64_t k[2] = {sc.a[lane * 2], sc.a[lane * 2 + 1]}; mm_wave_bitonic<2>(k, lane); nOut = mm_l1_fused<2>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane); }
-        else if (K <= 256) {
-          uint64_t k[4] = {sc.a[lane * 4], sc.a[lane * 4 + 1], sc.a[lane * 4 + 2], sc.a[lane * 4 + 3]};
-          mm_wave_bitonic<4>(k, lane); nOut = mm_l1_fused<4>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
-        } else {
-          uint64_t k[8];
-#pragma unroll
-          for (int e = 0; e < 8; e++) k[e] = sc.a[lane * 8 + e];
-          mm_wave_bitonic<8>(k, lane); nOut = mm_l1_fused<8>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
-        }
+        else nOut = mm_sort_fuse(sc, K, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
       }
     }
     if (nOut < 0) {                                                // to the HBM path after all, as k_lookup_l1 queues a fragment
@@ -880,19 +898,7 @@ k_lookup_mid(int nList, const unsigned long long* __restrict__ nDev, const int32
         if (ok) bigList[atomicAdd(&counters[MM_PC_BIG_LEN], 1ull)] = f;
       }
     } else {
-      const int region = f & (MM_L1_REGIONS - 1);
-      unsigned long long at = 0;
-      if (nOut > 0) {
-        if (lane == 0) at = atomicAdd(&l1Cursors[(size_t)region * MM_L1_CURSOR_STRIDE], (unsigned long long)nOut);
-        at = ((unsigned long long)(uint32_t)__shfl((int)(at >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)at, 0);
-        if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
-      }
-      const unsigned long long base = (unsigned long long)region * regionCap + at;
-      for (int i = lane; i < nOut; i += 64) {
-        const L1Run x = sc.run[i];
-        mm_l1_candidate o; o.frag = f; o.seqId = x.seq; o.rangeStartPos = x.start; o.rangeEndPos = x.end; o.intersectionSize = x.isize;
-        l1[base + i] = o;
-      }
+      const unsigned long long base = mm_region_emit(f, nOut, sc.run, l1, regionCap, l1Cursors, counters, lane);
       if (lane == 0) {
         mm_frag_stats st = st0;
         st.nPoints = nValid; st.nL1 = nOut; stats[f] = st;
@@ -1043,17 +1049,7 @@ k_lookup_groups(const unsigned long long* __restrict__ nDev, const int32_t* __re
           for (int e = 0; e < 16; e++) k[e] = sc.a[lane * 16 + e];
           mm_wave_bitonic<16>(k, lane); nOut = mm_l1_fused<16>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
         }
-        else if (K <= 64) { uint64_t k[1] = {sc.a[lane]}; mm_wave_bitonic<1>(k, lane); nOut = mm_l1_fused<1>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane); }
-        else if (K <= 128) { uint64_t k[2] = {sc.a[lane * 2], sc.a[lane * 2 + 1]}; mm_wave_bitonic<2>(k, lane); nOut = mm_l1_fused<2>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane); }
-        else if (K <= 256) {
-          uint64_t k[4] = {sc.a[lane * 4], sc.a[lane * 4 + 1], sc.a[lane * 4 + 2], sc.a[lane * 4 + 3]};
-          mm_wave_bitonic<4>(k, lane); nOut = mm_l1_fused<4>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
-        } else {
-          uint64_t k[8];
-#pragma unroll
-          for (int e = 0; e < 8; e++) k[e] = sc.a[lane * 8 + e];
-          mm_wave_bitonic<8>(k, lane); nOut = mm_l1_fused<8>(k, sc, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
-        }
+        else nOut = mm_sort_fuse(sc, K, outIdx, minHits, fl.hg, cutoffs, nCutoffs, s, segLength, lane);
         if (nOut < 0 || total + nOut > MM_GRP_MAXCAND) { hand = true; break; }
         for (int i = lane; i < nOut; i += 64) out[total + i] = sc.run[i];
         total += nOut;
@@ -1064,19 +1060,7 @@ k_lookup_groups(const unsigned long long* __restrict__ nDev, const int32_t* __re
       if (lane == 0) handList[atomicAdd(&counters[MM_PC_GRP_LEN], 1ull)] = f;
     } else {
       int nOut = total;
-      const int region = f & (MM_L1_REGIONS - 1);
-      unsigned long long at = 0;
-      if (nOut > 0) {
-        if (lane == 0) at = atomicAdd(&l1Cursors[(size_t)region * MM_L1_CURSOR_STRIDE], (unsigned long long)nOut);
-        at = ((unsigned long long)(uint32_t)__shfl((int)(at >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)at, 0);
-        if (at + (unsigned long long)nOut > regionCap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); nOut = 0; }
-      }
-      const unsigned long long base = (unsigned long long)region * regionCap + at;
-      for (int i = lane; i < nOut; i += 64) {
-        const L1Run x = out[i];
-        mm_l1_candidate o; o.frag = f; o.seqId = x.seq; o.rangeStartPos = x.start; o.rangeEndPos = x.end; o.intersectionSize = x.isize;
-        l1[base + i] = o;
-      }
+      const unsigned long long base = mm_region_emit(f, nOut, out, l1, regionCap, l1Cursors, counters, lane);
       if (lane == 0) {
         mm_frag_stats st = st0;
         st.nPoints = nValid; st.nL1 = nOut; stats[f] = st;
@@ -1254,6 +1238,72 @@ __global__ void k_classify_sort(int nList, const unsigned long long* __restrict_
 // one-thread-per-fragment kernel costs 50-170 ns per fragment (profiles/r03j_repeat_probe.txt).
 // ---------------------------------------------------------------------------------------------
 #define MM_STREAM_BUF 64            // candidates kept in LDS by the counting pass (more: the writing pass runs again)
+// What k_l1_stream and k_l1_stream_groups share, all in line.  L1Stream: the wave's view of a sorted point list, over an extent [b, e) of it
+// (the whole list: 0, nPts) -- nothing outside the extent is a neighbour, and the carried overlap count starts at 0 at b.
+struct L1Stream {
+  const uint64_t* p; int lane;
+  // one chunk of 64 points of the extent: key, overlap count after the point, whether it ends a position group
+  __device__ __forceinline__ void chunk(int b, int e, int i0, int carry, uint64_t& k, int& run, bool& gLast, bool& mixed, int& sum) const {
+    const int idx = i0 + lane;
+    const bool valid = idx < e;
+    k = valid ? p[idx] : MM_EMPTY;
+    const uint64_t prv = (valid && idx > b) ? p[idx - 1] : MM_EMPTY;
+    const uint64_t nxt = (idx + 1 < e) ? p[idx + 1] : MM_EMPTY;
+    mixed = valid && prv != MM_EMPTY && (uint32_t)(prv >> 1) == (uint32_t)(k >> 1) && (prv >> 33) != (k >> 33);
+    const int delta = valid ? ((k & 1ull) ? 1 : -1) : 0;
+    run = carry + mm_wave_excl_scan(delta) + delta;
+    gLast = valid && (nxt == MM_EMPTY || (uint32_t)(nxt >> 1) != (uint32_t)(k >> 1));
+    sum = mm_wave_sum(delta);
+  }
+  // ---- pass 1 over the extent: best overlap count, number of groups, the mixed-group test ----
+  __device__ __forceinline__ void pass1(int b, int e, int& best, int& G, bool& anyMixed) const {
+    int carry = 0;
+    for (int i0 = b; i0 < e; i0 += 64) {
+      uint64_t k; int run, sum; bool gLast, mixed;
+      chunk(b, e, i0, carry, k, run, gLast, mixed, sum);
+      if (gLast && run > best) best = run;
+      G += (int)__popcll(__ballot(gLast));
+      anyMixed = anyMixed || __ballot(mixed) != 0;
+      carry += sum;
+    }
+    best = mm_wave_max(best);
+  }
+};
+// computeMap.hpp:984-998 for a call whose pass 1 found `best` over G groups: false when the call yields nothing; under --hg minimumHits is
+// raised to the cutoff of the best count
+__device__ __forceinline__ bool mm_l1_raise_min_hits(int best, int G, int S, int hg, int sParam, const int32_t* __restrict__ cutoffs, int nCutoffs, int& minHits) {
+  bool go = G > 0;
+  if (go && hg) {
+    if (best < minHits) go = false;
+    else {
+      const double div = (double)sParam / 1000.0 > 1.0 ? (double)sParam / 1000.0 : 1.0;
+      int ci = (int)((double)(best < S ? best : S) / div);
+      if (ci >= nCutoffs) ci = nCutoffs - 1;
+      const int cut = cutoffs[ci];
+      minHits = cut > minHits ? cut : minHits;
+    }
+  }
+  return go;
+}
+// the pending-candidate joiner of one pass over a fragment (L1Emit::run inside one computeL1CandidateRegions call): runs of one contig closer
+// than segLength become one candidate; the counting pass keeps the first MM_STREAM_BUF in LDS, the writing pass stores from `base` on
+struct L1Join {
+  mm_l1_candidate* l1; L1Run* buf; long long base; int f, lane, segLength; bool write;
+  int count = 0; bool have = false; L1Run pend{0, 0, 0, 0};
+  __device__ __forceinline__ void flush() {
+    if (have) {
+      if (lane == 0) {
+        if (write) mm_store_candidate(l1, base + count, f, pend);
+        else if (count < MM_STREAM_BUF) buf[count] = pend;
+      }
+      count++; have = false;
+    }
+  }
+  __device__ __forceinline__ void emit(int seq, int start, int end, int isize) {
+    if (have && seq == pend.seq && !(start > pend.end + segLength)) { pend.end = end; pend.isize = isize > pend.isize ? isize : pend.isize; }
+    else { flush(); pend.seq = seq; pend.start = start; pend.end = end; pend.isize = isize; have = true; }
+  }
+};
 __global__ void __launch_bounds__(256)
 k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restrict__ ptOff, const uint64_t* __restrict__ pts,
             mm_frag_stats* __restrict__ stats, const int32_t* __restrict__ minHitsTab, const int32_t* __restrict__ cutoffs, int nCutoffs,
@@ -1267,48 +1317,12 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
   auto one = [&](const int f) {
   const int nPts = ptKept[f], S = stats[f].sketchSize;
   if (nPts <= 0 || S <= 0) { if (lane == 0) { stats[f].nL1 = 0; l1Off[f] = 0; } return; }
-  const uint64_t* p = pts + ptOff[2 * f];
+  const L1Stream st{pts + ptOff[2 * f], lane};
   int minHits = minHitsTab[S];
-
-  // one chunk of 64 points: key, overlap count after the point, whether it ends a position group
-  auto chunk = [&](int i0, int carry, uint64_t& k, int& run, bool& gLast, bool& mixed, int& sum) {
-    const int idx = i0 + lane;
-    const bool valid = idx < nPts;
-    k = valid ? p[idx] : MM_EMPTY;
-    const uint64_t prv = (valid && idx > 0) ? p[idx - 1] : MM_EMPTY;
-    const uint64_t nxt = (idx + 1 < nPts) ? p[idx + 1] : MM_EMPTY;
-    mixed = valid && prv != MM_EMPTY && (uint32_t)(prv >> 1) == (uint32_t)(k >> 1) && (prv >> 33) != (k >> 33);
-    const int delta = valid ? ((k & 1ull) ? 1 : -1) : 0;
-    run = carry + mm_wave_excl_scan(delta) + delta;
-    gLast = valid && (nxt == MM_EMPTY || (uint32_t)(nxt >> 1) != (uint32_t)(k >> 1));
-    sum = mm_wave_sum(delta);
-  };
-
-  // ---- pass 1: best overlap count, number of groups, the mixed-group test ----
+  // pass 1 once, over the whole list
   int best = 0, G = 0; bool anyMixed = false;
-  {
-    int carry = 0;
-    for (int i0 = 0; i0 < nPts; i0 += 64) {
-      uint64_t k; int run, sum; bool gLast, mixed;
-      chunk(i0, carry, k, run, gLast, mixed, sum);
-      if (gLast && run > best) best = run;
-      G += (int)__popcll(__ballot(gLast));
-      anyMixed = anyMixed || __ballot(mixed) != 0;
-      carry += sum;
-    }
-    best = mm_wave_max(best);
-  }
-  bool go = G > 0;
-  if (go && hg) {                                                 // computeMap.hpp:984-998
-    if (best < minHits) go = false;
-    else {
-      const double div = (double)sParam / 1000.0 > 1.0 ? (double)sParam / 1000.0 : 1.0;
-      int ci = (int)((double)(best < S ? best : S) / div);
-      if (ci >= nCutoffs) ci = nCutoffs - 1;
-      const int cut = cutoffs[ci];
-      minHits = cut > minHits ? cut : minHits;
-    }
-  }
+  st.pass1(0, nPts, best, G, anyMixed);
+  const bool go = mm_l1_raise_min_hits(best, G, S, hg, sParam, cutoffs, nCutoffs, minHits);
   if (anyMixed || minHits <= 0) {                                 // the literal kernel's business
     if (lane == 0) lit[atomicAdd(litCount, 1u)] = f;
     return;
@@ -1318,28 +1332,14 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
   int total = 0; long long base = 0;
   for (int pass = 0; pass < 2; pass++) {
     const bool write = pass == 1;
-    int count = 0;
-    bool have = false; L1Run pend{0, 0, 0, 0};
-    auto flush = [&]() {
-      if (have) {
-        if (lane == 0) {
-          if (write) { mm_l1_candidate o; o.frag = f; o.seqId = pend.seq; o.rangeStartPos = pend.start; o.rangeEndPos = pend.end; o.intersectionSize = pend.isize; l1[base + count] = o; }
-          else if (count < MM_STREAM_BUF) buf[count] = pend;
-        }
-        count++; have = false;
-      }
-    };
-    auto emit = [&](int seq, int start, int end, int isize) {      // L1Emit::run for a single reference group
-      if (have && seq == pend.seq && !(start > pend.end + segLength)) { pend.end = end; pend.isize = isize > pend.isize ? isize : pend.isize; }
-      else { flush(); pend.seq = seq; pend.start = start; pend.end = end; pend.isize = isize; have = true; }
-    };
+    L1Join jn{l1, buf, base, f, lane, segLength, write};
     if (go) {
       bool inRun = false; int rSeq = 0, rStart = 0, rEnd = 0, rSize = 0;
       int carry = 0, gBase = 0;
       bool prevFlagC = false; int prevSeqC = 0;                   // the last group of the chunks so far: flagged?, its contig
       for (int i0 = 0; i0 < nPts; i0 += 64) {
         uint64_t k; int run, sum; bool gLast, mixed;
-        chunk(i0, carry, k, run, gLast, mixed, sum);
+        st.chunk(0, nPts, i0, carry, k, run, gLast, mixed, sum);
         carry += sum;
         const uint64_t GM = __ballot(gLast);
         if (!GM) continue;
@@ -1376,9 +1376,9 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
             const int bpos = (int)__builtin_ctzll(ev);
             ev &= ev - 1ull;
             if (inRun) extend(segLo, bpos);
-            if ((breakM >> bpos) & 1ull) { if (inRun) emit(rSeq, rStart, rEnd, rSize); inRun = false; }
+            if ((breakM >> bpos) & 1ull) { if (inRun) jn.emit(rSeq, rStart, rEnd, rSize); inRun = false; }
             else {
-              if (inRun) emit(rSeq, rStart, rEnd, rSize);
+              if (inRun) jn.emit(rSeq, rStart, rEnd, rSize);
               rSeq = __builtin_amdgcn_readlane(gseq, bpos); rStart = __builtin_amdgcn_readlane(gpos, bpos); rEnd = rStart;
               rSize = __builtin_amdgcn_readlane(run, bpos); inRun = true;
             }
@@ -1388,20 +1388,20 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
         }
         prevFlagC = lastFlag; prevSeqC = lastSeq;
       }
-      if (inRun) emit(rSeq, rStart, rEnd, rSize);
-      flush();
+      if (inRun) jn.emit(rSeq, rStart, rEnd, rSize);
+      jn.flush();
     }
     if (!write) {
-      total = count;
+      total = jn.count;
       if (total > 0) {
         long long b0 = 0;
         if (lane == 0) b0 = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)total);
-        base = ((long long)__builtin_amdgcn_readfirstlane((int)(b0 >> 32)) << 32) | (unsigned int)__builtin_amdgcn_readfirstlane((int)b0);
+        base = (long long)mm_bcast64_readfirstlane((uint64_t)b0);
         if ((unsigned long long)base + (unsigned long long)total > l1Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); total = 0; }
       }
       if (total > 0 && total <= MM_STREAM_BUF) {                   // the counting pass kept them all
         __threadfence_block();
-        if (lane < total) { const L1Run r = buf[lane]; mm_l1_candidate o; o.frag = f; o.seqId = r.seq; o.rangeStartPos = r.start; o.rangeEndPos = r.end; o.intersectionSize = r.isize; l1[base + lane] = o; }
+        if (lane < total) mm_store_candidate(l1, base + lane, f, buf[lane]);
         break;
       }
       if (total == 0) break;
@@ -1420,8 +1420,10 @@ k_l1_stream(int nList, const int32_t* __restrict__ list, const int64_t* __restri
 // never flagged, the carried count starting at 0, no neighbour across its ends, runs joined inside it only.  The candidates of all
 // extents are counted together, claimed once and written in extent order.  A position group across two contigs INSIDE an extent (one
 // shared by the last point of an extent and the first of the next is none: those are two calls) or minimumHits <= 0 leaves the whole
-// fragment to k_l1_sweep.  A kernel of its own: sharing the body with k_l1_stream changed that kernel's code (register allocation,
-// 23 instructions more), and the plain path is to stay as it is.
+// fragment to k_l1_sweep.  A kernel of its own, built from what k_l1_stream is built from: the chunk and pass 1 over an extent (L1Stream; the
+// plain kernel's extent is 0, nPts), the minimum-hits raise, the pending-candidate joiner (L1Join) and the candidate store.  The fold of an
+// extent and the claim-and-write tail of the counting pass stand in both kernels: as functions they raise the VGPR count of k_l1_stream,
+// which sits at the SGPR limit, and that kernel keeps its registers.  A change to either copy goes into the other.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 k_l1_stream_groups(int nList, const int32_t* __restrict__ list, const int64_t* __restrict__ ptOff, const uint64_t* __restrict__ pts,
@@ -1437,50 +1439,8 @@ k_l1_stream_groups(int nList, const int32_t* __restrict__ list, const int64_t* _
   auto one = [&](const int f) {
   const int nPts = ptKept[f], S = stats[f].sketchSize;
   if (nPts <= 0 || S <= 0) { if (lane == 0) { stats[f].nL1 = 0; l1Off[f] = 0; } return; }
-  const uint64_t* p = pts + ptOff[2 * f];
+  const L1Stream st{pts + ptOff[2 * f], lane};
   int minHits = minHitsTab[S];
-
-  // one chunk of 64 points of the extent [b, e): key, overlap count after the point, whether it ends a position group
-  auto chunk = [&](int b, int e, int i0, int carry, uint64_t& k, int& run, bool& gLast, bool& mixed, int& sum) {
-    const int idx = i0 + lane;
-    const bool valid = idx < e;
-    k = valid ? p[idx] : MM_EMPTY;
-    const uint64_t prv = (valid && idx > b) ? p[idx - 1] : MM_EMPTY;
-    const uint64_t nxt = (idx + 1 < e) ? p[idx + 1] : MM_EMPTY;
-    mixed = valid && prv != MM_EMPTY && (uint32_t)(prv >> 1) == (uint32_t)(k >> 1) && (prv >> 33) != (k >> 33);
-    const int delta = valid ? ((k & 1ull) ? 1 : -1) : 0;
-    run = carry + mm_wave_excl_scan(delta) + delta;
-    gLast = valid && (nxt == MM_EMPTY || (uint32_t)(nxt >> 1) != (uint32_t)(k >> 1));
-    sum = mm_wave_sum(delta);
-  };
-
-  // ---- pass 1 over [b, e): best overlap count, number of groups, the mixed-group test ----
-  auto pass1 = [&](int b, int e, int& best, int& G, bool& anyMixed) {
-    int carry = 0;
-    for (int i0 = b; i0 < e; i0 += 64) {
-      uint64_t k; int run, sum; bool gLast, mixed;
-      chunk(b, e, i0, carry, k, run, gLast, mixed, sum);
-      if (gLast && run > best) best = run;
-      G += (int)__popcll(__ballot(gLast));
-      anyMixed = anyMixed || __ballot(mixed) != 0;
-      carry += sum;
-    }
-    best = mm_wave_max(best);
-  };
-  auto hgRule = [&](int best, int G, int& mh) {                   // computeMap.hpp:984-998
-    bool go = G > 0;
-    if (go && hg) {
-      if (best < mh) go = false;
-      else {
-        const double div = (double)sParam / 1000.0 > 1.0 ? (double)sParam / 1000.0 : 1.0;
-        int ci = (int)((double)(best < S ? best : S) / div);
-        if (ci >= nCutoffs) ci = nCutoffs - 1;
-        const int cut = cutoffs[ci];
-        mh = cut > mh ? cut : mh;
-      }
-    }
-    return go;
-  };
   auto toLiteral = [&]() { if (lane == 0) lit[atomicAdd(litCount, 1u)] = f; };   // the literal kernel's business
 
   if (minHits <= 0) { toLiteral(); return; }
@@ -1489,21 +1449,7 @@ k_l1_stream_groups(int nList, const int32_t* __restrict__ list, const int64_t* _
   int total = 0; long long base = 0;
   for (int pass = 0; pass < 2; pass++) {
     const bool write = pass == 1;
-    int count = 0;
-    bool have = false; L1Run pend{0, 0, 0, 0};
-    auto flush = [&]() {
-      if (have) {
-        if (lane == 0) {
-          if (write) { mm_l1_candidate o; o.frag = f; o.seqId = pend.seq; o.rangeStartPos = pend.start; o.rangeEndPos = pend.end; o.intersectionSize = pend.isize; l1[base + count] = o; }
-          else if (count < MM_STREAM_BUF) buf[count] = pend;
-        }
-        count++; have = false;
-      }
-    };
-    auto emit = [&](int seq, int start, int end, int isize) {      // L1Emit::run inside one reference group
-      if (have && seq == pend.seq && !(start > pend.end + segLength)) { pend.end = end; pend.isize = isize > pend.isize ? isize : pend.isize; }
-      else { flush(); pend.seq = seq; pend.start = start; pend.end = end; pend.isize = isize; have = true; }
-    };
+    L1Join jn{l1, buf, base, f, lane, segLength, write};
     // the extent [b, e) with its G groups and its minimumHits; ends with the pending candidate flushed (L1Emit::run's firstOfGroup)
     auto pass2 = [&](int b, int e, int G, int minHits) {
       bool inRun = false; int rSeq = 0, rStart = 0, rEnd = 0, rSize = 0;
@@ -1511,7 +1457,7 @@ k_l1_stream_groups(int nList, const int32_t* __restrict__ list, const int64_t* _
       bool prevFlagC = false; int prevSeqC = 0;                   // the last group of the chunks so far: flagged?, its contig
       for (int i0 = b; i0 < e; i0 += 64) {
         uint64_t k; int run, sum; bool gLast, mixed;
-        chunk(b, e, i0, carry, k, run, gLast, mixed, sum);
+        st.chunk(b, e, i0, carry, k, run, gLast, mixed, sum);
         carry += sum;
         const uint64_t GM = __ballot(gLast);
         if (!GM) continue;
@@ -1548,9 +1494,9 @@ k_l1_stream_groups(int nList, const int32_t* __restrict__ list, const int64_t* _
             const int bpos = (int)__builtin_ctzll(ev);
             ev &= ev - 1ull;
             if (inRun) extend(segLo, bpos);
-            if ((breakM >> bpos) & 1ull) { if (inRun) emit(rSeq, rStart, rEnd, rSize); inRun = false; }
+            if ((breakM >> bpos) & 1ull) { if (inRun) jn.emit(rSeq, rStart, rEnd, rSize); inRun = false; }
             else {
-              if (inRun) emit(rSeq, rStart, rEnd, rSize);
+              if (inRun) jn.emit(rSeq, rStart, rEnd, rSize);
               rSeq = __builtin_amdgcn_readlane(gseq, bpos); rStart = __builtin_amdgcn_readlane(gpos, bpos); rEnd = rStart;
               rSize = __builtin_amdgcn_readlane(run, bpos); inRun = true;
             }
@@ -1560,38 +1506,38 @@ k_l1_stream_groups(int nList, const int32_t* __restrict__ list, const int64_t* _
         }
         prevFlagC = lastFlag; prevSeqC = lastSeq;
       }
-      if (inRun) emit(rSeq, rStart, rEnd, rSize);
-      flush();
+      if (inRun) jn.emit(rSeq, rStart, rEnd, rSize);
+      jn.flush();
     };
     {
       for (int b = 0; b < nPts;) {
         // the extent's end: the first point behind b whose contig is of another group
-        const int g0 = refGroup[(int)(p[b] >> 33)];
+        const int g0 = refGroup[(int)(st.p[b] >> 33)];
         int e = nPts;
         for (int i0 = b; i0 < nPts; i0 += 64) {
           const int idx = i0 + lane;
-          const uint64_t D = __ballot(idx < nPts && refGroup[(int)(p[idx < nPts ? idx : b] >> 33)] != g0);
+          const uint64_t D = __ballot(idx < nPts && refGroup[(int)(st.p[idx < nPts ? idx : b] >> 33)] != g0);
           if (D) { e = i0 + (int)__builtin_ctzll(D); break; }
         }
         int bestE = 0, GE = 0; bool mixedE = false;
-        pass1(b, e, bestE, GE, mixedE);
+        st.pass1(b, e, bestE, GE, mixedE);
         if (mixedE) { toLiteral(); return; }                      // (found by the counting pass: nothing of the fragment is out yet)
         int mh = minHits;
-        if (hgRule(bestE, GE, mh)) pass2(b, e, GE, mh);
+        if (mm_l1_raise_min_hits(bestE, GE, S, hg, sParam, cutoffs, nCutoffs, mh)) pass2(b, e, GE, mh);
         b = e;
       }
     }
     if (!write) {
-      total = count;
+      total = jn.count;
       if (total > 0) {
         long long b0 = 0;
         if (lane == 0) b0 = (long long)atomicAdd(&counters[MM_PC_L1_CAND], (unsigned long long)total);
-        base = ((long long)__builtin_amdgcn_readfirstlane((int)(b0 >> 32)) << 32) | (unsigned int)__builtin_amdgcn_readfirstlane((int)b0);
+        base = (long long)mm_bcast64_readfirstlane((uint64_t)b0);
         if ((unsigned long long)base + (unsigned long long)total > l1Cap) { if (lane == 0) atomicOr(&counters[MM_PC_L1_OVERFLOW], MM_OVERFLOWED); total = 0; }
       }
       if (total > 0 && total <= MM_STREAM_BUF) {                   // the counting pass kept them all
         __threadfence_block();
-        if (lane < total) { const L1Run r = buf[lane]; mm_l1_candidate o; o.frag = f; o.seqId = r.seq; o.rangeStartPos = r.start; o.rangeEndPos = r.end; o.intersectionSize = r.isize; l1[base + lane] = o; }
+        if (lane < total) mm_store_candidate(l1, base + lane, f, buf[lane]);
         break;
       }
       if (total == 0) break;

@@ -1,6 +1,7 @@
 """Helpers of tests/test_gpu_large_wave.py: the oracle per fragment with buffers large enough for long segments, the figures of a
-candidate's slice of the index as k_l2_extents cuts it, and one mapping run of a batch on a fresh context with a value of
-MM_OPT_L2_LARGE_WAVE."""
+candidate's slice of the index as k_l2_extents cuts it, one mapping run of a batch on a fresh context with a value of
+MM_OPT_L2_LARGE_WAVE, and the "loci8" batch that outgrows the locus buffer behind either wave kernel (tests/test_gpu_window_wave.py
+uses it too)."""
 import ctypes as C
 
 import numpy as np
@@ -21,10 +22,39 @@ def fragments_of(read_len, L):
     return fr
 
 
-def arrayed(seed, unit, copies, div):
-    """tests/test_gpu_steady.py's arrayed(): a tandem array of the unit between random flanks of 3 kbp; div 0: exact copies, which tie in L2"""
-    parts = [unit if div == 0 else U.mutate(unit, seed * 17 + i, div) for i in range(copies)]
-    return np.concatenate([U.random_dna(seed + 1, 3000)] + parts + [U.random_dna(seed + 2, 3000)])
+arrayed = U.arrayed                    # a tandem array of the unit between random flanks of 3 kbp; div 0: exact copies, which tie in L2
+
+
+# ---- the locus buffer behind a wave kernel: tests/test_gpu_map.py's eight-copy "loci8" index (k 16, segLength 1 000, pi 0.95) at its s = 32
+LOCI8_K, LOCI8_L, LOCI8_PI = 16, 1000, 0.95
+
+
+def loci8_reads(n):
+    return U.unit_reads(U.random_dna(9052, 1300), 9056, n, rl=LOCI8_L)
+
+
+def loci8_pass(reads, flags, set_option, s=32):
+    """the batch on a fresh context with the kernel timers on, the option set by set_option(ctx), mapped TWICE: everything the first pass
+    leaves, (L1, L2) counts, loci per candidate, the context's two (candidates, literal) queries -- and `l2_brackets`, the MM_K_L2 timer
+    brackets of the first and of the second pass.  mm_launch_l2_window closes one bracket per kernel launch of an attempt and keeps the
+    grown l2Cap in the context, so the first pass has more of them than the second exactly when it had to repeat an attempt"""
+    import gpucheck
+    from mashmap_amd import capi
+    ua, ub = U.random_dna(9051, 1100), U.random_dna(9052, 1300)
+    ctx = capi.Context(k=LOCI8_K, segLength=LOCI8_L, sketchSize=s, flags=capi.MM_FLAG_HG_FILTER | flags)
+    ctx.index_build([U.random_dna(9001, 500000)[:200000], arrayed(9053, ua, 6, 0.03), arrayed(9054, ub, 8, 0)], kmerPct=0.0); ctx.set_tables_default(LOCI8_PI)
+    set_option(ctx)
+    ctx.reads_upload(reads); ctx.synchronize(); ctx.profile(True); ctx.profile_read(True)
+    ctx.map(); ctx.synchronize()
+    first = ctx.profile_read(True)["l2"][1]
+    l2 = ctx.results()[2]
+    out = dict(bytes=gpucheck.pass_bytes(ctx), counts=ctx.result_counts(), per=np.bincount(l2["cand"]) if len(l2) else np.zeros(1, dtype=np.int64),
+               large=ctx.pass_l2_large(), window=ctx.pass_l2_window())
+    ctx.map(); ctx.synchronize()
+    out["l2_brackets"] = (first, ctx.profile_read(True)["l2"][1])
+    assert ctx.result_counts() == out["counts"]
+    ctx.close()
+    return out
 
 
 def map_fragment(orc, h, seq, seqCounter, name, fullLen, s, npts=1 << 19):

@@ -61,9 +61,12 @@ def takes_literal_grouped(points, q_sketch, min_hits_tab, rg):
     return int(min_hits_tab[q_sketch]) <= 0
 
 
-def run_y(oracle, contigs, reads, hg, option, kmerPct=0.001):
+def run_y(oracle, contigs, reads, hg, option, kmerPct=0.001, before=None, brackets=False):
     """one sized -Y pass over the batch on a fresh context, with or without MM_OPT_L1_GROUP_STREAM: (queued, literal) and everything it
-    leaves, as bytes and per fragment"""
+    leaves, as bytes and per fragment.  before: a batch the context maps first, which leaves it its buffers.  brackets: the kernel timers
+    are on and the batch is mapped once more at the end; `l1_brackets` = the MM_K_L1 timer brackets of its first and of its second pass
+    (pass_l1_sweeps closes one per attempt and the grown buffer stays with the context, so the first pass has more exactly when it had to
+    launch the sweep again)"""
     from mashmap_amd import capi
     flags = U.FLAG_SKIP_PREFIX | (U.FLAG_HG if hg else 0)
     h = oracle.session(contigs, K, L, S, PI, U.FILTER_MAP, flags, b"#", kmerPct)
@@ -74,15 +77,23 @@ def run_y(oracle, contigs, reads, hg, option, kmerPct=0.001):
     ctx.index_upload(ix["minmers"], ix["keys"], ix["offsets"], ix["points"], ix["freq"], ix["contigLen"], rg)
     ctx.set_tables(oracle.min_hits_table(S, K, PI), oracle.cutoffs(h))
     ctx.set_replay_tables(*capi.stat_replay_tables(S, K, PI, 0.0, True))
-    ctx.reads_upload([a for _, a in reads], [-1] * len(reads), [-1] * len(reads), 0)
-    ctx.map()
+    for batch in ([before] if before else []) + [reads]:
+        ctx.reads_upload([a for _, a in batch], [-1] * len(batch), [-1] * len(batch), 0)
+        if brackets and batch is reads: ctx.synchronize(); ctx.profile(True); ctx.profile_read(True)
+        ctx.map()
+    if brackets: ctx.synchronize(); first = ctx.profile_read(True)["l1"][1]
     queued, literal = ctx.pass_l1_literal()
     stats, l1, l2 = ctx.results()
     per = {}
     for c in l1:
         per.setdefault(int(c["frag"]), []).append((int(c["seqId"]), int(c["rangeStartPos"]), int(c["rangeEndPos"]), int(c["intersectionSize"])))
     out = dict(queued=queued, literal=literal, stats=stats.tobytes().hex(), l1=l1.tobytes().hex(), l2=l2.tobytes().hex(),
-               mappings=ctx.mappings().tobytes().hex(), l1_per_frag=[per.get(f, []) for f in range(len(stats))])
+               mappings=ctx.mappings().tobytes().hex(), l1_per_frag=[per.get(f, []) for f in range(len(stats))],
+               steady=ctx.pass_stats()[1], cause=ctx.pass_redo_cause(), totals=ctx.pass_totals())
+    if brackets:
+        ctx.map(); ctx.synchronize()
+        out["l1_brackets"] = (first, ctx.profile_read(True)["l1"][1])
+        assert ctx.results()[1].tobytes().hex() == out["l1"]
     ctx.close(); oracle.free(h)
     return out
 
@@ -191,6 +202,35 @@ def test_extents_off_the_chunk_grid_and_more_candidates_than_the_lds_buffer(orac
     assert any(len(s) >= 6 for s in sizes)
     assert all(len(p) <= SORT_LDSCAP for p, _, _ in per)
     check_both_ways(oracle, cs, reads, hg, per, kmerPct=0.0)
+
+
+@pytest.mark.gpu
+def test_candidates_outgrow_the_buffer_inside_the_grouped_wave_kernel(oracle):
+    """k_l1_stream_groups' claim running past l1Cap: the context is sized on the three reads above, then maps 120 one-segment reads of the
+    unit -- every fragment a candidate per copy it still sees, thousands in all, none from the fused kernels (under -Y every fragment is
+    queued) and none from the literal one, against the dense buffer a pass over 120 fragments starts with (tests/mmutil.py: dense_cap):
+    the kernel's first launch raises MM_PC_L1_OVERFLOW and the sweep is launched again -- the pass closes more MM_K_L1 timer brackets than a
+    second pass of the same batch on the same context, which finds the grown buffer.
+    FINDING: there is no MM_REDO_L1 to expect.  mm_launch_map makes no steady attempt under MM_FLAG_SKIP_PREFIX (allSlow), so the batch is
+    a sized pass, and a sized pass absorbs the flag itself: pass_l1_sweeps grows the buffer to the cursor's demand, rewinds the cursor
+    and launches the kernel again.  Pinned: no attempt, nothing redone, cause 0 -- and the bytes of a fresh context with the option and
+    of one without it (the literal kernel)."""
+    cs, few = case_repeats()
+    unit = U.random_dna(301, 800)
+    B = [("r%d" % i, T.subst(unit[x:x + L], 40 + i, 0.01)) for i, x in enumerate(np.linspace(0, len(unit) - L, 120).astype(int))]
+    assert all(len(T.fragments_of(a)) == 1 for _, a in B) and len(B) > sum(len(T.fragments_of(a)) for _, a in few)
+    behind = run_y(oracle, cs, B, True, True, kmerPct=0.0, before=few, brackets=True)
+    fresh = run_y(oracle, cs, B, True, True, kmerPct=0.0)
+    off = run_y(oracle, cs, B, True, False, kmerPct=0.0)
+    n1 = len(fresh["l1"]) // (2 * 20)                              # (hex digits of 20-byte records)
+    print("%d fragments, %d candidates, dense buffer of a pass over them %d; queued %d, literal %d; MM_K_L1 brackets of the first and the second pass %r"
+          % (len(B), n1, U.dense_cap(len(B)), behind["queued"], behind["literal"], behind["l1_brackets"]))
+    assert behind["queued"] == len(B) and behind["literal"] == 0   # every candidate is the wave kernel's
+    assert n1 > U.dense_cap(len(B)), "the candidates fit the buffer the kernel is first launched with"
+    assert behind["l1_brackets"][0] > behind["l1_brackets"][1] > 0, "the sweep was not launched again: the buffer did not grow"
+    for what in ("stats", "l1", "l2", "mappings"):
+        assert len(behind[what]) > 0 and behind[what] == fresh[what] == off[what], what
+    assert not behind["steady"] and behind["cause"] == 0 and behind["totals"] == {"passes": 2, "steady": 0, "redone": 0}
 
 
 # ----------------------------------------------------------------------------- 4: the HG rule, per extent

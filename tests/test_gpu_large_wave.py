@@ -205,6 +205,31 @@ def test_one_sketch_entry_more_than_the_lds_holds_is_the_literal_kernels(oracle,
         oracle.free(h)
 
 
+# ----------------------------------------------------------------------------- the locus buffer behind the wave kernel
+@pytest.mark.gpu
+def test_loci_outgrow_the_buffer_behind_the_large_wave_kernel(oracle):
+    """k_l2_large_wave's claim running past l2Cap: 700 one-segment reads out of eight exact copies -- up to eight tied loci in a candidate,
+    which its slots hold, so every candidate stays on the wave kernel -- bring more loci than the 2 n1 + 1 024 the literal route's buffer
+    starts with on a fresh context (mm_launch_l2_window: l2w_extents).  The kernel's first launch raises MM_PC_L2_OVERFLOW, the launcher
+    grows l2Cap to the cursor's demand and launches it again -- seen as the first pass closing more MM_K_L2 timer brackets than a second
+    pass of the same batch on the same context, which finds the grown buffer (tests/largewave.py: loci8_pass) -- and the pass leaves the
+    bytes of the pass with the option off (the fast split kernels).
+    At s = 32, the sketch size of the "loci8" case: at this module's s = 80 the same index cuts a read's candidates at every copy (400
+    reads: 1 749 candidates with 2 943 loci), fewer than the two loci per candidate the buffer starts with, at any number of reads"""
+    reads = W.loci8_reads(700)
+    off = W.loci8_pass(reads, 0, lambda c: c.l2_large_wave(0))
+    on = W.loci8_pass(reads, 0, lambda c: c.l2_large_wave(3))
+    n1, n2 = off["counts"]
+    print("%d candidates, %d loci (at most %d in one), the buffer starts at %d; with the option %r, MM_K_L2 brackets of the first and the second pass %r"
+          % (n1, n2, off["per"].max(), 2 * n1 + 1024, on["large"], on["l2_brackets"]))
+    assert off["per"].max() <= W.LOCAP0 + 1, "a candidate has more loci than the wave kernel holds"
+    assert n2 > 2 * n1 + 1024, "the loci fit the buffer the kernel is first launched with"
+    assert off["large"] == (0, 0) and on["large"] == (n1, 0)       # every candidate, and its loci, on the wave kernel
+    assert on["l2_brackets"][0] > on["l2_brackets"][1] > 0, "the first pass did not repeat an attempt: l2Cap did not grow"
+    for a, b, what in zip(on["bytes"], off["bytes"], ("stats", "l1", "l2", "mappings", "query sketches")):
+        assert a == b, what
+
+
 # ----------------------------------------------------------------------------- 7: the command line
 def case_command_line():
     cs = [U.random_dna(9301, 400000), U.random_dna(9302, 380000)]

@@ -30,17 +30,8 @@ K, L, PI = 16, 1000, 0.95                                 # (at 0.95 minimumHits
 WIDE_CAP, EXACT_CAP, LOCAP0 = 4096, 1024, 8               # mm_l2.hip: MM_WIDE_CAP, MM_EXACT_CAP, MM_LOCAP0
 
 
-# ---- the capacities a sized pass leaves (mm_internal.h: DevBuf::ensure; mm_map.hip, mm_l2.hip, mm_select.hip), restated ------------------
-def devbuf(need): return need + need // 8 + 256                                   # bytes DevBuf::ensure(need) allocates when it grows
-def pts_cap(nF): return nF * 8 + 65536                                            # interval points (pass_prepare), while no sized pass had to grow it
-def region_cap(nF): return (nF * 2 + 1024 + 63) // 64 + 64                        # L1 candidates per output region (pass_lookup), likewise
-def dense_cap(nF): return devbuf(region_cap(nF) * 64 * 20 + 64) // 20 - 4         # ... and in the dense buffer behind them (pass_compact)
-def cand_cap(nL1): return nL1 + nL1 // 8 + 1024                                   # candidate-indexed staging (mm_launch_l2)
-def loci_cap(nL1, nL2):                                                           # L2 loci (mm_launch_l2: l2Cap, grown by a sized pass that overflows it)
-    cap = cand_cap(nL1) * 2 + 1024
-    return cap if nL2 <= cap else nL2 + nL2 // 8 + 1024
-def map_cap(total): return devbuf((total + total // 16) * 48 + 4096) // 48 - 2    # candidate mappings (mm_launch_select)
-def ops_cap(ops): return devbuf((ops + ops // 16) * 4 + 256) // 4 - 64            # L2 stream entries (dL2Ops as k_l2_gate sees it)
+# the capacities a sized pass leaves, restated, and the tandem arrays with their reads: tests/mmutil.py (other modules use them too)
+from mmutil import (arrayed, cand_cap, dense_cap, devbuf, loci_cap, map_cap, ops_cap, pts_cap, region_cap, unit_reads)  # noqa: E402,F401
 
 
 class Fresh:
@@ -250,19 +241,6 @@ def test_more_doubly_open_candidates_than_the_exact_kernel_covers(oracle):
         gpucheck.run_and_compare(oracle, named("c", cs), named("a", A[:15]) + named("b", B[:15]), pi=PI, mutate_index=overlap, verbose=False)
     finally:
         oracle.free(h)
-
-
-def arrayed(seed, unit, copies, div):
-    """a tandem array of the unit between random flanks; div 0: exact copies, which tie in L2 -- a unit longer than a segment gives a locus
-    per copy; div > 0: every copy diverged on its own, the same long candidates and streams with one best locus"""
-    parts = [unit if div == 0 else U.mutate(unit, seed * 17 + i, div) for i in range(copies)]
-    return np.concatenate([U.random_dna(seed + 1, 3000)] + parts + [U.random_dna(seed + 2, 3000)])
-
-
-def unit_reads(unit, seed, n, err=0.02):
-    """n reads of one segment out of the (circular) unit, at evenly spread offsets"""
-    two = np.concatenate([unit, unit])
-    return [U.mutate(two[x:x + L + 60], seed * 1000 + i, err)[:L].copy() for i, x in enumerate(np.linspace(0, len(unit) - 1, n).astype(int))]
 
 
 def loci_per_candidate(make_ctx, reads):

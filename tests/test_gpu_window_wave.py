@@ -228,6 +228,30 @@ def test_the_option_leaves_other_batches_alone(oracle, nosplit):
         assert len(on[what]) > 0 and on[what] == off[what], what
 
 
+@pytest.mark.gpu
+def test_loci_outgrow_the_buffer_behind_the_window_wave_kernel(oracle):
+    """k_l2_window_wave's claim running past l2Cap: tests/largewave.py's loci8 batch out of eight exact copies (s = 32), under --noSplit and with
+    a read of three segments in front, which makes the batch a windowed one -- more loci than the 2 n1 + 1 024 the buffer starts with
+    (mm_launch_l2_window: l2w_extents), of candidates the wave kernel keeps.  Its first launch raises MM_PC_L2_OVERFLOW, the launcher
+    grows l2Cap to the cursor's demand and launches it again (the first pass closes more MM_K_L2 timer brackets than a second pass of the
+    same batch on the same context: loci8_pass): the bytes of the pass without the option (the literal kernel)"""
+    import largewave as T
+    from mashmap_amd import capi
+    ub = U.random_dna(9052, 1300)
+    long_read = U.mutate(np.concatenate([ub, ub, ub]), 9057, 0.02)[:3 * T.LOCI8_L].copy()
+    reads = [long_read] + T.loci8_reads(700)
+    off = T.loci8_pass(reads, capi.MM_FLAG_NO_SPLIT, lambda c: c.l2_window_wave(False))
+    on = T.loci8_pass(reads, capi.MM_FLAG_NO_SPLIT, lambda c: c.l2_window_wave(True))
+    n1, n2 = off["counts"]
+    print("%d candidates, %d loci (at most %d in one), the buffer starts at %d; windowed: %r without the option, %r with it; MM_K_L2 brackets of the first and the second pass %r"
+          % (n1, n2, off["per"].max(), 2 * n1 + 1024, off["window"], on["window"], on["l2_brackets"]))
+    assert off["window"] == (n1, n1) and on["window"][0] == n1
+    assert n2 - on["window"][1] * int(off["per"].max()) > 2 * n1 + 1024, "the loci of the candidates the wave kernel keeps fit the buffer it is first launched with"
+    assert on["l2_brackets"][0] > on["l2_brackets"][1] > 0, "the first pass did not repeat an attempt: l2Cap did not grow"
+    for a, b, what in zip(on["bytes"], off["bytes"], ("stats", "l1", "l2", "mappings", "query sketches")):
+        assert a == b, what
+
+
 # ----------------------------------------------------------------------------- 7: CPU
 def test_the_option_and_the_query_are_declared_exported_and_bound():
     import ctypes
