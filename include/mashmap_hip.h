@@ -347,6 +347,64 @@ int mm_mappings_count(const mm_ctx* ctx, size_t* n);
 int mm_mappings_download(mm_ctx* ctx, mm_mapping* out, size_t cap, size_t* n);
 /* device address of the same records; valid until the next map call */
 int mm_mappings_device(const mm_ctx* ctx, const mm_mapping** dMappings, size_t* n);
+/*
+ * The tail of Map::mapModule on the device (computeMap.hpp:679-714): for every read of the batch, from its resident candidate mappings,
+ * what the host side's MapPost::finishRead computes up to and including filterByGroup -- the kmerComplexity gate and the sort of
+ * mapSingleQueryFrag (:799-800, :1137), the coordinates of a split read (:632-636), mergeMappingsInRange (:1580-1702),
+ * filterWeakMappings (:423), filterByGroup on the query axis (:504-561) with the plane sweep of filter.hpp:36-160 --, one mm_chain_row per
+ * surviving mapping.  The caller starts the stage explicitly after mm_map_fragments; nothing of that call changes.  The restatement is
+ * mashmap_amd/csrc/mm_chain_core.h (one function per read, compiled for the host by tests/hostlogic/chain_check.cpp); DESIGN.md
+ * section 6 has the argument why rows equal the host's bit for bit.  A read with more than MM_CHAIN_MAX_RECORDS records is not taken:
+ * up to that size libstdc++'s std::sort is a stable insertion sort, which a stable sort reproduces; beyond, the representative of a
+ * chain depends on introsort's moves.  Its records are handed over untouched (the left-over array) and the host finishes it as before.
+ * What stays on the host, applied to the rows: filterFalseHighIdentity, mappingBoundarySanityCheck, sparsifyMappings,
+ * nucIdentityUpperBound and the PAF text (MapPost::finishRows).
+ *
+ * mm_chain_params: chainGap = Parameters::chain_gap (refused above 1 << 25: every accepted pair's squared distances are then exact in
+ * a double); minMerged = floor(block_length / segLength); secondaryShort / secondarySegment = numMappingsForShortSequence - 1 /
+ * numMappingsForSegment - 1 (secondaryToKeep of a read shorter than segLength / of any other; -1, a count of 0, is 65535 behind the
+ * reference's cast to uint16_t, here as there; below -1 the block is refused, as is a negative minMerged); merge = mergeMappings; filter =
+ * MM_CHAIN_FILTER_NONE or MM_CHAIN_FILTER_QUERY (filter modes map and one-to-one; the reference-axis filter of one-to-one is global
+ * and stays on the host).
+ * mm_set_chain_tables uploads the block and identity[Qs * stride + shared] = 1 - j2md(1.0 * shared / Qs, k) as floats (stride =
+ * sketchSize + 1, the stride of the replay tables; mm_stat_identity_table fills it with the host's own expression).
+ * mm_chain_reads runs the stage on the context's stream and waits once, at its end, for the four counts.  MM_ERR_STATE, with the reason
+ * in mm_last_error: nothing mapped or no replay tables; mm_set_chain_tables not called; MM_FLAG_SKIP_PREFIX (its filter runs group by
+ * group); MM_FLAG_NO_SPLIT; sketchSize above MM_CHAIN_MAX_SKETCH (the identity table would pass 16 MB); a record that names a sketch
+ * size or shared count outside the identity table ("corrupt record": an error, never a hand-over -- the 16-record limit is the single
+ * hand-over cause).  An empty batch, or one
+ * without records, is MM_OK with zero counts.
+ * mm_chain_counts: *offered = reads with at least one record, *finished = those of them the kernel took, *rows, *leftover = entries of
+ * the two arrays.  Rows are in read order, inside a read in the order filterByGroup leaves them; the left-over mm_mapping records are
+ * the handed-over reads', read-major, in their original order.  The device addresses are valid until the next mm_chain_reads or map call.
+ * Purely additive: MM_ABI_VERSION stays 2.
+ */
+#define MM_CHAIN_MAX_RECORDS 16
+#define MM_CHAIN_MAX_SKETCH 2048
+#define MM_CHAIN_MAX_GAP (1 << 25)
+enum { MM_CHAIN_FILTER_NONE = 0, MM_CHAIN_FILTER_QUERY = 1 };
+typedef struct {
+  int32_t chainGap, minMerged, secondaryShort, secondarySegment, merge, filter;
+  float kmerComplexityThreshold;
+  int32_t pad_;
+} mm_chain_params;
+/* every field of MappingResult (base_types.hpp:154) that finishRead leaves defined behind filterByGroup.  72 bytes.  kmerComplexity is
+ * a double: a merged chain's is an average taken in double (:1668), a lone mapping's the float of getSeedHits (:831) widened. */
+typedef struct {
+  int32_t querySeqId, queryLen, queryStartPos, queryEndPos;
+  int32_t refSeqId, refStartPos, refEndPos, strand;
+  int32_t conservedSketches, sketchSize, blockLength, approxMatches, n_merged, splitMappingId;
+  float nucIdentity;
+  int32_t pad_;
+  double kmerComplexity;
+} mm_chain_row;
+int mm_stat_identity_table(int sketchSize, int k, float* identity);   /* (sketchSize+1)^2 floats; row 0 (Qs == 0) is never read */
+int mm_set_chain_tables(mm_ctx* ctx, const mm_chain_params* params, const float* identity, size_t stride);
+int mm_chain_reads(mm_ctx* ctx);
+int mm_chain_counts(const mm_ctx* ctx, size_t* offered, size_t* finished, size_t* rows, size_t* leftover);
+int mm_chain_download(mm_ctx* ctx, mm_chain_row* out, size_t cap, size_t* n);
+int mm_chain_leftover_download(mm_ctx* ctx, mm_mapping* out, size_t cap, size_t* n);
+int mm_chain_device(const mm_ctx* ctx, const mm_chain_row** dRows, size_t* nRows, const mm_mapping** dLeftover, size_t* nLeftover);
 /* post-removal sketches Q.minmerTableQuery: out[f*sketchSize + r] (valid r < stats[f].sketchSize) */
 int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
 /*

@@ -34,6 +34,20 @@ class Params(C.Structure):
     _fields_ = [("kmerSize", C.c_int32), ("segLength", C.c_int32), ("sketchSize", C.c_int32), ("flags", C.c_int32)]
 
 
+class ChainParams(C.Structure):
+    """mm_chain_params (include/mashmap_hip.h)"""
+    _fields_ = [("chainGap", C.c_int32), ("minMerged", C.c_int32), ("secondaryShort", C.c_int32), ("secondarySegment", C.c_int32),
+                ("merge", C.c_int32), ("filter", C.c_int32), ("kmerComplexityThreshold", C.c_float), ("pad", C.c_int32)]
+
+
+MM_CHAIN_MAX_RECORDS, MM_CHAIN_MAX_SKETCH, MM_CHAIN_MAX_GAP = 16, 2048, 1 << 25
+MM_CHAIN_FILTER_NONE, MM_CHAIN_FILTER_QUERY = 0, 1
+# mm_chain_row: one mapping of a read as filterByGroup leaves it (mm_chain_reads)
+CHAIN_ROW_DT = np.dtype([("querySeqId", "<i4"), ("queryLen", "<i4"), ("queryStartPos", "<i4"), ("queryEndPos", "<i4"), ("refSeqId", "<i4"),
+                         ("refStartPos", "<i4"), ("refEndPos", "<i4"), ("strand", "<i4"), ("conservedSketches", "<i4"), ("sketchSize", "<i4"),
+                         ("blockLength", "<i4"), ("approxMatches", "<i4"), ("n_merged", "<i4"), ("splitMappingId", "<i4"),
+                         ("nucIdentity", "<f4"), ("pad", "<i4"), ("kmerComplexity", "<f8")])
+assert CHAIN_ROW_DT.itemsize == 72
 MINMER_DT = np.dtype([("hash", "<u8"), ("wpos", "<i4"), ("wpos_end", "<i4"), ("seqId", "<i4"), ("strand", "<i2"),
                       ("pad", "<i2")])
 POINT_DT = np.dtype([("pos", "<i4"), ("pad0", "<i4"), ("hash", "<u8"), ("seqId", "<i4"), ("side", "i1"),
@@ -144,6 +158,13 @@ def load():
         "mm_reads_prefetch_packed_append": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_int)]),
         "mm_reads_prefetch_drop": (C.c_int, [vp]),
         "mm_reads_prefetch_reserve": (C.c_int, [vp, sz]),
+        "mm_stat_identity_table": (C.c_int, [C.c_int, C.c_int, vp]),
+        "mm_set_chain_tables": (C.c_int, [vp, C.POINTER(ChainParams), vp, sz]),
+        "mm_chain_reads": (C.c_int, [vp]),
+        "mm_chain_counts": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+        "mm_chain_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
+        "mm_chain_leftover_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
+        "mm_chain_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
         "mm_synchronize": (C.c_int, [vp]),
         "mm_stream": (vp, [vp]),
     }
@@ -170,7 +191,9 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_reads_upload_packed", "mm_reads_prefetch_packed", "mm_pack_read", "mm_pack_read_portable", "mm_reads_packed_download",
            "mm_index_layout_get", "mm_pass_stats", "mm_comm_info", "mm_pass_totals", "mm_reads_exchange", "mm_reads_upload_packed_parts",
            "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
-           "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large"]
+           "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
+           "mm_stat_identity_table", "mm_set_chain_tables", "mm_chain_reads", "mm_chain_counts", "mm_chain_download",
+           "mm_chain_leftover_download", "mm_chain_device"]
 
 
 def stat_sketch_cutoffs(sketchSize, k, hg=True):
@@ -206,6 +229,14 @@ def stat_replay_tables(sketchSize, k, pi, aniDiff=0.0, keepLow=True):
     if load().mm_stat_replay_tables(sketchSize, k, pi, aniDiff, 1 if keepLow else 0, _ptr(acc), _ptr(mi)) != 0:
         raise MashmapError("mm_stat_replay_tables failed")
     return acc, mi
+
+
+def stat_identity_table(sketchSize, k):
+    """identity[Qs * (sketchSize + 1) + shared] = 1 - j2md(shared / Qs, k), the floats mm_set_chain_tables takes"""
+    out = np.zeros((sketchSize + 1) ** 2, dtype=np.float32)
+    if load().mm_stat_identity_table(sketchSize, k, _ptr(out)) != 0:
+        raise MashmapError("mm_stat_identity_table failed")
+    return out
 
 
 def pack_reads(reads, portable=False):
@@ -543,6 +574,43 @@ class Context:
         out = np.zeros(n.value, dtype=MAPPING_DT)
         self._ck(self.lib.mm_mappings_download(self.h, _ptr(out), n.value, C.byref(n)), "mm_mappings_download")
         return out
+
+    # ---- chaining and filtering on the device
+    def set_chain_tables(self, chainGap, minMerged=1, secondaryShort=0, secondarySegment=0, merge=True, filter=MM_CHAIN_FILTER_QUERY,
+                         kmerComplexityThreshold=0.0, identity=None):
+        """mm_set_chain_tables: the parameter block of mm_chain_reads and the identity table (stat_identity_table of this context's
+        sketch size and k unless given)"""
+        ident = stat_identity_table(self.s, self.params.kmerSize) if identity is None else np.ascontiguousarray(identity, dtype=np.float32)
+        p = ChainParams(chainGap, minMerged, secondaryShort, secondarySegment, 1 if merge else 0, filter, kmerComplexityThreshold, 0)
+        self._ck(self.lib.mm_set_chain_tables(self.h, C.byref(p), _ptr(ident), self.s + 1), "mm_set_chain_tables")
+
+    def chain_reads(self):
+        """mm_chain_reads: every read's candidate mappings chained and filtered on the device (after map())"""
+        self._ck(self.lib.mm_chain_reads(self.h), "mm_chain_reads")
+
+    def chain_counts(self):
+        """dict(offered, finished, rows, leftover) of the last chain_reads()"""
+        v = [C.c_size_t() for _ in range(4)]
+        self._ck(self.lib.mm_chain_counts(self.h, *[C.byref(x) for x in v]), "mm_chain_counts")
+        return dict(zip(("offered", "finished", "rows", "leftover"), (int(x.value) for x in v)))
+
+    def chain_rows(self):
+        n = self.chain_counts()["rows"]
+        out = np.zeros(n, dtype=CHAIN_ROW_DT); got = C.c_size_t()
+        self._ck(self.lib.mm_chain_download(self.h, _ptr(out), n, C.byref(got)), "mm_chain_download")
+        return out
+
+    def chain_leftover(self):
+        n = self.chain_counts()["leftover"]
+        out = np.zeros(n, dtype=MAPPING_DT); got = C.c_size_t()
+        self._ck(self.lib.mm_chain_leftover_download(self.h, _ptr(out), n, C.byref(got)), "mm_chain_leftover_download")
+        return out
+
+    def chain_device(self):
+        """(device address of the rows, rows, device address of the left-over records, records)"""
+        a, b, na, nb = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        self._ck(self.lib.mm_chain_device(self.h, C.byref(a), C.byref(na), C.byref(b), C.byref(nb)), "mm_chain_device")
+        return a.value, na.value, b.value, nb.value
 
     def comm_init_rank(self, comm_id, rank, world):
         buf = (C.c_char * COMM_ID_BYTES).from_buffer_copy(bytes(comm_id))

@@ -265,6 +265,12 @@ struct mm_ctx {
   // candidate mappings (mm_select.hip)
   DevBuf dAccept, dMinIsz; bool haveReplayTables = false;
   DevBuf dSelCnt, dSelOff, dSelHeap, dFragTab, dMappings; size_t nMappings = 0; bool fragTabStale = true;
+  // chaining and filtering on the device (mm_chain.hip): the identity table and parameter block of mm_set_chain_tables; per read the
+  // record range, row / left-over counts and their scans; the two output arrays; the four counts of the last mm_chain_reads
+  DevBuf dChainIdent, dChainBegin, dChainEnd, dChainCntR, dChainCntL, dChainOffR, dChainOffL, dChainRows, dChainLeft, dChainTotals;
+  mm_chain_params chainP{}; bool haveChainTables = false;
+  uint64_t chainPass = 0;                               // nPasses when mm_chain_reads last went through: its results belong to that pass (0: none)
+  size_t chOffered = 0, chFinished = 0, chRows = 0, chLeft = 0;
   // multi-GPU exchange (mm_comm.hip)
   void* comm = nullptr; int commRank = 0, commWorld = 0; bool commCopy = false;   // commCopy: local group whose contexts share a device
   DevBuf dCommCounts, dGathered; std::vector<size_t> gatherCounts, gatherDisp; size_t nGathered = 0; bool gathered = false;

@@ -61,6 +61,96 @@ int64_t mmh_post_batch(int k, int segLength, int sketchSize, float pi, int filte
   return n;
 }
 
+// The same stage behind mm_chain_reads: chainRows are the batch's rows (mm_chain_download: the reads the device finished, in read
+// order) and recs the left-over records of the reads it handed over (mm_chain_leftover_download), read-major; a read has rows, or
+// records, or neither.  Rows go through MapPost::finishRows, records through mapModuleFromRecords, and the reported mappings come out
+// in input order.  With no rows at all this is mmh_post_batch with chain_gap, block_length and the two mapping counts given
+// explicitly.  nMerged / approxMatches (may be null) receive those two fields of every reported mapping beside `rows`.
+int64_t mmh_post_chained(int k, int segLength, int sketchSize, float pi, int filterMode, int hgFilter, int numMappingsShort, int numMappingsSegment,
+                         int chainGap, int blockLength, int nContigs, const int32_t* contigLens, const mm_chain_row* chainRows, size_t nChainRows,
+                         const mm_mapping* recs, size_t nRecs, const int32_t* readLens, size_t nReads, int32_t firstSeqCounter, int threads,
+                         double* seconds, mmh_row* rows, int32_t* nMerged, int32_t* approxMatches, size_t cap) {
+  skch::Parameters p;
+  p.kmerSize = k; p.segLength = segLength; p.block_length = blockLength; p.chain_gap = chainGap; p.sketchSize = sketchSize;
+  p.percentageIdentity = pi; p.filterMode = filterMode; p.stage1_topANI_filter = hgFilter != 0;
+  p.numMappingsForSegment = (uint32_t)numMappingsSegment; p.numMappingsForShortSequence = (uint32_t)numMappingsShort;
+  std::vector<skch::ContigInfo> meta((size_t)nContigs);
+  for (int i = 0; i < nContigs; i++) meta[i] = skch::ContigInfo{"c" + std::to_string(i), contigLens[i]};
+  std::vector<int> grp((size_t)nContigs, 0);
+  skch::MapPost post(p, meta, grp);
+  const auto t0 = std::chrono::high_resolution_clock::now();
+  std::vector<size_t> recBegin(nReads + 1, nRecs), rowBegin(nReads + 1, nChainRows);
+  { size_t i = 0; for (size_t r = 0; r <= nReads; r++) { while (i < nRecs && (size_t)(recs[i].querySeqId - firstSeqCounter) < r) i++; recBegin[r] = i; } }
+  { size_t i = 0; for (size_t r = 0; r <= nReads; r++) { while (i < nChainRows && (size_t)(chainRows[i].querySeqId - firstSeqCounter) < r) i++; rowBegin[r] = i; } }
+  std::vector<skch::MappingResultsVector_t> perRead(nReads);
+  std::atomic<size_t> next(0);
+  auto work = [&]() {
+    const size_t chunk = 64;
+    for (size_t r0 = next.fetch_add(chunk); r0 < nReads; r0 = next.fetch_add(chunk))
+      for (size_t r = r0; r < std::min(nReads, r0 + chunk); r++) {
+        if (readLens[r] < k) continue;
+        if (rowBegin[r] != rowBegin[r + 1]) post.finishRows(chainRows + rowBegin[r], chainRows + rowBegin[r + 1], readLens[r], perRead[r]);
+        else if (recBegin[r] != recBegin[r + 1]) post.mapModuleFromRecords(recs + recBegin[r], recs + recBegin[r + 1], readLens[r], perRead[r]);
+      }
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < threads; t++) pool.emplace_back(work);
+  work();
+  for (auto& th : pool) th.join();
+  int64_t n = 0;
+  for (size_t r = 0; r < nReads; r++)
+    for (const auto& e : perRead[r]) {
+      if ((size_t)n < cap) {
+        if (rows) rows[n] = mmh_row{e.querySeqId, e.queryLen, e.queryStartPos, e.queryEndPos, e.refSeqId, e.refStartPos, e.refEndPos, (int32_t)e.strand,
+                                    e.conservedSketches, e.blockLength, e.nucIdentity, (float)e.kmerComplexity};
+        if (nMerged) nMerged[n] = e.n_merged;
+        if (approxMatches) approxMatches[n] = e.approxMatches;
+      }
+      n++;
+    }
+  if (seconds) *seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+  return n;
+}
+
+// What mm_chain_reads must leave, from the host's own code: for every read with 1 .. maxRecords records, MapPost::chainedFromRecords
+// (mapModuleFromRecords stopped behind filterByGroup) as mm_chain_row, in read order.  Returns the number of rows (out receives the
+// first `cap`).  The checker of the device rows in tests/test_gpu_chain.py; one thread.
+int64_t mmh_chain_rows(int k, int segLength, int sketchSize, float pi, int filterMode, int numMappingsShort, int numMappingsSegment, int chainGap,
+                       int blockLength, int nContigs, const int32_t* contigLens, const mm_mapping* recs, size_t nRecs, const int32_t* readLens,
+                       size_t nReads, int32_t firstSeqCounter, int maxRecords, mm_chain_row* out, size_t cap) {
+  skch::Parameters p;
+  p.kmerSize = k; p.segLength = segLength; p.block_length = blockLength; p.chain_gap = chainGap; p.sketchSize = sketchSize;
+  p.percentageIdentity = pi; p.filterMode = filterMode;
+  p.numMappingsForSegment = (uint32_t)numMappingsSegment; p.numMappingsForShortSequence = (uint32_t)numMappingsShort;
+  std::vector<skch::ContigInfo> meta((size_t)nContigs);
+  for (int i = 0; i < nContigs; i++) meta[i] = skch::ContigInfo{"c" + std::to_string(i), contigLens[i]};
+  std::vector<int> grp((size_t)nContigs, 0);
+  skch::MapPost post(p, meta, grp);
+  int64_t n = 0;
+  skch::MappingResultsVector_t v;
+  for (size_t i = 0; i < nRecs;) {
+    size_t j = i;
+    while (j < nRecs && recs[j].querySeqId == recs[i].querySeqId) j++;
+    const size_t r = (size_t)(recs[i].querySeqId - firstSeqCounter);
+    if (r < nReads && j - i <= (size_t)maxRecords) {
+      post.chainedFromRecords(recs + i, recs + j, readLens[r], v);
+      for (const auto& e : v) {
+        if ((size_t)n < cap) {
+          mm_chain_row& o = out[n];
+          std::memset(&o, 0, sizeof o);
+          o.querySeqId = e.querySeqId; o.queryLen = (int32_t)e.queryLen; o.queryStartPos = (int32_t)e.queryStartPos; o.queryEndPos = (int32_t)e.queryEndPos;
+          o.refSeqId = e.refSeqId; o.refStartPos = (int32_t)e.refStartPos; o.refEndPos = (int32_t)e.refEndPos; o.strand = e.strand;
+          o.conservedSketches = e.conservedSketches; o.sketchSize = e.sketchSize; o.blockLength = e.blockLength; o.approxMatches = e.approxMatches;
+          o.n_merged = e.n_merged; o.splitMappingId = (int32_t)e.splitMappingId; o.nucIdentity = e.nucIdentity; o.kmerComplexity = (double)e.kmerComplexity;
+        }
+        n++;
+      }
+    }
+    i = j;
+  }
+  return n;
+}
+
 // slots of the all-gatherv of candidate mappings (mm_exchange_plan.h, what mm_comm.hip places its RCCL broadcasts by): disp[world + 1]
 uint64_t mmh_exchange_plan(const uint64_t* counts, int world, uint64_t* disp) { return mm_exchange_place(counts, world, disp); }
 

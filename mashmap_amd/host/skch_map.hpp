@@ -85,6 +85,11 @@ class Map {
   // it has parsed a batch, the device stage right after an upload has emptied part of the area -- so the copies of the batches behind a
   // pass always run under that pass's kernels.  stagedBases[i]: bases of queued batches already sent to context i (guarded by pfMu).
   std::mutex pfMu; std::vector<size_t> stagedBases; size_t stageCapBases = 0, stageReserveBases = 0;
+  // MASHMAP_HIP_DEVICE_CHAIN: the device stage runs mm_chain_reads behind mm_map_fragments and brings back the rows of the reads it
+  // finished plus the records of the reads it handed over, instead of every record; the post stage finishes both kinds.  Only in a run
+  // with one context, split reads, no reference groups (-Y), filter mode map or one-to-one, sketchSize <= MM_CHAIN_MAX_SKETCH and a
+  // chain gap the stage takes; anywhere else the switch does nothing
+  bool deviceChain = false;
   bool exchangeFellBack = false;                 // a default RCCL all-gatherv failed once: per-context downloads for the rest of the run
   skch::Time::time_point tStart = skch::Time::now();   // MASHMAP_HIP_TIMING lines carry the time since the Map was constructed
   // one write per diagnostic line: three stages log at once, and `std::cerr << a << b` from two threads interleaves inside a line
@@ -100,6 +105,8 @@ class Map {
     // candidate mappings of the batch, read-major: a slice of the records its device pass brought back (page-locked, skch_types.hpp;
     // shared by the batches of the pass)
     std::shared_ptr<PinnedRecs<mm_mapping>> recOwner; const mm_mapping* recs = nullptr; size_t nRecs = 0;
+    // under MASHMAP_HIP_DEVICE_CHAIN: the rows of the reads mm_chain_reads finished (recs are then the handed-over reads' records only)
+    std::shared_ptr<PinnedRecs<mm_chain_row>> rowOwner; const mm_chain_row* rows = nullptr; size_t nRows = 0;
     mutable std::vector<char> prefetched;        // per context: the batch's block is already on its way to that GPU (guarded by pfMu)
     size_t size() const { return in.names.size(); }
     size_t bases() const { return (size_t)in.totalBases(); }
@@ -130,7 +137,16 @@ class Map {
       if (mm_set_tables(c, minHits.data(), minHits.size(), cut32.data(), cut32.size()) != MM_OK) die("mm_set_tables", c);
       if (mm_set_replay_tables(c, accept.data(), minIsz.data(), (size_t)p.sketchSize + 1) != MM_OK) die("mm_set_replay_tables", c);
     }
-    if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] integer tables ready" << at();
+    if (getenv("MASHMAP_HIP_DEVICE_CHAIN") && ctxs.size() == 1 && p.split && !p.skip_prefix && (p.filterMode == filter::MAP || p.filterMode == filter::ONETOONE) &&
+        p.sketchSize <= MM_CHAIN_MAX_SKETCH && p.chain_gap >= 0 && p.chain_gap <= MM_CHAIN_MAX_GAP) {
+      const size_t stride = (size_t)p.sketchSize + 1;
+      std::vector<float> identity(stride * stride);
+      if (mm_stat_identity_table(p.sketchSize, p.kmerSize, identity.data()) != MM_OK) die("mm_stat_identity_table");
+      const mm_chain_params cp = post.chainParams();
+      if (mm_set_chain_tables(ctx, &cp, identity.data(), stride) != MM_OK) die("mm_set_chain_tables");
+      deviceChain = true;
+    }
+    if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] integer tables ready" << (deviceChain ? " (chaining on the device)" : "") << at();
     this->mapQuery();
     if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] mapQuery done" << at();
   }
@@ -357,6 +373,8 @@ class Map {
     bool gatherOnDevice = nCtx > 1 && !exchangeFellBack && refSketch.commReady() && (xe ? gatherAsked : refSketch.distinctDevices());
     std::vector<PinnedRecs<mm_mapping>> blockRecs(nCtx == 1 ? 0 : nCtx);
     auto all = std::make_shared<PinnedRecs<mm_mapping>>();
+    auto allRows = std::make_shared<PinnedRecs<mm_chain_row>>();
+    size_t nRows = 0;
     double phase[3] = {0, 0, 0};                           // context 0: upload, kernels, download (seconds)
     auto releaseBuffers = [&]() {                           // the bases are in HBM: the page-locked buffers go back to the reader
       for (auto& b : grp) if (b.in.bases) { HostBufferPool::instance().give(b.in.bases, b.in.cap); b.in.bases = nullptr; }
@@ -408,7 +426,14 @@ class Map {
     }
     size_t n = 0;
     const auto p2 = skch::Time::now();
-    if (nCtx == 1) {
+    if (nCtx == 1 && deviceChain) {
+      // rows of the reads the device finished + records of the reads it handed over, instead of every record
+      if (mm_chain_reads(ctx) != MM_OK) die("mm_chain_reads");
+      if (mm_chain_counts(ctx, nullptr, nullptr, &nRows, &n) != MM_OK) die("mm_chain_counts");
+      allRows->resize(nRows); all->resize(n);
+      if (nRows && mm_chain_download(ctx, allRows->data(), nRows, &nRows) != MM_OK) die("mm_chain_download");
+      if (n && mm_chain_leftover_download(ctx, all->data(), n, &n) != MM_OK) die("mm_chain_leftover_download");
+    } else if (nCtx == 1) {
       if (mm_mappings_count(ctx, &n) != MM_OK) die("mm_mappings_count");
       all->resize(n);
       if (n && mm_mappings_download(ctx, all->data(), n, &n) != MM_OK) die("mm_mappings_download");
@@ -439,17 +464,20 @@ class Map {
     }
     // the records are read-major in input order: every batch of the pass gets its slice
     {
-      size_t at = 0;
+      size_t at = 0, rowAt = 0;
       for (size_t j = 0; j < nB; j++) {
         const seqno_t endId = grp[j].firstSeqCounter + (seqno_t)grp[j].size();
-        const size_t b0 = at;
+        const size_t b0 = at, r0 = rowAt;
         while (at < n && (*all)[at].querySeqId < endId) at++;
+        while (rowAt < nRows && (*allRows)[rowAt].querySeqId < endId) rowAt++;
         grp[j].recOwner = all; grp[j].recs = all->data() + b0; grp[j].nRecs = at - b0;
+        grp[j].rowOwner = allRows; grp[j].rows = allRows->data() + r0; grp[j].nRows = rowAt - r0;
       }
-      if (at != n) { std::cerr << "[mashmap_hip::skch::Map] ERROR: candidate mappings of a pass are not in input order" << std::endl; exit(1); }
+      if (at != n || rowAt != nRows) { std::cerr << "[mashmap_hip::skch::Map] ERROR: candidate mappings of a pass are not in input order" << std::endl; exit(1); }
     }
     if (timing) LogLine() << "[mashmap_hip::timing] device stage (upload + pack + kernels" << (gatherOnDevice ? " + all-gatherv" : "") << " + download of " << n
-                          << " candidate mappings): " << std::chrono::duration<double>(skch::Time::now() - t0).count() << " s (upload " << phase[0] << ", kernels " << phase[1]
+                          << (deviceChain ? " left-over candidate mappings and " + std::to_string(nRows) + " chained rows): " : std::string(" candidate mappings): "))
+                          << std::chrono::duration<double>(skch::Time::now() - t0).count() << " s (upload " << phase[0] << ", kernels " << phase[1]
                           << ", download " << std::chrono::duration<double>(skch::Time::now() - p2).count() << ") [bases " << passBases << "] [batches " << nB << "]" << at();
   }
 
@@ -465,6 +493,15 @@ class Map {
       for (size_t r = 0; r <= nReads; r++) {
         while (i < batch.nRecs && (size_t)(batch.recs[i].querySeqId - batch.firstSeqCounter) < r) i++;
         recBegin[r] = i;
+      }
+    }
+    // ... and, under MASHMAP_HIP_DEVICE_CHAIN, first row of every read (a read has rows, or records, or neither)
+    std::vector<size_t> rowBegin(batch.nRows ? nReads + 1 : 0, batch.nRows);
+    if (batch.nRows) {
+      size_t i = 0;
+      for (size_t r = 0; r <= nReads; r++) {
+        while (i < batch.nRows && (size_t)(batch.rows[i].querySeqId - batch.firstSeqCounter) < r) i++;
+        rowBegin[r] = i;
       }
     }
     // per CHUNK of 64 consecutive reads, not per read: one text buffer, one result vector, one counter (a hundred thousand small
@@ -487,9 +524,11 @@ class Map {
         int mappedHere = 0;
         for (size_t r = ci * chunk; r < std::min(nReads, (ci + 1) * chunk); r++) {
           const offset_t len = (offset_t)(batch.in.offs[r + 1] - batch.in.offs[r]);
-          if (len < param.kmerSize || recBegin[r] == recBegin[r + 1]) continue;
+          const bool hasRows = batch.nRows && rowBegin[r] != rowBegin[r + 1];
+          if (len < param.kmerSize || (recBegin[r] == recBegin[r + 1] && !hasRows)) continue;
           one.clear();
-          post.mapModuleFromRecords(batch.recs + recBegin[r], batch.recs + recBegin[r + 1], len, one);
+          if (hasRows) post.finishRows(batch.rows + rowBegin[r], batch.rows + rowBegin[r + 1], len, one);
+          else post.mapModuleFromRecords(batch.recs + recBegin[r], batch.recs + recBegin[r + 1], len, one);
           if (one.empty()) continue;
           mappedHere++;
           if (reportNow) post.appendReadMappings(one, batch.in.names[r], text);

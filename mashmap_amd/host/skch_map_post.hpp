@@ -218,6 +218,12 @@ class MapPost {
 
   // the tail of mapModule (:679-714): chaining, weak-chain filter, plane-sweep filter, sanity checks
   void finishRead(MappingResultsVector_t& unfiltered, offset_t len, bool split_mapping, MappingResultsVector_t& out) const {
+    chainAndFilter(unfiltered, len, split_mapping);
+    out.swap(unfiltered);
+    reportSteps(len, out);
+  }
+  // ... its first half, up to and including filterByGroup (:679-702): what mm_chain_reads computes on the device (mm_chain_core.h)
+  void chainAndFilter(MappingResultsVector_t& unfiltered, offset_t len, bool split_mapping) const {
     const int n_mappings = (int)(len < param.segLength ? param.numMappingsForShortSequence : param.numMappingsForSegment) - 1;
     if (split_mapping && param.mergeMappings) {
       mergeMappingsInRange(unfiltered, param.chain_gap);
@@ -228,10 +234,46 @@ class MapPost {
       filterByGroup(unfiltered, tmp, n_mappings, false);
       unfiltered = std::move(tmp);
     }
-    out.swap(unfiltered);
+  }
+  // ... and its second half (:703-713): per-record steps
+  void reportSteps(offset_t len, MappingResultsVector_t& out) const {
     if (param.filterLengthMismatches) filterFalseHighIdentity(out);
     mappingBoundarySanityCheck(len, out);
     sparsifyMappings(out);
+  }
+
+  // the parameter block mm_set_chain_tables takes for these parameters (include/mashmap_hip.h: mm_chain_params)
+  mm_chain_params chainParams() const {
+    mm_chain_params c{};
+    c.chainGap = (int32_t)param.chain_gap;
+    c.minMerged = (int32_t)std::floor(param.block_length / param.segLength);
+    c.secondaryShort = (int32_t)param.numMappingsForShortSequence - 1;
+    c.secondarySegment = (int32_t)param.numMappingsForSegment - 1;
+    c.merge = param.mergeMappings ? 1 : 0;
+    c.filter = (param.filterMode == filter::MAP || param.filterMode == filter::ONETOONE) ? MM_CHAIN_FILTER_QUERY : MM_CHAIN_FILTER_NONE;
+    c.kmerComplexityThreshold = param.kmerComplexityThreshold;
+    return c;
+  }
+
+  // One read's rows of mm_chain_reads [b, e) -- its mappings as filterByGroup leaves them -- to reported mappings: the fields of the
+  // row, the identity's upper bound of the row's (conservedSketches, sketchSize) from the cache, then the per-record steps above.
+  // rows + finishRows == mapModuleFromRecords on the read's records.
+  void finishRows(const mm_chain_row* b, const mm_chain_row* e, offset_t len, MappingResultsVector_t& out) const {
+    out.clear();
+    for (const mm_chain_row* r = b; r != e; ++r) {
+      float mash_dist;
+      MappingResult res{};
+      (void)identityOf(r->conservedSketches, r->sketchSize, &mash_dist);
+      res.nucIdentityUpperBound = identityUpperBound(mash_dist, r->conservedSketches, r->sketchSize);
+      res.nucIdentity = r->nucIdentity;
+      res.queryLen = r->queryLen; res.queryStartPos = r->queryStartPos; res.queryEndPos = r->queryEndPos;
+      res.refSeqId = r->refSeqId; res.refStartPos = r->refStartPos; res.refEndPos = r->refEndPos;
+      res.querySeqId = r->querySeqId; res.sketchSize = r->sketchSize; res.conservedSketches = r->conservedSketches;
+      res.blockLength = r->blockLength; res.approxMatches = r->approxMatches; res.strand = (strand_t)r->strand;
+      res.kmerComplexity = r->kmerComplexity; res.n_merged = r->n_merged; res.splitMappingId = r->splitMappingId;
+      out.push_back(res);
+    }
+    reportSteps(len, out);
   }
 
   // identity of a locus sharing `shared` of Qs sketch elements (:1211-1213); a function of two small integers, cached like the bound
@@ -244,7 +286,19 @@ class MapPost {
   // mapModule (:570-714) for one read from the device's candidate mappings [b, e) (include/mashmap_hip.h: mm_mapping): the read's
   // records, fragment-major, inside a fragment in doL2Mapping's push order -- i.e. l2Mappings of mapSingleQueryFrag before its sort
   void mapModuleFromRecords(const mm_mapping* b, const mm_mapping* e, offset_t len, MappingResultsVector_t& out) const {
-    MappingResultsVector_t unfiltered, l2Mappings;
+    MappingResultsVector_t unfiltered;
+    const bool split_mapping = unfilteredFromRecords(b, e, len, unfiltered);
+    finishRead(unfiltered, len, split_mapping, out);
+  }
+  // ... stopped behind filterByGroup: what one read's rows of mm_chain_reads are compared with (tests/hostlogic/chain_check.cpp)
+  void chainedFromRecords(const mm_mapping* b, const mm_mapping* e, offset_t len, MappingResultsVector_t& out) const {
+    out.clear();
+    const bool split_mapping = unfilteredFromRecords(b, e, len, out);
+    chainAndFilter(out, len, split_mapping);
+  }
+  // ... its first part: the records as MappingResults, every fragment's gated and sorted as mapSingleQueryFrag leaves them; returns split_mapping
+  bool unfilteredFromRecords(const mm_mapping* b, const mm_mapping* e, offset_t len, MappingResultsVector_t& unfiltered) const {
+    MappingResultsVector_t l2Mappings;
     const bool split_mapping = param.split && len > param.segLength;
     for (const mm_mapping* p = b; p != e;) {
       const mm_mapping* q = p;
@@ -283,7 +337,7 @@ class MapPost {
       }
       p = q;
     }
-    finishRead(unfiltered, len, split_mapping, out);
+    return split_mapping;
   }
 
   // ------------------------------------------------------------------------------------------------------------------

@@ -28,6 +28,14 @@ def host_lib():
         lib.mmh_post_batch.restype = C.c_int64
         lib.mmh_post_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_size_t, C.c_int32, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_size_t]
+        # the same stage behind mm_chain_reads (rows + left-over records), and the host's own rows to check the device's against
+        lib.mmh_post_chained.restype = C.c_int64
+        lib.mmh_post_chained.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_int,
+                                         C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mmh_chain_rows.restype = C.c_int64
+        lib.mmh_chain_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_int, C.c_void_p, C.c_size_t]
         _host = lib
     return _host
 
