@@ -354,9 +354,12 @@ int mm_mappings_device(const mm_ctx* ctx, const mm_mapping** dMappings, size_t* 
  * filterWeakMappings (:423), filterByGroup on the query axis (:504-561) with the plane sweep of filter.hpp:36-160 --, one mm_chain_row per
  * surviving mapping.  The caller starts the stage explicitly after mm_map_fragments; nothing of that call changes.  The restatement is
  * mashmap_amd/csrc/mm_chain_core.h (one function per read, compiled for the host by tests/hostlogic/chain_check.cpp); DESIGN.md
- * section 6 has the argument why rows equal the host's bit for bit.  A read with more than MM_CHAIN_MAX_RECORDS records is not taken:
- * up to that size libstdc++'s std::sort is a stable insertion sort, which a stable sort reproduces; beyond, the representative of a
- * chain depends on introsort's moves.  Its records are handed over untouched (the left-over array) and the host finishes it as before.
+ * section 6 has the argument why rows equal the host's bit for bit.  A read with more than MM_CHAIN_MAX_RECORDS records is not taken
+ * by the one-thread-per-read kernel: up to that size libstdc++'s std::sort is a stable insertion sort; beyond, the representative of a
+ * chain depends on introsort's moves.  Its records are handed over untouched (the left-over array) and the host finishes it as before
+ * -- unless MM_OPT_CHAIN_LONG is set: then a read of 17 .. MM_CHAIN_LONG_MAX_RECORDS (512) records goes to k_chain_reads_long, a wave
+ * per read with the working set in LDS, whose sorts are std::sort restated move for move (mashmap_amd/csrc/mm_stdsort.h), and only
+ * reads above 512 records are handed over.
  * What stays on the host, applied to the rows: filterFalseHighIdentity, mappingBoundarySanityCheck, sparsifyMappings,
  * nucIdentityUpperBound and the PAF text (MapPost::finishRows).
  *
@@ -377,9 +380,12 @@ int mm_mappings_device(const mm_ctx* ctx, const mm_mapping** dMappings, size_t* 
  * mm_chain_counts: *offered = reads with at least one record, *finished = those of them the kernel took, *rows, *leftover = entries of
  * the two arrays.  Rows are in read order, inside a read in the order filterByGroup leaves them; the left-over mm_mapping records are
  * the handed-over reads', read-major, in their original order.  The device addresses are valid until the next mm_chain_reads or map call.
+ * mm_chain_long_counts: *offered = reads of the batch with more than MM_CHAIN_MAX_RECORDS records, *finished = those of them
+ * k_chain_reads_long wrote rows for (0 without MM_OPT_CHAIN_LONG); MM_ERR_STATE under the conditions of mm_chain_counts.
  * Purely additive: MM_ABI_VERSION stays 2.
  */
-#define MM_CHAIN_MAX_RECORDS 16
+#define MM_CHAIN_MAX_RECORDS 16          /* what k_chain_reads (one thread per read, std::sort == __insertion_sort) takes */
+#define MM_CHAIN_LONG_MAX_RECORDS 512
 #define MM_CHAIN_MAX_SKETCH 2048
 #define MM_CHAIN_MAX_GAP (1 << 25)
 enum { MM_CHAIN_FILTER_NONE = 0, MM_CHAIN_FILTER_QUERY = 1 };
@@ -402,6 +408,7 @@ int mm_stat_identity_table(int sketchSize, int k, float* identity);   /* (sketch
 int mm_set_chain_tables(mm_ctx* ctx, const mm_chain_params* params, const float* identity, size_t stride);
 int mm_chain_reads(mm_ctx* ctx);
 int mm_chain_counts(const mm_ctx* ctx, size_t* offered, size_t* finished, size_t* rows, size_t* leftover);
+int mm_chain_long_counts(const mm_ctx* ctx, uint64_t* offered, uint64_t* finished);
 int mm_chain_download(mm_ctx* ctx, mm_chain_row* out, size_t cap, size_t* n);
 int mm_chain_leftover_download(mm_ctx* ctx, mm_mapping* out, size_t cap, size_t* n);
 int mm_chain_device(const mm_ctx* ctx, const mm_chain_row** dRows, size_t* nRows, const mm_mapping** dLeftover, size_t* nLeftover);
@@ -446,8 +453,13 @@ int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
  * loci, same order.  Bit 1 (value 2; 3 with bit 0): split batches take the literal L2 route at ANY sketch size, so that both kernels can be
  * checked at small sketches; such a context runs sized passes only.  Batches with a read longer than segLength are untouched at every
  * value.  Purely additive: MM_ABI_VERSION stays 2.
+ * MM_OPT_CHAIN_LONG (default 0): with 1, mm_chain_reads no longer hands over a read of 17 .. MM_CHAIN_LONG_MAX_RECORDS records: the count
+ * pass lists such reads, and k_chain_reads_long (one wave per read, working set in LDS) chains and filters them; their rows stand in
+ * read order among the others'.  Reads above 512 records are handed over as before -- the single hand-over cause left.  Rows of every
+ * other read, the refusals and the one host wait of the stage are unchanged; mm_chain_long_counts reports what the kernel took.  Purely
+ * additive: MM_ABI_VERSION stays 2.
  */
-enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6, MM_OPT_L2_LARGE_WAVE = 7 };
+enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6, MM_OPT_L2_LARGE_WAVE = 7, MM_OPT_CHAIN_LONG = 8 };
 int mm_set_option(mm_ctx* ctx, int option, int value);
 /* sorted interval points of fragment f after the seqId filters of computeMap.hpp:891-896 (needs MM_OPT_KEEP_POINTS; (seqId,pos,side) only, hash = 0).
  * Under MM_FLAG_SKIP_PREFIX the points are in HBM without that option too -- unless MM_OPT_L1_GROUP_FUSED is set: then MM_ERR_STATE. */

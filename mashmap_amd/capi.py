@@ -16,6 +16,7 @@ MM_FLAG_HG_FILTER, MM_FLAG_SKIP_SELF, MM_FLAG_SKIP_PREFIX, MM_FLAG_LOWER_TRIANGU
 MM_OPT_KEEP_POINTS, MM_OPT_KEEP_FULL_INDEX, MM_OPT_RESERVE_FRAGMENTS, MM_OPT_L1_GROUP_STREAM, MM_OPT_L2_WINDOW_WAVE = 1, 2, 3, 4, 5
 MM_OPT_L1_GROUP_FUSED = 6
 MM_OPT_L2_LARGE_WAVE = 7
+MM_OPT_CHAIN_LONG = 8
 # bits of Context.pass_redo_cause() (include/mashmap_hip.h: MM_REDO_*)
 (MM_REDO_POINTS, MM_REDO_L1, MM_REDO_L2_LOCI, MM_REDO_L2_SLOTS, MM_REDO_L2_STREAM, MM_REDO_L2_OPS, MM_REDO_L2_LIST, MM_REDO_L2_CANDS,
  MM_REDO_MAPPINGS, MM_REDO_NO_STREAM_BUFFER) = (1 << i for i in range(10))
@@ -41,6 +42,7 @@ class ChainParams(C.Structure):
 
 
 MM_CHAIN_MAX_RECORDS, MM_CHAIN_MAX_SKETCH, MM_CHAIN_MAX_GAP = 16, 2048, 1 << 25
+MM_CHAIN_LONG_MAX_RECORDS = 512      # with MM_OPT_CHAIN_LONG: what k_chain_reads_long takes
 MM_CHAIN_FILTER_NONE, MM_CHAIN_FILTER_QUERY = 0, 1
 # mm_chain_row: one mapping of a read as filterByGroup leaves it (mm_chain_reads)
 CHAIN_ROW_DT = np.dtype([("querySeqId", "<i4"), ("queryLen", "<i4"), ("queryStartPos", "<i4"), ("queryEndPos", "<i4"), ("refSeqId", "<i4"),
@@ -162,6 +164,7 @@ def load():
         "mm_set_chain_tables": (C.c_int, [vp, C.POINTER(ChainParams), vp, sz]),
         "mm_chain_reads": (C.c_int, [vp]),
         "mm_chain_counts": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+        "mm_chain_long_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_chain_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_leftover_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
@@ -193,7 +196,7 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
            "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
            "mm_stat_identity_table", "mm_set_chain_tables", "mm_chain_reads", "mm_chain_counts", "mm_chain_download",
-           "mm_chain_leftover_download", "mm_chain_device"]
+           "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts"]
 
 
 def stat_sketch_cutoffs(sketchSize, k, hg=True):
@@ -593,6 +596,18 @@ class Context:
         v = [C.c_size_t() for _ in range(4)]
         self._ck(self.lib.mm_chain_counts(self.h, *[C.byref(x) for x in v]), "mm_chain_counts")
         return dict(zip(("offered", "finished", "rows", "leftover"), (int(x.value) for x in v)))
+
+    def chain_long(self, on=True):
+        """MM_OPT_CHAIN_LONG: chain_reads() no longer hands over a read of 17 .. MM_CHAIN_LONG_MAX_RECORDS records; the wave-per-read
+        k_chain_reads_long chains and filters it.  Reads above 512 records are handed over as before"""
+        self._ck(self.lib.mm_set_option(self.h, MM_OPT_CHAIN_LONG, 1 if on else 0), "mm_set_option")
+
+    def chain_long_counts(self):
+        """dict(offered, finished) of the last chain_reads(): reads with more than 16 records, and those of them k_chain_reads_long
+        wrote rows for (0 without chain_long())"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.mm_chain_long_counts(self.h, C.byref(a), C.byref(b)), "mm_chain_long_counts")
+        return dict(offered=int(a.value), finished=int(b.value))
 
     def chain_rows(self):
         n = self.chain_counts()["rows"]

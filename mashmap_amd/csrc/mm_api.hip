@@ -109,6 +109,7 @@ int mm_set_option(mm_ctx* c, int option, int value) {
   if (option == MM_OPT_L1_GROUP_FUSED) { c->l1GroupFused = value != 0; return MM_OK; }
   if (option == MM_OPT_L2_WINDOW_WAVE) { c->l2WindowWave = value != 0; return MM_OK; }
   if (option == MM_OPT_L2_LARGE_WAVE) { c->l2LargeWave = value & 3; return MM_OK; }
+  if (option == MM_OPT_CHAIN_LONG) { c->chainLong = value != 0; return MM_OK; }
   c->err = "mm_set_option: unknown option"; return MM_ERR_ARG;
 }
 

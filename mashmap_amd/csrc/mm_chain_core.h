@@ -7,17 +7,28 @@
 //   Map::filterByGroup         both sorts, the query-axis plane sweep                   :504-561, src/map/include/filter.hpp:36-160
 //
 // i.e. MapPost::finishRead (mashmap_amd/host/skch_map_post.hpp) up to and including filterByGroup, on the integers of mm_mapping.
-// Shared by the kernel (k_chain_reads, mm_chain.hip) and by the CPU check (tests/hostlogic/chain_check.cpp), which runs it beside
-// MapPost on generated reads and compares every field bit for bit.  Compiles for the host (g++) and for the device (hipcc).
+// Shared by the kernels (k_chain_reads, k_chain_reads_long, mm_chain.hip) and by the CPU checks (tests/hostlogic/chain_check.cpp,
+// chain_long_check.cpp), which run it beside MapPost on generated reads and compare every field bit for bit.  Compiles for the host (g++)
+// and for the device (hipcc).
+//
+// Two entry points over one body (mm_chain_read_t, a template over the working set): mm_chain_read takes a read of at most
+// MM_CHAIN_MAX_RECORDS (16) records with its working set on the stack and 8-bit ids; mm_chain_read_long takes one of at most
+// MM_CHAIN_LONG_MAX_RECORDS (512) with a working set the caller provides (the kernel's is in LDS) and 16-bit ids.  The body is made of the
+// steps the wave-per-read kernel calls one by one: mm_chain_prepare (one record), mm_chain_partner (the best partner of member i),
+// mm_chain_unite, mm_chain_finish_chain, mm_chain_keep, mm_chain_filter with mm_chain_sweep, mm_chain_emit (one row).
 //
 // Why the result is the host's, bit for bit:
-//   sorts     The function takes a read only when it has at most MM_CHAIN_MAX_RECORDS (16) records.  libstdc++'s std::sort of 16 or
-//             fewer elements is __insertion_sort alone (_S_threshold), which is stable; mm_chain_sort is a stable insertion sort by
-//             the same key from the same input order, so all five sorts of the tail come out the same -- including the one by
-//             splitMappingId, whose first member of every chain becomes the chain's representative (conservedSketches of the PAF
-//             line).  The 2n events of the sweep and the (dist + score, id) pairs are totally ordered tuples: any sort does.
+//   sorts     All five order-sensitive sorts of the tail -- per fragment, before the pair loop, by splitMappingId, the two of
+//             filterByGroup -- go through mm_std_sort (mm_stdsort.h): libstdc++'s std::sort restated comparison for comparison and move
+//             for move, from the same input order with the same key.  Up to 16 elements that is __insertion_sort alone, which is stable;
+//             beyond it is introsort, whose order among equal keys is neither the input's nor any stable sort's, and it decides the chain's
+//             representative: every member of a chain ties in the sort by splitMappingId, and the first of them afterwards gives
+//             conservedSketches, sketchSize and approxMatches of the PAF line.  tests/hostlogic/stdsort_check.cpp compares the restated
+//             sort with std::sort call for call.  The 2n events of the sweep and the (dist + score, id) pairs are totally ordered tuples:
+//             any sort does (the events are heap-sorted, the pair's minimum is taken in passing).
 //   status    The sweep's std::set finds two mappings equivalent when identity, queryStartPos and refSeqId agree: insert is then a
-//             no-op and erase(id) removes whichever element is equivalent.  A sorted array of at most 16 ids with the same two rules.
+//             no-op and erase(id) removes whichever element is equivalent.  A sorted array of at most m ids (m <= 512) with the same two
+//             rules.
 //   identity  a function of (sketchSize, conservedSketches): the host's own floats arrive as a table.
 //   chaining  chainGap <= 1 << 25 (mm_chain_params_ok).  A pair that passes dist < max_dist has |query_dist|, |ref_dist| < 2^25, their
 //             squares and the sum are integers below 2^53, (query_dist - ref_dist)^2 one below 2^52: exact in a double, with or without
@@ -25,10 +36,13 @@
 //             fast-math).  For a pair that fails the test nothing computed is used.
 //   averages  accumulated in double from 0.0 in member order, as std::accumulate does.  The identity's sum is double + float on the host
 //             too.  The complexity's is not: the host's lambda adds the long double member kmerComplexity in 80 bits and rounds the sum
-//             to double, this function adds in double.  ASSUMPTION, not enforced: the complexities of one chain's members lie within a
-//             factor 2^24 of each other.  They are floats, at most 16 of them, so every partial sum then spans at most 24 + 24 + 4 = 52
-//             bits and is exact in a double and in an 80-bit long double alike; the one rounding is the division.  Beyond that factor a
-//             sum rounds once here and twice on the host, and the two can differ in the last bit.  Complexity is
+//             to double at every step, this function adds in double.  The two agree whenever the 80-bit sum is exact, for then the host
+//             rounds once, to double, as this function does.  ASSUMPTION, not enforced: the complexities of one chain's members lie
+//             within a factor 2^24 of each other.  They are floats (24 bits), at most 2^9 of them, so every exact partial sum spans at
+//             most 24 + 24 + 9 + 1 = 58 bits, at most the 64 of the 80-bit format: the host's additions are exact, its conversion to
+//             double is the one rounding of the step -- and the double the next step starts from is the same on both sides, by
+//             induction from 0.0.  (With at most 16 members the span is 24 + 24 + 4 = 52 bits and nothing rounds before the division.)
+//             Beyond the factor a sum rounds once here and twice on the host, and the two can differ in the last bit.  Complexity is
 //             rawSketchSize / (maxHash / 2^64) / (2 (len - k + 1)): a factor 2^24 between two fragments of a read needs a bottom-s sketch
 //             whose LARGEST hash lies below 2^40 -- s hashes out of 2^64 all that small -- which no sequence a sketch is taken of yields.
 //             tests/hostlogic/chain_check.cpp draws maxHash over the whole assumed range (2^40 .. 2^64).
@@ -36,6 +50,7 @@
 #pragma once
 #include <math.h>
 #include "mm_heap.h"
+#include "mm_stdsort.h"
 #include "../../include/mashmap_hip.h"
 
 // what the function needs beside the caller's parameter block
@@ -83,38 +98,244 @@ MM_HD double mm_chain_sqrt(double x) {
 #endif
 }
 
-// one read's working set: the MappingResult fields the tail reads and writes, per record
-struct mm_chain_work {
-  int32_t qs[MM_CHAIN_MAX_RECORDS], qe[MM_CHAIN_MAX_RECORDS], rs[MM_CHAIN_MAX_RECORDS], re[MM_CHAIN_MAX_RECORDS];
-  int32_t sid[MM_CHAIN_MAX_RECORDS], cons[MM_CHAIN_MAX_RECORDS], sk[MM_CHAIN_MAX_RECORDS], blk[MM_CHAIN_MAX_RECORDS], approx[MM_CHAIN_MAX_RECORDS];
-  int32_t nm[MM_CHAIN_MAX_RECORDS], smid[MM_CHAIN_MAX_RECORDS];
-  float ident[MM_CHAIN_MAX_RECORDS];
-  double kc[MM_CHAIN_MAX_RECORDS];
-  int8_t strand[MM_CHAIN_MAX_RECORDS], discard[MM_CHAIN_MAX_RECORDS];
+// One read's working set: the MappingResult fields the tail reads and writes, per record, the order v, and the scratch of the two
+// phases that need any -- the union-find and the partners of mergeMappingsInRange, then the events and the status set of the sweep,
+// which share their bytes.  CAP 16 with int8_t ids: 1.2 KB; CAP 512 with int16_t ids: 78 bytes a record, 39 KB.
+template <int CAP_, class ID_>
+struct mm_chain_work_t {
+  enum : int { CAP = CAP_ };
+  typedef ID_ ID;
+  int32_t qs[CAP_], qe[CAP_], rs[CAP_], re[CAP_];
+  int32_t sid[CAP_], cons[CAP_], sk[CAP_], blk[CAP_], approx[CAP_];
+  int32_t nm[CAP_], smid[CAP_];
+  float ident[CAP_];
+  double kc[CAP_];
+  int8_t strand[CAP_], discard[CAP_];
+  ID_ v[CAP_];
+  union {
+    struct { ID_ parent[CAP_], best[CAP_]; int8_t rnk[CAP_]; } uf;         // rank <= lg CAP
+    struct { uint64_t ev[2 * CAP_]; ID_ status[CAP_]; } sw;
+  };
 };
-
-// stable insertion sort of ids v[b, e) by less(x, y) -- what std::sort is for at most 16 elements
-template <class Less>
-MM_HD void mm_chain_sort(int8_t* v, int b, int e, Less less) {
-  for (int i = b + 1; i < e; i++) {
-    const int8_t x = v[i];
-    int j = i;
-    while (j > b && less(x, v[j - 1])) { v[j] = v[j - 1]; j--; }
-    v[j] = x;
-  }
-}
+typedef mm_chain_work_t<MM_CHAIN_MAX_RECORDS, int8_t> mm_chain_work;
+typedef mm_chain_work_t<MM_CHAIN_LONG_MAX_RECORDS, int16_t> mm_chain_work_long;
 
 // res.approxMatches = std::round(res.nucIdentity * res.blockLength / 100.0): a float product, a double quotient (:1247, :1661)
 MM_HD int32_t mm_chain_approx(float ident, int32_t blk) { return (int32_t)round((double)(ident * (float)blk) / 100.0); }
 
-// Finishes the read of length readLen whose records are recs[0, n), in mm_mappings_download's order.  Writes the surviving mappings to
-// out (when non-null; up to n of them), in the order filterByGroup leaves them, and returns their number; -1 for n above
-// MM_CHAIN_MAX_RECORDS (the read is not taken: the single hand-over cause), MM_CHAIN_BAD_RECORD for a record outside the identity table.
-MM_HD int mm_chain_read(const mm_chain_env& E, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out) {
-  if (n > MM_CHAIN_MAX_RECORDS) return -1;
-  if (n <= 0) return 0;
-  mm_chain_work W;
-  int8_t v[MM_CHAIN_MAX_RECORDS];
+// the three keys the tail sorts by, as less(x, y) over ids
+template <class W> MM_HD bool mm_chain_less_ref(const W& w, int x, int y) { return w.sid[x] != w.sid[y] ? w.sid[x] < w.sid[y] : w.rs[x] < w.rs[y]; }   // :799-800, filterByGroup's first
+template <class W> MM_HD bool mm_chain_less_merge(const W& w, int x, int y) {
+  if (w.sid[x] != w.sid[y]) return w.sid[x] < w.sid[y];
+  if (w.rs[x] != w.rs[y]) return w.rs[x] < w.rs[y];
+  return w.qs[x] < w.qs[y];
+}
+template <class W> MM_HD bool mm_chain_less_query(const W& w, int x, int y) {
+  if (w.qs[x] != w.qs[y]) return w.qs[x] < w.qs[y];
+  if (w.sid[x] != w.sid[y]) return w.sid[x] < w.sid[y];
+  return w.rs[x] < w.rs[y];
+}
+// a working set of at most 16 records never leaves __insertion_sort: its kernel does not carry introsort's range stack
+template <class W, class Less>
+MM_HD void mm_chain_sort(W& w, int b, int e, Less less) {
+  if constexpr (W::CAP <= MM_STDSORT_THRESHOLD) mm_std_insertion_sort(w.v, b, e, less);
+  else mm_std_sort(w.v + b, e - b, less);
+}
+template <class W> MM_HD void mm_chain_sort_ref(W& w, int b, int e) { mm_chain_sort(w, b, e, [&w](int x, int y) { return mm_chain_less_ref(w, x, y); }); }
+template <class W> MM_HD void mm_chain_sort_merge(W& w, int m) { mm_chain_sort(w, 0, m, [&w](int x, int y) { return mm_chain_less_merge(w, x, y); }); }
+template <class W> MM_HD void mm_chain_sort_smid(W& w, int m) { mm_chain_sort(w, 0, m, [&w](int x, int y) { return w.smid[x] < w.smid[y]; }); }
+template <class W> MM_HD void mm_chain_sort_query(W& w, int m) { mm_chain_sort(w, 0, m, [&w](int x, int y) { return mm_chain_less_query(w, x, y); }); }
+
+// ---- prepare one record: record r of a fragment of length Qlen and complexity kc that passed the gate becomes member x (v[x] = x).
+// qs / qe are the read's coordinates at once (:632-636 sets them behind the fragment's sort, to the same values for every record of the
+// fragment).  false: the record names an entry outside the identity table -- not a hand-over cause but an error (k_l2_select writes
+// shared <= Qs <= sketchSize): nothing is read outside the table, and the caller reports it (mm_chain_reads: MM_ERR_STATE, "corrupt record")
+template <class W>
+MM_HD bool mm_chain_prepare(const mm_chain_env& E, W& w, int x, const mm_mapping& r, bool split, float kc) {
+  if ((uint32_t)r.sketchSize >= (uint32_t)E.stride || (uint32_t)r.conservedSketches >= (uint32_t)E.stride) return false;
+  const int32_t Qlen = r.fragLen;
+  w.v[x] = (typename W::ID)x;
+  w.ident[x] = E.identity[(size_t)r.sketchSize * (size_t)E.stride + (size_t)r.conservedSketches];
+  w.rs[x] = r.refStartPos; w.re[x] = r.refStartPos + Qlen;
+  w.qs[x] = split ? r.fragStart : 0; w.qe[x] = w.qs[x] + Qlen;
+  w.sid[x] = r.refSeqId; w.sk[x] = r.sketchSize; w.cons[x] = r.conservedSketches;
+  w.blk[x] = Qlen;                                                 // max(refEnd - refStart, queryEnd - queryStart)
+  w.approx[x] = mm_chain_approx(w.ident[x], Qlen);
+  w.strand[x] = (int8_t)r.strand; w.kc[x] = (double)kc;
+  w.nm[x] = 0; w.smid[x] = 0; w.discard[x] = 0;
+  return true;
+}
+
+// ---- the pair loop's inner part for member i of the sorted order: the position j > i of the partner with the least (dist + score, j), -1
+// when no pair passes dist < max_dist.  Reads the working set only: the m calls are independent of each other.
+template <class W>
+MM_HD int mm_chain_partner(const W& w, int m, int i, int max_dist) {
+  const int a = w.v[i];
+  bool have = false; double bestKey = 0; int bestJ = -1;
+  for (int j = i + 1; j < m; j++) {
+    const int b = w.v[j];
+    if (w.sid[b] != w.sid[a] || w.rs[b] > w.re[a] + max_dist) break;
+    if (w.strand[b] != w.strand[a]) continue;
+    const int ref_dist = w.rs[b] - w.re[a];
+    int query_dist;
+    if (w.strand[a] == 1 && w.qs[a] <= w.qs[b]) query_dist = w.qs[b] - w.qe[a];
+    else if (w.strand[a] != 1 && w.qe[a] >= w.qe[b]) query_dist = w.qs[a] - w.qe[b];
+    else continue;                                                 // dist stays at the double's maximum
+    const double qd = (double)query_dist, rd = (double)ref_dist, df = (double)(query_dist - ref_dist);
+    const double dist = mm_chain_sqrt(qd * qd + rd * rd);
+    const double score = df * df;
+    if (dist < (double)max_dist) {
+      const double key = dist + score;
+      if (!have || key < bestKey) { have = true; bestKey = key; bestJ = j; }     // the front of the sorted (key, id) pairs: ids ascend with j
+    }
+  }
+  return bestJ;
+}
+
+template <class W>
+MM_HD int mm_chain_find(W& w, int x) {
+  while (w.uf.parent[x] != x) { w.uf.parent[x] = w.uf.parent[w.uf.parent[x]]; x = w.uf.parent[x]; }
+  return x;
+}
+
+// ---- DisjointSets::unite (dset64.hpp:93-125) of positions i and j
+template <class W>
+MM_HD void mm_chain_unite(W& w, int i, int j) {
+  int x = mm_chain_find(w, i), y = mm_chain_find(w, j);
+  if (x == y) return;
+  if (w.uf.rnk[x] > w.uf.rnk[y] || (w.uf.rnk[x] == w.uf.rnk[y] && x < y)) { const int t = x; x = y; y = t; }     // x goes under y
+  w.uf.parent[x] = (typename W::ID)y;
+  if (w.uf.rnk[x] == w.uf.rnk[y]) w.uf.rnk[y]++;
+}
+
+// ---- finish one chain: v[it, end) are its members in the order the sort by splitMappingId left them, v[it] its representative.
+// Extents, the two averages in member order, block length, approxMatches (from the representative's own identity), n_merged.  Writes the
+// representative's entries only, and no other chain reads them.
+template <class W>
+MM_HD void mm_chain_finish_chain(W& w, int it, int end) {
+  const int rep = w.v[it];
+  const float repIdent = w.ident[rep];
+  int32_t qs = w.qs[rep], qe = w.qe[rep], rs = w.rs[rep], re = w.re[rep];
+  double sumI = 0.0, sumK = 0.0;
+  for (int j = it; j < end; j++) {
+    const int x = w.v[j];
+    qs = w.qs[x] < qs ? w.qs[x] : qs;
+    rs = w.rs[x] < rs ? w.rs[x] : rs;
+    qe = w.qe[x] > qe ? w.qe[x] : qe;
+    re = w.re[x] > re ? w.re[x] : re;
+    sumI = sumI + (double)w.ident[x];
+    sumK = sumK + w.kc[x];
+  }
+  w.qs[rep] = qs; w.qe[rep] = qe; w.rs[rep] = rs; w.re[rep] = re;
+  const int32_t dr = re - rs, dq = qe - qs;
+  w.blk[rep] = dr > dq ? dr : dq;
+  w.approx[rep] = mm_chain_approx(repIdent, w.blk[rep]);
+  w.nm[rep] = end - it;
+  w.ident[rep] = (float)(sumI / (double)w.nm[rep]);
+  w.kc[rep] = sumK / (double)w.nm[rep];
+}
+
+// ---- the sweep: filterQueryAxis over v[0, m) (m > 1), sorted by (queryStartPos, refSeqId, refStartPos); ids of the sweep are positions
+// in v.  An event is (pos, BEGIN = 1 / END = 2, id) in one word; marks the survivors with discard == 0.
+template <class W>
+MM_HD void mm_chain_sweep(W& w, int m, int secondaryToKeep) {
+  uint64_t* ev = w.sw.ev;
+  for (int i = 0; i < m; i++) {
+    w.discard[w.v[i]] = 1;
+    ev[2 * i] = ((uint64_t)((uint32_t)w.qs[w.v[i]] ^ 0x80000000u) << 12) | (1u << 10) | (uint64_t)i;
+    ev[2 * i + 1] = ((uint64_t)((uint32_t)w.qe[w.v[i]] ^ 0x80000000u) << 12) | (2u << 10) | (uint64_t)i;
+  }
+  const int nE = 2 * m;
+  mm_std_heap_sort(ev, 0, nE, [](uint64_t x, uint64_t y) { return x < y; });     // distinct words: any sort does
+  // better(x, y): std::tie(identity as double, queryStartPos, refSeqId) of x > that of y
+  auto better = [&w](int x, int y) {
+    const int a = w.v[x], b = w.v[y];
+    if (w.ident[a] != w.ident[b]) return w.ident[a] > w.ident[b];
+    if (w.qs[a] != w.qs[b]) return w.qs[a] > w.qs[b];
+    return w.sid[a] > w.sid[b]; };
+  typename W::ID* status = w.sw.status;
+  int nS = 0;
+  for (int i = 0; i < nE;) {
+    int j = i;
+    while (j < nE && (ev[j] >> 12) == (ev[i] >> 12)) j++;
+    for (int e = i; e < j; e++) {
+      const int id = (int)(ev[e] & 1023u);
+      int at = 0;
+      while (at < nS && better(status[at], id)) at++;              // lower bound
+      const bool equivalent = at < nS && !better(id, status[at]);
+      if (((ev[e] >> 10) & 3u) == 1u) {
+        if (!equivalent) { for (int t = nS; t > at; t--) status[t] = status[t - 1]; status[at] = (typename W::ID)id; nS++; }
+      } else if (equivalent) {
+        for (int t = at; t + 1 < nS; t++) status[t] = status[t + 1];
+        nS--;
+      }
+    }
+    if (nS > 0) {                                                  // markGood (filter.hpp:77-95)
+      const float best = w.ident[w.v[status[0]]];
+      int kept = 0;
+      for (int t = 0; t < nS; t++) {
+        const int x = w.v[status[t]];
+        const bool worseOrSeen = best > w.ident[x] || w.discard[x] == 0;
+        if (worseOrSeen && kept > secondaryToKeep) break;
+        w.discard[x] = 0;
+        ++kept;
+      }
+    }
+    i = j;
+  }
+}
+
+// ---- behind the chains' extents: the representatives (the first of every run of equal splitMappingId in v[0, m)) in order, then
+// filterWeakMappings over them; -> new m
+template <class W>
+MM_HD int mm_chain_keep(const mm_chain_env& E, W& w, int m, int32_t queryLen, bool merged) {
+  int k = 0;
+  if (merged) {
+    int32_t last = 0;
+    for (int it = 0; it < m; it++) {
+      const int x = w.v[it];
+      const int32_t id = w.smid[x];
+      if (it == 0 || id != last) w.v[k++] = (typename W::ID)x;
+      last = id;
+    }
+    m = k; k = 0;
+  }
+  for (int i = 0; i < m; i++) if (!(queryLen > w.blk[w.v[i]] && w.nm[w.v[i]] < E.p.minMerged)) w.v[k++] = w.v[i];     // filterWeakMappings
+  return k;
+}
+
+// ---- filterByGroup, query axis, over v[0, m); -> new m
+template <class W>
+MM_HD int mm_chain_filter(const mm_chain_env& E, W& w, int m, int32_t readLen) {
+  if (E.p.filter != MM_CHAIN_FILTER_QUERY) return m;
+  const int secondaryToKeep = (int)(uint16_t)(readLen < E.segLength ? E.p.secondaryShort : E.p.secondarySegment);
+  mm_chain_sort_ref(w, 0, m);
+  mm_chain_sort_query(w, m);
+  if (m > 1) {
+    mm_chain_sweep(w, m, secondaryToKeep);
+    int k = 0;
+    for (int i = 0; i < m; i++) if (w.discard[w.v[i]] == 0) w.v[k++] = w.v[i];
+    m = k;
+  }
+  mm_chain_sort_query(w, m);
+  return m;
+}
+
+// ---- emit one row: member x
+template <class W>
+MM_HD mm_chain_row mm_chain_emit(const W& w, int x, int32_t querySeqId, int32_t queryLen) {
+  mm_chain_row r;
+  r.querySeqId = querySeqId; r.queryLen = queryLen; r.queryStartPos = w.qs[x]; r.queryEndPos = w.qe[x];
+  r.refSeqId = w.sid[x]; r.refStartPos = w.rs[x]; r.refEndPos = w.re[x]; r.strand = w.strand[x];
+  r.conservedSketches = w.cons[x]; r.sketchSize = w.sk[x]; r.blockLength = w.blk[x]; r.approxMatches = w.approx[x];
+  r.n_merged = w.nm[x]; r.splitMappingId = w.smid[x];
+  r.nucIdentity = w.ident[x]; r.pad_ = 0; r.kmerComplexity = w.kc[x];
+  return r;
+}
+
+// the whole tail on one thread, 1 <= n <= W::CAP
+template <class W>
+MM_HD int mm_chain_read_t(const mm_chain_env& E, W& w, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out) {
   int m = 0;
   const bool split = readLen > E.segLength;                       // :583 (MM_FLAG_NO_SPLIT is refused by the caller)
   const int32_t querySeqId = recs[0].querySeqId;
@@ -123,27 +344,11 @@ MM_HD int mm_chain_read(const mm_chain_env& E, const mm_mapping* recs, int n, in
   for (int p = 0; p < n;) {
     int q = p;
     while (q < n && recs[q].fragStart == recs[p].fragStart) q++;
-    const int32_t Qlen = recs[p].fragLen;
-    const float kc = mm_chain_kmer_complexity(recs[p].maxHash, recs[p].rawSketchSize, Qlen, E.kmerSize);
+    const float kc = mm_chain_kmer_complexity(recs[p].maxHash, recs[p].rawSketchSize, recs[p].fragLen, E.kmerSize);
     if (!(kc < E.p.kmerComplexityThreshold)) {                    // :1137
       const int b = m;
-      for (int i = p; i < q; i++) {
-        const mm_mapping& r = recs[i];
-        // a record that names an entry outside the identity table is not a hand-over cause but an error (k_l2_select writes shared <= Qs <=
-        // sketchSize): nothing is read outside the table, and the caller reports it (mm_chain_reads: MM_ERR_STATE, "corrupt record")
-        if ((uint32_t)r.sketchSize >= (uint32_t)E.stride || (uint32_t)r.conservedSketches >= (uint32_t)E.stride) return MM_CHAIN_BAD_RECORD;
-        const int x = m++;
-        v[x] = (int8_t)x;
-        W.ident[x] = E.identity[(size_t)r.sketchSize * (size_t)E.stride + (size_t)r.conservedSketches];
-        W.rs[x] = r.refStartPos; W.re[x] = r.refStartPos + Qlen; W.qs[x] = 0; W.qe[x] = Qlen;
-        W.sid[x] = r.refSeqId; W.sk[x] = r.sketchSize; W.cons[x] = r.conservedSketches;
-        W.blk[x] = Qlen;                                           // max(refEnd - refStart, queryEnd - queryStart)
-        W.approx[x] = mm_chain_approx(W.ident[x], Qlen);
-        W.strand[x] = (int8_t)r.strand; W.kc[x] = (double)kc;
-        W.nm[x] = 0; W.smid[x] = 0; W.discard[x] = 0;
-      }
-      mm_chain_sort(v, b, m, [&W](int x, int y) { return W.sid[x] != W.sid[y] ? W.sid[x] < W.sid[y] : W.rs[x] < W.rs[y]; });   // :799-800
-      if (split) for (int i = b; i < m; i++) { W.qs[v[i]] = recs[p].fragStart; W.qe[v[i]] = recs[p].fragStart + Qlen; }          // :632-636
+      for (int i = p; i < q; i++) if (!mm_chain_prepare(E, w, m++, recs[i], split, kc)) return MM_CHAIN_BAD_RECORD;
+      mm_chain_sort_ref(w, b, m);                                  // :799-800
     }
     p = q;
   }
@@ -152,148 +357,44 @@ MM_HD int mm_chain_read(const mm_chain_env& E, const mm_mapping* recs, int n, in
   // ---- mergeMappingsInRange + filterWeakMappings
   if (split && E.p.merge) {
     if (m >= 2) {
-      const int max_dist = E.p.chainGap;
-      mm_chain_sort(v, 0, m, [&W](int x, int y) {
-        if (W.sid[x] != W.sid[y]) return W.sid[x] < W.sid[y];
-        if (W.rs[x] != W.rs[y]) return W.rs[x] < W.rs[y];
-        return W.qs[x] < W.qs[y]; });
-      int8_t parent[MM_CHAIN_MAX_RECORDS], rnk[MM_CHAIN_MAX_RECORDS];
-      for (int i = 0; i < m; i++) { parent[i] = (int8_t)i; rnk[i] = 0; W.smid[v[i]] = i; }
-      auto find = [&parent](int x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
+      mm_chain_sort_merge(w, m);
+      for (int i = 0; i < m; i++) { w.uf.parent[i] = (typename W::ID)i; w.uf.rnk[i] = 0; w.smid[w.v[i]] = i; }
       for (int i = 0; i < m; i++) {
-        const int a = v[i];
-        bool have = false; double bestKey = 0; int bestJ = 0;
-        for (int j = i + 1; j < m; j++) {
-          const int b = v[j];
-          if (W.sid[b] != W.sid[a] || W.rs[b] > W.re[a] + max_dist) break;
-          if (W.strand[b] != W.strand[a]) continue;
-          const int ref_dist = W.rs[b] - W.re[a];
-          int query_dist;
-          if (W.strand[a] == 1 && W.qs[a] <= W.qs[b]) query_dist = W.qs[b] - W.qe[a];
-          else if (W.strand[a] != 1 && W.qe[a] >= W.qe[b]) query_dist = W.qs[a] - W.qe[b];
-          else continue;                                           // dist stays at the double's maximum
-          const double qd = (double)query_dist, rd = (double)ref_dist, df = (double)(query_dist - ref_dist);
-          const double dist = mm_chain_sqrt(qd * qd + rd * rd);
-          const double score = df * df;
-          if (dist < (double)max_dist) {
-            const double key = dist + score;
-            if (!have || key < bestKey) { have = true; bestKey = key; bestJ = j; }     // the front of the sorted (key, id) pairs: ids ascend with j
-          }
-        }
-        if (have) {                                                // DisjointSets::unite (dset64.hpp:93-125)
-          int x = find(i), y = find(bestJ);
-          if (x != y) {
-            if (rnk[x] > rnk[y] || (rnk[x] == rnk[y] && x < y)) { const int t = x; x = y; y = t; }     // x goes under y
-            parent[x] = (int8_t)y;
-            if (rnk[x] == rnk[y]) rnk[y]++;
-          }
-        }
+        const int j = mm_chain_partner(w, m, i, E.p.chainGap);
+        if (j >= 0) mm_chain_unite(w, i, j);
       }
-      for (int i = 0; i < m; i++) W.smid[v[i]] = find(W.smid[v[i]]);
-      mm_chain_sort(v, 0, m, [&W](int x, int y) { return W.smid[x] < W.smid[y]; });
-      int w = 0;
+      for (int i = 0; i < m; i++) w.smid[w.v[i]] = mm_chain_find(w, w.smid[w.v[i]]);
+      mm_chain_sort_smid(w, m);
       for (int it = 0; it < m;) {
-        const int rep = v[it];
         int end = it;
-        while (end < m && W.smid[v[end]] == W.smid[rep]) end++;
-        const float repIdent = W.ident[rep];
-        double sumI = 0.0, sumK = 0.0;
-        for (int j = it; j < end; j++) {
-          const int x = v[j];
-          W.qs[rep] = W.qs[x] < W.qs[rep] ? W.qs[x] : W.qs[rep];
-          W.rs[rep] = W.rs[x] < W.rs[rep] ? W.rs[x] : W.rs[rep];
-          W.qe[rep] = W.qe[x] > W.qe[rep] ? W.qe[x] : W.qe[rep];
-          W.re[rep] = W.re[x] > W.re[rep] ? W.re[x] : W.re[rep];
-          sumI = sumI + (double)W.ident[x];
-          sumK = sumK + W.kc[x];
-        }
-        const int32_t dr = W.re[rep] - W.rs[rep], dq = W.qe[rep] - W.qs[rep];
-        W.blk[rep] = dr > dq ? dr : dq;
-        W.approx[rep] = mm_chain_approx(repIdent, W.blk[rep]);
-        W.nm[rep] = end - it;
-        W.ident[rep] = (float)(sumI / (double)W.nm[rep]);
-        W.kc[rep] = sumK / (double)W.nm[rep];
-        v[w++] = (int8_t)rep;
+        while (end < m && w.smid[w.v[end]] == w.smid[w.v[it]]) end++;
+        mm_chain_finish_chain(w, it, end);
         it = end;
       }
-      m = w;
     }
-    int w = 0;
-    for (int i = 0; i < m; i++) if (!(queryLen > W.blk[v[i]] && W.nm[v[i]] < E.p.minMerged)) v[w++] = v[i];     // filterWeakMappings
-    m = w;
+    m = mm_chain_keep(E, w, m, queryLen, m >= 2);
   }
 
-  // ---- filterByGroup, query axis
-  if (E.p.filter == MM_CHAIN_FILTER_QUERY) {
-    const int secondaryToKeep = (int)(uint16_t)(readLen < E.segLength ? E.p.secondaryShort : E.p.secondarySegment);
-    mm_chain_sort(v, 0, m, [&W](int x, int y) { return W.sid[x] != W.sid[y] ? W.sid[x] < W.sid[y] : W.rs[x] < W.rs[y]; });
-    auto byQuery = [&W](int x, int y) {
-      if (W.qs[x] != W.qs[y]) return W.qs[x] < W.qs[y];
-      if (W.sid[x] != W.sid[y]) return W.sid[x] < W.sid[y];
-      return W.rs[x] < W.rs[y]; };
-    mm_chain_sort(v, 0, m, byQuery);
-    if (m > 1) {                                                   // filterQueryAxis; ids of the sweep are positions in v
-      uint64_t ev[2 * MM_CHAIN_MAX_RECORDS];
-      for (int i = 0; i < m; i++) {
-        W.discard[v[i]] = 1;
-        ev[2 * i] = ((uint64_t)((uint32_t)W.qs[v[i]] ^ 0x80000000u) << 8) | (1u << 5) | (uint64_t)i;          // (pos, BEGIN = 1, id)
-        ev[2 * i + 1] = ((uint64_t)((uint32_t)W.qe[v[i]] ^ 0x80000000u) << 8) | (2u << 5) | (uint64_t)i;      // (pos, END = 2, id)
-      }
-      const int nE = 2 * m;
-      for (int i = 1; i < nE; i++) { const uint64_t x = ev[i]; int j = i; while (j > 0 && x < ev[j - 1]) { ev[j] = ev[j - 1]; j--; } ev[j] = x; }
-      // better(x, y): std::tie(identity as double, queryStartPos, refSeqId) of x > that of y
-      auto better = [&W, &v](int x, int y) {
-        const int a = v[x], b = v[y];
-        if (W.ident[a] != W.ident[b]) return W.ident[a] > W.ident[b];
-        if (W.qs[a] != W.qs[b]) return W.qs[a] > W.qs[b];
-        return W.sid[a] > W.sid[b]; };
-      int8_t status[MM_CHAIN_MAX_RECORDS];
-      int nS = 0;
-      for (int i = 0; i < nE;) {
-        int j = i;
-        while (j < nE && (ev[j] >> 8) == (ev[i] >> 8)) j++;
-        for (int e = i; e < j; e++) {
-          const int id = (int)(ev[e] & 31u);
-          int at = 0;
-          while (at < nS && better(status[at], id)) at++;          // lower bound
-          const bool equivalent = at < nS && !better(id, status[at]);
-          if (((ev[e] >> 5) & 7u) == 1u) {
-            if (!equivalent) { for (int t = nS; t > at; t--) status[t] = status[t - 1]; status[at] = (int8_t)id; nS++; }
-          } else if (equivalent) {
-            for (int t = at; t + 1 < nS; t++) status[t] = status[t + 1];
-            nS--;
-          }
-        }
-        if (nS > 0) {                                              // markGood (filter.hpp:77-95)
-          const float best = W.ident[v[status[0]]];
-          int kept = 0;
-          for (int t = 0; t < nS; t++) {
-            const int x = v[status[t]];
-            const bool worseOrSeen = best > W.ident[x] || W.discard[x] == 0;
-            if (worseOrSeen && kept > secondaryToKeep) break;
-            W.discard[x] = 0;
-            ++kept;
-          }
-        }
-        i = j;
-      }
-      int w = 0;
-      for (int i = 0; i < m; i++) if (W.discard[v[i]] == 0) v[w++] = v[i];
-      m = w;
-    }
-    mm_chain_sort(v, 0, m, byQuery);
-  }
+  m = mm_chain_filter(E, w, m, readLen);
 
-  if (out)
-    for (int i = 0; i < m; i++) {
-      const int x = v[i];
-      mm_chain_row r;
-      r.querySeqId = querySeqId; r.queryLen = queryLen; r.queryStartPos = W.qs[x]; r.queryEndPos = W.qe[x];
-      r.refSeqId = W.sid[x]; r.refStartPos = W.rs[x]; r.refEndPos = W.re[x]; r.strand = W.strand[x];
-      r.conservedSketches = W.cons[x]; r.sketchSize = W.sk[x]; r.blockLength = W.blk[x]; r.approxMatches = W.approx[x];
-      r.n_merged = W.nm[x]; r.splitMappingId = W.smid[x];
-      r.nucIdentity = W.ident[x]; r.pad_ = 0; r.kmerComplexity = W.kc[x];
-      out[i] = r;
-    }
+  if (out) for (int i = 0; i < m; i++) out[i] = mm_chain_emit(w, w.v[i], querySeqId, queryLen);
   return m;
+}
+
+// Finishes the read of length readLen whose records are recs[0, n), in mm_mappings_download's order.  Writes the surviving mappings to
+// out (when non-null; up to n of them), in the order filterByGroup leaves them, and returns their number; -1 for n above
+// MM_CHAIN_MAX_RECORDS (the read is not taken), MM_CHAIN_BAD_RECORD for a record outside the identity table.
+MM_HD int mm_chain_read(const mm_chain_env& E, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out) {
+  if (n > MM_CHAIN_MAX_RECORDS) return -1;
+  if (n <= 0) return 0;
+  mm_chain_work W;
+  return mm_chain_read_t(E, W, recs, n, readLen, out);
+}
+
+// The same for a read of up to MM_CHAIN_LONG_MAX_RECORDS (512) records in the working set W the caller provides (39 KB: not for a
+// device stack); -1 above that.  For n <= 16 the rows are mm_chain_read's.
+MM_HD int mm_chain_read_long(const mm_chain_env& E, mm_chain_work_long& W, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out) {
+  if (n > MM_CHAIN_LONG_MAX_RECORDS) return -1;
+  if (n <= 0) return 0;
+  return mm_chain_read_t(E, W, recs, n, readLen, out);
 }

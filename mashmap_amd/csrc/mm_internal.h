@@ -271,6 +271,12 @@ struct mm_ctx {
   mm_chain_params chainP{}; bool haveChainTables = false;
   uint64_t chainPass = 0;                               // nPasses when mm_chain_reads last went through: its results belong to that pass (0: none)
   size_t chOffered = 0, chFinished = 0, chRows = 0, chLeft = 0;
+  // MM_OPT_CHAIN_LONG: the list of reads with 17 .. 512 records (filled by the count pass), the rows k_chain_reads_long leaves at each
+  // read's record offset, and the two counts of mm_chain_long_counts
+  bool chainLong = false;
+  DevBuf dChainLongList, dChainStage;
+  uint64_t chLongOffered = 0, chLongFinished = 0;
+  int chainCUs = 0;                                     // compute units of the device (k_chain_reads_long's grid), asked for once
   // multi-GPU exchange (mm_comm.hip)
   void* comm = nullptr; int commRank = 0, commWorld = 0; bool commCopy = false;   // commCopy: local group whose contexts share a device
   DevBuf dCommCounts, dGathered; std::vector<size_t> gatherCounts, gatherDisp; size_t nGathered = 0; bool gathered = false;

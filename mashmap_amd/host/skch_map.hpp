@@ -88,8 +88,9 @@ class Map {
   // MASHMAP_HIP_DEVICE_CHAIN: the device stage runs mm_chain_reads behind mm_map_fragments and brings back the rows of the reads it
   // finished plus the records of the reads it handed over, instead of every record; the post stage finishes both kinds.  Only in a run
   // with one context, split reads, no reference groups (-Y), filter mode map or one-to-one, sketchSize <= MM_CHAIN_MAX_SKETCH and a
-  // chain gap the stage takes; anywhere else the switch does nothing
-  bool deviceChain = false;
+  // chain gap the stage takes; anywhere else the switch does nothing.  With the value `long` the context additionally gets
+  // MM_OPT_CHAIN_LONG: reads of 17 .. 512 records are chained on the device too, and only reads above 512 are handed over
+  bool deviceChain = false, deviceChainLong = false;
   bool exchangeFellBack = false;                 // a default RCCL all-gatherv failed once: per-context downloads for the rest of the run
   skch::Time::time_point tStart = skch::Time::now();   // MASHMAP_HIP_TIMING lines carry the time since the Map was constructed
   // one write per diagnostic line: three stages log at once, and `std::cerr << a << b` from two threads interleaves inside a line
@@ -145,6 +146,10 @@ class Map {
       const mm_chain_params cp = post.chainParams();
       if (mm_set_chain_tables(ctx, &cp, identity.data(), stride) != MM_OK) die("mm_set_chain_tables");
       deviceChain = true;
+      if (std::strcmp(getenv("MASHMAP_HIP_DEVICE_CHAIN"), "long") == 0) {
+        if (mm_set_option(ctx, MM_OPT_CHAIN_LONG, 1) != MM_OK) die("mm_set_option(MM_OPT_CHAIN_LONG)");
+        deviceChainLong = true;
+      }
     }
     if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] integer tables ready" << (deviceChain ? " (chaining on the device)" : "") << at();
     this->mapQuery();
@@ -425,11 +430,13 @@ class Map {
       releaseBuffers();
     }
     size_t n = 0;
+    uint64_t longOffered = 0, longFinished = 0;
     const auto p2 = skch::Time::now();
     if (nCtx == 1 && deviceChain) {
       // rows of the reads the device finished + records of the reads it handed over, instead of every record
       if (mm_chain_reads(ctx) != MM_OK) die("mm_chain_reads");
       if (mm_chain_counts(ctx, nullptr, nullptr, &nRows, &n) != MM_OK) die("mm_chain_counts");
+      if (deviceChainLong && mm_chain_long_counts(ctx, &longOffered, &longFinished) != MM_OK) die("mm_chain_long_counts");
       allRows->resize(nRows); all->resize(n);
       if (nRows && mm_chain_download(ctx, allRows->data(), nRows, &nRows) != MM_OK) die("mm_chain_download");
       if (n && mm_chain_leftover_download(ctx, all->data(), n, &n) != MM_OK) die("mm_chain_leftover_download");
@@ -478,7 +485,8 @@ class Map {
     if (timing) LogLine() << "[mashmap_hip::timing] device stage (upload + pack + kernels" << (gatherOnDevice ? " + all-gatherv" : "") << " + download of " << n
                           << (deviceChain ? " left-over candidate mappings and " + std::to_string(nRows) + " chained rows): " : std::string(" candidate mappings): "))
                           << std::chrono::duration<double>(skch::Time::now() - t0).count() << " s (upload " << phase[0] << ", kernels " << phase[1]
-                          << ", download " << std::chrono::duration<double>(skch::Time::now() - p2).count() << ") [bases " << passBases << "] [batches " << nB << "]" << at();
+                          << ", download " << std::chrono::duration<double>(skch::Time::now() - p2).count() << ") [bases " << passBases << "] [batches " << nB << "]"
+                          << (deviceChainLong ? " [" + std::to_string(longFinished) + " of " + std::to_string(longOffered) + " reads of more than 16 records chained on the device]" : std::string()) << at();
   }
 
   // post stage: per read, chaining + filters + PAF text on param.threads threads; then output in input order

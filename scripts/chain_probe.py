@@ -9,6 +9,12 @@ mapped once, then three alternations of two forms on the resident candidate mapp
 -- and per form: device milliseconds of the stage (events on mm_stream around mm_chain_reads; form A has no device stage), download
 milliseconds and bytes, host wall time and CPU-seconds, the share of reads handed over, the reported mappings (both forms must agree).
 
+With --chain-long a third form joins every alternation of part 1 --
+  C  form B with MM_OPT_CHAIN_LONG set: reads of 17 .. 512 records are chained on the device by k_chain_reads_long
+-- on the same resident records (on configs[1] no read is long: C then costs what the list counter and an empty kernel cost), and
+part 1 runs a second time on a long-read workload (key "long_reads"): reads of 100 kbp (--long-read-len) at the same segLength against the
+same reference, --long-reads of them, about 20 records a read in one chain, where form B hands every read over.
+
 Part 2, the command line: mashmap_hip FASTA -> PAF on the same workload's files without and with MASHMAP_HIP_DEVICE_CHAIN, three times
 alternating, with the stage lines of MASHMAP_HIP_TIMING ('time spent mapping the query', device stage, post stage); the PAFs must be equal.
 Every run has a time limit (--run-timeout); behind a run that fails or does not end in time nothing more is started: the probe writes
@@ -66,17 +72,18 @@ class StreamEvents:
         return round(float(ms.value), 3)
 
 
-def part1(torch, dev, W, nreads, out):
+def part1(torch, dev, W, nreads, out, chain_long=False, L=None, key="one_context", ref=None):
     from mashmap_amd import capi, shard
     host = shard.host_lib()
-    K, SEG, S, PI, L = W["k"], W["seg"], W["sketch"], W["pi"], W["read_len"]
-    contigs = make_reference(torch, dev, W["ref_contigs"], W["ref_contig_len"])
-    ref_np = contiguous_views(torch, contigs)
+    K, SEG, S, PI = W["k"], W["seg"], W["sketch"], W["pi"]
+    L = W["read_len"] if L is None else L
+    contigs = make_reference(torch, dev, W["ref_contigs"], W["ref_contig_len"]) if ref is None else ref[1]
+    ref_np = contiguous_views(torch, contigs) if ref is None else ref[0]
     ctx = capi.Context(k=K, segLength=SEG, sketchSize=S, flags=capi.MM_FLAG_HG_FILTER)
     ctx.index_build(ref_np, kmerPct=0.001)
     ctx.set_tables_default(PI)
     ctx.set_chain_tables(SEG, 1, 0, 0, True, capi.MM_CHAIN_FILTER_QUERY, 0.0)
-    reads_t = make_reads(torch, dev, contigs, nreads, L, W["err"], seed=4242)
+    reads_t = make_reads(torch, dev, contigs, nreads, L, W["err"], seed=4242, chunk=max(64, 8192 * 10000 // L))      # the same bytes a chunk at any read length
     torch.cuda.synchronize()
     offs = np.arange(nreads + 1, dtype=np.int64) * L
     ctx.reads_upload_device(reads_t.data_ptr(), reads_t.numel(), offs)
@@ -84,7 +91,7 @@ def part1(torch, dev, W, nreads, out):
     ctx.map(); ctx.map(); ctx.synchronize()                        # the second pass is a steady-state one: the records of a run in progress
     clens = np.array([len(a) for a in ref_np], dtype=np.int32); rl = np.full(nreads, L, dtype=np.int32)
     ev = StreamEvents(ctx.lib.mm_stream(ctx.h))
-    forms = {"A": [], "B": []}
+    forms = {"A": [], "B": [], "C": []} if chain_long else {"A": [], "B": []}
     for rep in range(3):
         # ---- A
         t0 = time.perf_counter()
@@ -114,8 +121,30 @@ def part1(torch, dev, W, nreads, out):
                                reported=int(nb), rows=int(len(rows)), leftover_records=int(len(left)), offered=cnt["offered"], finished=cnt["finished"],
                                handed_over_share=round(1 - cnt["finished"] / max(1, cnt["offered"]), 6), same_as_A=bool(na == nb and rows_a[:na].tobytes() == rows_b[:nb].tobytes())))
         log("[chain_probe] alternation %d: A %r | B %r" % (rep, forms["A"][-1], forms["B"][-1]))
+        if chain_long:
+            # ---- C
+            ctx.chain_long(True)
+            ev.start(); t0 = time.perf_counter()
+            ctx.chain_reads()
+            wall_stage = time.perf_counter() - t0
+            dev_ms = ev.elapsed()
+            cnt, lcnt = ctx.chain_counts(), ctx.chain_long_counts()
+            t0 = time.perf_counter()
+            rows = ctx.chain_rows(); left = ctx.chain_leftover()
+            dl = time.perf_counter() - t0
+            ctx.chain_long(False)
+            c0 = cpu_seconds(); t0 = time.perf_counter()
+            rows_c = np.zeros(len(recs) + 1, dtype=rows_a.dtype)
+            nc = host.mmh_post_chained(K, SEG, S, PI, 1, 1, 1, 1, SEG, SEG, len(clens), clens.ctypes.data, rows.ctypes.data if len(rows) else None, len(rows),
+                                       left.ctypes.data if len(left) else None, len(left), rl.ctypes.data, nreads, 0, THREADS, None, rows_c.ctypes.data, None, None, len(rows_c))
+            forms["C"].append(dict(device_ms=dev_ms, stage_wall_ms=round(wall_stage * 1e3, 3), download_ms=round(dl * 1e3, 3),
+                                   download_bytes=int(rows.nbytes + left.nbytes), host_ms=round((time.perf_counter() - t0) * 1e3, 3), host_cpu_s=round(cpu_seconds() - c0, 4),
+                                   reported=int(nc), rows=int(len(rows)), leftover_records=int(len(left)), offered=cnt["offered"], finished=cnt["finished"],
+                                   long_offered=lcnt["offered"], long_finished=lcnt["finished"],
+                                   handed_over_share=round(1 - cnt["finished"] / max(1, cnt["offered"]), 6), same_as_A=bool(na == nc and rows_a[:na].tobytes() == rows_c[:nc].tobytes())))
+            log("[chain_probe] alternation %d: C %r" % (rep, forms["C"][-1]))
     nrec = np.bincount(recs["querySeqId"], minlength=nreads)
-    out["one_context"] = dict(reads=nreads, read_len=L, host_threads=THREADS, forms=forms,
+    out[key] = dict(reads=nreads, read_len=L, host_threads=THREADS, forms=forms,
                               records_per_read={"mean": round(float(nrec.mean()), 3), "max": int(nrec.max()), "reads_above_16": int((nrec > 16).sum()),
                                                 "histogram_0_to_17plus": np.bincount(np.minimum(nrec, 17), minlength=18).tolist()})
     ctx.close()
@@ -187,6 +216,9 @@ def main():
     ap.add_argument("--cli-reads", type=int, default=WORKLOADS["configs1"]["reads"])
     ap.add_argument("--no-cli", action="store_true")
     ap.add_argument("--run-timeout", type=int, default=120, help="seconds one mashmap_hip run of part 2 may take (it takes about 2.5 at the default size)")
+    ap.add_argument("--chain-long", action="store_true", help="form C (MM_OPT_CHAIN_LONG) in part 1, and part 1 again on the long-read workload")
+    ap.add_argument("--long-reads", type=int, default=20000, help="reads of the long-read workload (20 000 x 100 kbp: about 400 000 records)")
+    ap.add_argument("--long-read-len", type=int, default=100000)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -196,7 +228,9 @@ def main():
     torch.zeros(1, device=dev).cpu()
     W = WORKLOADS["configs1"]
     out = {"workload": W["label"]}
-    ref_np, contigs = part1(torch, dev, W, a.reads, out)
+    ref_np, contigs = part1(torch, dev, W, a.reads, out, chain_long=a.chain_long)
+    if a.chain_long:
+        part1(torch, dev, W, a.long_reads, out, chain_long=True, L=a.long_read_len, key="long_reads", ref=(ref_np, contigs))
     stopped = None
     if not a.no_cli:
         stopped = part2(torch, dev, W, a.cli_reads, ref_np, contigs, out, a.run_timeout)
