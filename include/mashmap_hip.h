@@ -551,6 +551,11 @@ const char* mm_kernel_name(int which);
 /* integer-roofline yardstick: a kernel that does nothing but the 2 x MurmurHash3_x64_128 per position of
  * every resident fragment (both strands, same tables and staging as the sketch kernel); *msAvg = average of `reps` launches */
 int mm_bench_hash_only(mm_ctx* ctx, int reps, double* msAvg);
+/* diagnostic: bytes of device memory the library holds at this moment, over every context of the process (their indexes, batches of
+ * reads -- the parked ones included --, staging buffers) and the scratch of a call in progress.  Counted where the library allocates and
+ * frees, not asked of the device: memory other libraries or processes hold is not in it.  After the last mm_destroy it is 0.  May be
+ * called from any thread.  Purely additive: MM_ABI_VERSION stays 2. */
+size_t mm_device_bytes(void);
 int mm_synchronize(mm_ctx* ctx);
 /* the HIP stream all work of this ctx is ordered on (a hipStream_t) */
 void* mm_stream(const mm_ctx* ctx);

@@ -168,6 +168,7 @@ def load():
         "mm_chain_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_leftover_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
+        "mm_device_bytes": (sz, []),
         "mm_synchronize": (C.c_int, [vp]),
         "mm_stream": (vp, [vp]),
     }
@@ -196,7 +197,12 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
            "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
            "mm_stat_identity_table", "mm_set_chain_tables", "mm_chain_reads", "mm_chain_counts", "mm_chain_download",
-           "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts"]
+           "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts", "mm_device_bytes"]
+
+
+def device_bytes():
+    """bytes of device memory the library holds at this moment, over every context of the process (mm_device_bytes; a diagnostic)"""
+    return int(load().mm_device_bytes())
 
 
 def stat_sketch_cutoffs(sketchSize, k, hg=True):

@@ -29,19 +29,10 @@ mm_env mm_read_env() {
   return v;
 }
 
-std::vector<DevBuf*> mm_ctx::allBufs() {
-  DeviceIndex& I = idx;
-  return {&I.evKey, &I.evAux, &I.evHash, &I.contigOff, &I.opKey, &I.opAux, &I.opHash, &I.blockOff, &I.evBlock, &I.contigBlock, &I.contigLen, &I.refGroup,
-          &I.htSlots, &I.htTags, &I.filter, &I.ptKeys, &I.keys, &I.keyOff, &I.keyFreq, &dMinHits, &dCutoffs, &dAscii, &dAsciiNext, &dReadSrcOff, &dReadPackOff, &dReadLen, &dReadGroup, &dReadSelf, &dReadHasN,
-          &dBases2, &dNmask, &dFrags, &dSkHash, &dSkPos, &dSkStrand, &dSkCount, &dHardList, &dCounters, &dSketchSpill, &dSketchTabs, &dQHash, &dQStrand,
-          &dStats, &dPtOff, &dPts, &dPtKept, &dPtIds, &dWinFreq, &dWinExt, &dWinHeap, &dWinKeys, &dWinVals, &dWinOffH, &dWinOffT, &dWinCntH, &dWinCntT, &dL1, &dL1b, &dL1Cursors, &dL1Off, &dL1Regions, &dL2, &dL2Info, &dL2Cnt, &dL2Off, &dL2Ops, &dScanTmp, &dL2Tmp, &dL2Wide, &dL2Exact, &dL2Cells,
-          &dListB, &dListC, &dBigList, &dMidList, &dGrpList, &dL2Sort[0], &dL2Sort[1], &dL2Sort[2], &dL2Sort[3], &dL2Order, &dL2OrderPos, &dL2InitCells, &dL2InitState, &dL2First, &dL2Num, &dAccept, &dMinIsz, &dSelCnt, &dSelOff, &dSelHeap, &dFragTab, &dMappings, &dCommCounts, &dGathered,
-          &dChainIdent, &dChainBegin, &dChainEnd, &dChainCntR, &dChainCntL, &dChainOffR, &dChainOffL, &dChainRows, &dChainLeft, &dChainTotals};
-}
-
 extern "C" {
 
 int mm_abi_version(void) { return MM_ABI_VERSION; }
+size_t mm_device_bytes(void) { return g_mmDeviceBytes.load(); }
 const char* mm_kernel_name(int which) { return (which >= 0 && which < MM_K_COUNT) ? kKernelNames[which] : "?"; }
 
 const char* mm_last_error(const mm_ctx* ctx) { return ctx ? ctx->err.c_str() : g_createErr.c_str(); }
@@ -86,16 +77,12 @@ void mm_destroy(mm_ctx* c) {
   if (c->commStream) (void)hipStreamDestroy(c->commStream);
   if (c->copyStream) { (void)hipStreamSynchronize(c->copyStream); (void)hipStreamDestroy(c->copyStream); }
   if (c->copyDone) (void)hipEventDestroy(c->copyDone);
-  for (DevBuf* b : c->allBufs()) b->release();
-  c->dGatherSrc.release();
-  for (auto& p : c->parked)
-    for (DevBuf* b : {&p.dReadSrcOff, &p.dReadPackOff, &p.dReadLen, &p.dReadGroup, &p.dReadSelf, &p.dReadHasN, &p.dBases2, &p.dNmask, &p.dFrags}) b->release();
   if (c->hPass) (void)hipHostFree(c->hPass);
   for (auto& pr : c->evPool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   if (c->evA) (void)hipEventDestroy(c->evA);
   if (c->evB) (void)hipEventDestroy(c->evB);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;   // frees every DevBuf of the context, the parked batches' included -- behind the streams' destruction: each was synchronised above (commStream by the joined gather thread)
 }
 
 int mm_synchronize(mm_ctx* c) { MM_HIP(c, hipStreamSynchronize(c->stream)); return MM_OK; }
@@ -503,13 +490,7 @@ int mm_reads_exchange(mm_ctx* c, int slot) {
   std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);   // an upload of the resident batch is not under way
   MM_HIP(c, hipSetDevice(c->device));
   MM_HIP(c, hipStreamSynchronize(c->stream));                // nothing queued still reads the outgoing batch
-  mm_ctx::ParkedReads& p = c->parked[slot];
-  std::swap(c->nReads, p.nReads); std::swap(c->nFrags, p.nFrags); std::swap(c->nPackedBases, p.nPackedBases);
-  std::swap(c->seqCounterBase, p.seqCounterBase); std::swap(c->maxFragLen, p.maxFragLen); std::swap(c->windowed, p.windowed);
-  std::swap(c->dReadSrcOff, p.dReadSrcOff); std::swap(c->dReadPackOff, p.dReadPackOff); std::swap(c->dReadLen, p.dReadLen);
-  std::swap(c->dReadGroup, p.dReadGroup); std::swap(c->dReadSelf, p.dReadSelf); std::swap(c->dReadHasN, p.dReadHasN);
-  std::swap(c->dBases2, p.dBases2); std::swap(c->dNmask, p.dNmask); std::swap(c->dFrags, p.dFrags);
-  c->hFrags.swap(p.hFrags);
+  std::swap(static_cast<ReadBatch&>(*c), c->parked[slot]);
   c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false;
   return MM_OK;
 }

@@ -331,7 +331,7 @@ int mm_gathered_device(const mm_ctx* c, const mm_mapping** d, size_t* total) {
 }
 
 // replica of src's resident index on dst's GPU (device-to-device over xGMI; no second build, no host round trip).  dst gets the
-// device index only: the host mirrors behind mm_index_download stay with src.
+// device index only (MM_REPLICATED_BUFS, mm_internal.h): the host mirrors behind mm_index_download stay with src.
 int mm_index_replicate(mm_ctx* dst, mm_ctx* src) {
   if (!src->idx.ready) { dst->err = "mm_index_replicate: the source context has no index"; return MM_ERR_STATE; }
   if (dst->P.kmerSize != src->P.kmerSize || dst->P.segLength != src->P.segLength || dst->P.sketchSize != src->P.sketchSize) {
@@ -342,13 +342,12 @@ int mm_index_replicate(mm_ctx* dst, mm_ctx* src) {
   MM_HIP(dst, hipSetDevice(dst->device));
   DeviceIndex& D = dst->idx; DeviceIndex& S = src->idx;
   D.ready = false;
-  DevBuf* d[] = {&D.evKey, &D.evAux, &D.evHash, &D.contigOff, &D.opKey, &D.opAux, &D.opHash, &D.blockOff, &D.evBlock, &D.contigBlock, &D.contigLen, &D.refGroup, &D.htSlots, &D.htTags, &D.filter, &D.ptKeys};
-  DevBuf* s[] = {&S.evKey, &S.evAux, &S.evHash, &S.contigOff, &S.opKey, &S.opAux, &S.opHash, &S.blockOff, &S.evBlock, &S.contigBlock, &S.contigLen, &S.refGroup, &S.htSlots, &S.htTags, &S.filter, &S.ptKeys};
-  for (size_t i = 0; i < sizeof d / sizeof d[0]; i++) {
-    if (!s[i]->bytes) continue;
-    MM_HIP(dst, d[i]->ensure(s[i]->bytes));
-    if (dst->device == src->device) MM_HIP(dst, hipMemcpyAsync(d[i]->p, s[i]->p, s[i]->bytes, hipMemcpyDeviceToDevice, dst->stream));
-    else MM_HIP(dst, hipMemcpyPeerAsync(d[i]->p, dst->device, s[i]->p, src->device, s[i]->bytes, dst->stream));
+  for (DevBuf DeviceIndex::* const m : MM_REPLICATED_BUFS) {
+    DevBuf& d = D.*m; const DevBuf& s = S.*m;
+    if (!s.bytes) continue;
+    MM_HIP(dst, d.ensure(s.bytes));
+    if (dst->device == src->device) MM_HIP(dst, hipMemcpyAsync(d.p, s.p, s.bytes, hipMemcpyDeviceToDevice, dst->stream));
+    else MM_HIP(dst, hipMemcpyPeerAsync(d.p, dst->device, s.p, src->device, s.bytes, dst->stream));
   }
   MM_HIP(dst, hipStreamSynchronize(dst->stream));
   D.nRec = S.nRec; D.nKeys = S.nKeys; D.nPoints = S.nPoints; D.nContigs = S.nContigs; D.htCap = S.htCap; D.nOpen = S.nOpen; D.filterMask = S.filterMask; D.tagged = S.tagged;

@@ -257,18 +257,13 @@ static int finalize_index(mm_ctx* c, std::vector<mm_minmer>& all, bool haveMap, 
   return mm_build_device_index(c, contigLen, refGroup, nContigs);
 }
 
-extern "C" int mm_index_build(mm_ctx* c, const char* bases, const int64_t* contigOffsets, size_t nContigs, const int32_t* refGroup,
-                              float kmerPctThreshold) {
-  if (!bases || !contigOffsets || !nContigs) { c->err = "mm_index_build: null argument"; return MM_ERR_ARG; }
-  MM_HIP(c, hipSetDevice(c->device));
+// First half of mm_index_build: hash and winnow every contig on the device, finish each on a host thread (per[ci], clen[ci]).  The hashing
+// buffers and the winnow scratch live here: they are gone before the second half of the build allocates
+static int winnow_contigs(mm_ctx* c, HashContigFn hasher, const char* bases, const int64_t* contigOffsets, size_t nContigs, std::vector<int32_t>& clen,
+                          std::vector<std::vector<mm_minmer>>& per, std::chrono::steady_clock::time_point tStart) {
   const int k = c->P.kmerSize, w = c->P.segLength, s = c->P.sketchSize;
-  HashContigFn hasher = pick_hasher(k);
-  if (!hasher) { c->err = "mm_index_build: kmerSize not compiled in"; return MM_ERR_ARG; }
   const bool dbg = c->env.debug;
-  const auto tStart = std::chrono::steady_clock::now();
   auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count(); };
-  std::vector<int32_t> clen(nContigs);
-  std::vector<std::vector<mm_minmer>> per(nContigs);
   std::deque<std::shared_future<void>> inflight;
   std::shared_future<void> stagedBusy[2];               // the finishing job that still reads the page-locked landing buffer of that turn
   DevBuf dAscii, dB, dM, dMeta, dH, dS;
@@ -304,7 +299,21 @@ extern "C" int mm_index_build(mm_ctx* c, const char* bases, const int64_t* conti
   if (dbg) fprintf(stderr, "[mm] index: hash + winnow of %zu contigs issued at %.2f s\n", nContigs, since());
   while (!inflight.empty()) { inflight.front().get(); inflight.pop_front(); }
   if (dbg) fprintf(stderr, "[mm] index: host tails (stitch, sort, unique) done at %.2f s\n", since());
-  dAscii.release(); dB.release(); dM.release(); dMeta.release(); dH.release(); dS.release(); wb.release();
+  return rc;                                            // (every host job was waited for: nothing reads the page-locked areas any more)
+}
+
+extern "C" int mm_index_build(mm_ctx* c, const char* bases, const int64_t* contigOffsets, size_t nContigs, const int32_t* refGroup,
+                              float kmerPctThreshold) {
+  if (!bases || !contigOffsets || !nContigs) { c->err = "mm_index_build: null argument"; return MM_ERR_ARG; }
+  MM_HIP(c, hipSetDevice(c->device));
+  HashContigFn hasher = pick_hasher(c->P.kmerSize);
+  if (!hasher) { c->err = "mm_index_build: kmerSize not compiled in"; return MM_ERR_ARG; }
+  const bool dbg = c->env.debug;
+  const auto tStart = std::chrono::steady_clock::now();
+  auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count(); };
+  std::vector<int32_t> clen(nContigs);
+  std::vector<std::vector<mm_minmer>> per(nContigs);
+  const int rc = winnow_contigs(c, hasher, bases, contigOffsets, nContigs, clen, per, tStart);
   if (rc != MM_OK) return rc;
 
   size_t nRecords = 0; for (const auto& v : per) nRecords += v.size();

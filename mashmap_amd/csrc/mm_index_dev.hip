@@ -289,12 +289,6 @@ k_order_keys(int c0, int n, const int32_t* __restrict__ key, int shift, uint32_t
 
 namespace {
 
-struct Tmp {                        // scratch device buffers of one build, released at the end
-  std::vector<DevBuf*> all;
-  DevBuf* make() { all.push_back(new DevBuf()); return all.back(); }
-  ~Tmp() { for (DevBuf* b : all) { b->release(); delete b; } }
-};
-
 template <class K, class V>
 int sort_pairs(mm_ctx* c, DevBuf& tmp, const K* kin, K* kout, const V* vin, V* vout, size_t n, unsigned beginBit, unsigned endBit) {
   size_t bytes = 0;
@@ -320,13 +314,12 @@ unsigned bits_for(uint64_t v) { unsigned b = 1; while (b < 64 && (v >> b)) b++; 
 int mm_flatten_device_index(mm_ctx* c, const mm_minmer* dRec, size_t n, size_t nk, size_t np, const int32_t* contigLen, const int32_t* refGroup, size_t nContigs) {
   DeviceIndex& I = c->idx;
   I.ready = false;
-  Tmp T;
-  DevBuf& scratch = *T.make();
+  DevBuf scratch;
   unsigned long long* diag = c->dCounters.as<unsigned long long>() + MM_CW_INDEX_FLATTEN;   // MM_IX_FLAT_*
   MM_HIP(c, hipMemsetAsync(diag, 0, 32, c->stream));
   const int nC = (int)nContigs;
   if (n) K_LAUNCH(k_check_records, n, n, dRec, nC, diag);
-  DevBuf& dFirst = *T.make(); DevBuf& dLastW = *T.make();
+  DevBuf dFirst, dLastW;
   MM_HIP(c, dFirst.ensure((nContigs + 1) * 8)); MM_HIP(c, dLastW.ensure(nContigs * 4 + 4));
   hipLaunchKernelGGL(k_contig_ranges, dim3((unsigned)((nContigs + 1 + 255) / 256)), dim3(256), 0, c->stream, n, dRec, nC, dFirst.as<int64_t>(), dLastW.as<int32_t>());
   std::vector<int32_t> lastW(nContigs);
@@ -341,7 +334,7 @@ int mm_flatten_device_index(mm_ctx* c, const mm_minmer* dRec, size_t n, size_t n
   MM_HIP(c, I.evKey.ensure(nEv * 4 + 256)); MM_HIP(c, I.evAux.ensure(nEv * 4 + 256)); MM_HIP(c, I.evHash.ensure(nEv * 8 + 512));
   MM_HIP(c, I.contigOff.ensure((nContigs + 1) * 8));
   if (n) {
-    DevBuf& k0 = *T.make(); DevBuf& k1 = *T.make(); DevBuf& v0 = *T.make(); DevBuf& v1 = *T.make();
+    DevBuf k0, k1, v0, v1;
     MM_HIP(c, k0.ensure(nEv * 8)); MM_HIP(c, k1.ensure(nEv * 8)); MM_HIP(c, v0.ensure(nEv * 4)); MM_HIP(c, v1.ensure(nEv * 4));
     K_LAUNCH(k_event_keys, n, n, dRec, k0.as<uint64_t>(), v0.as<uint32_t>());
     // stable: equal keys keep minmerIndex order -- inserts at one position in index order, evictions in the order a stable sort by wpos_end gives
@@ -365,7 +358,7 @@ int mm_flatten_device_index(mm_ctx* c, const mm_minmer* dRec, size_t n, size_t n
   K_LAUNCH(k_block_events, nBlocks + 1, nBlocks, I.contigBlock.as<int64_t>(), nC, I.contigOff.as<int64_t>(), I.evKey.as<uint32_t>(), (int64_t)nEv, I.evBlock.as<int64_t>());
   int64_t nOpen = 0;
   {
-    DevBuf& cnt = *T.make();
+    DevBuf cnt;
     MM_HIP(c, cnt.ensure((size_t)nBlocks * 4 + 64));
     hipLaunchKernelGGL((k_block_open<false>), dim3((unsigned)((nBlocks + 3) / 4)), dim3(256), 0, c->stream, nBlocks, I.contigBlock.as<int64_t>(), nC, dFirst.as<int64_t>(),
                        dRec, maxLen, cnt.as<int32_t>(), (const int64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint64_t*)nullptr);
@@ -428,9 +421,7 @@ int mm_finalize_index_device(mm_ctx* c, const std::vector<std::pair<const mm_min
   size_t nAll = 0;
   for (const auto& p : parts) nAll += p.second;
   if (nAll >= (1ull << 31)) { c->err = "mm_index_build: more than 2^31 minmer records"; return MM_ERR_CAPACITY; }
-  Tmp T;
-  DevBuf& scratch = *T.make();
-  DevBuf& dAll = *T.make();
+  DevBuf scratch, dAll;
   MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
   unsigned long long* diag = c->dCounters.as<unsigned long long>() + MM_CW_INDEX_BUILD;   // MM_IX_BUILD_*
   MM_HIP(c, hipMemsetAsync(diag, 0, 32, c->stream));
@@ -443,9 +434,9 @@ int mm_finalize_index_device(mm_ctx* c, const std::vector<std::pair<const mm_min
     }
   }
   size_t nk = 0, nRuns = 0;
-  DevBuf& sIdx = *T.make(); DevBuf& flags = *T.make(); DevBuf& pre = *T.make();
+  DevBuf sIdx, flags, pre;
   if (nAll) {
-    DevBuf& h0 = *T.make(); DevBuf& h1 = *T.make(); DevBuf& i0 = *T.make();
+    DevBuf h0, h1, i0;
     MM_HIP(c, h0.ensure(nAll * 8)); MM_HIP(c, h1.ensure(nAll * 8)); MM_HIP(c, i0.ensure(nAll * 4)); MM_HIP(c, sIdx.ensure(nAll * 4));
     K_LAUNCH(k_idx_keys, nAll, nAll, dAll.as<mm_minmer>(), h0.as<uint64_t>(), i0.as<uint32_t>());
     int rc = sort_pairs(c, scratch, h0.as<uint64_t>(), h1.as<uint64_t>(), i0.as<uint32_t>(), sIdx.as<uint32_t>(), nAll, 0u, 64u);
@@ -462,7 +453,7 @@ int mm_finalize_index_device(mm_ctx* c, const std::vector<std::pair<const mm_min
     MM_HIP(c, hipStreamSynchronize(c->stream));
     nRuns = (size_t)(tot & 0xffffffffull); nk = (size_t)(tot >> 32);
     MM_HIP(c, I.keys.ensure(nk * 8 + 64)); MM_HIP(c, I.keyOff.ensure((nk + 1) * 8 + 64)); MM_HIP(c, I.keyFreq.ensure(nk + 64)); MM_HIP(c, I.ptKeys.ensure(2 * nRuns * 8 + 64));
-    DevBuf& runSeq = *T.make();
+    DevBuf runSeq;
     MM_HIP(c, runSeq.ensure(nRuns * 4 + 64));
     K_LAUNCH(k_idx_open, nAll, nAll, dAll.as<mm_minmer>(), h1.as<uint64_t>(), sIdx.as<uint32_t>(), flags.as<uint64_t>(), pre.as<uint64_t>(), I.keys.as<uint64_t>(),
              I.keyOff.as<uint64_t>(), I.ptKeys.as<uint64_t>(), runSeq.as<int32_t>());
@@ -481,9 +472,9 @@ int mm_finalize_index_device(mm_ctx* c, const std::vector<std::pair<const mm_min
   c->hFreq.clear();
   size_t nKeep = nAll;
   const mm_minmer* dRec = dAll.as<mm_minmer>();
-  DevBuf& dMin = *T.make();
+  DevBuf dMin;
   if (nk) {
-    DevBuf& c0 = *T.make(); DevBuf& c1 = *T.make();
+    DevBuf c0, c1;
     MM_HIP(c, c0.ensure(nk * 4)); MM_HIP(c, c1.ensure(nk * 4));
     K_LAUNCH(k_key_counts, nk, nk, I.keyOff.as<uint64_t>(), c0.as<uint32_t>());
     size_t bytes = 0;
@@ -502,13 +493,13 @@ int mm_finalize_index_device(mm_ctx* c, const std::vector<std::pair<const mm_min
     std::memcpy(&freqThreshold, &hd[MM_IX_BUILD_THRESHOLD], 4);
     const size_t nFreq = (size_t)hd[MM_IX_BUILD_NFREQ];
     if (nFreq) {
-      DevBuf& fl = *T.make();
+      DevBuf fl;
       MM_HIP(c, fl.ensure(nFreq * 8));
       K_LAUNCH(k_freq_list, nk, nk, I.keys.as<uint64_t>(), I.keyFreq.as<uint8_t>(), fl.as<uint64_t>(), diag + MM_IX_BUILD_CURSOR);
       c->hFreq.resize(nFreq);
       MM_HIP(c, hipMemcpyAsync(c->hFreq.data(), fl.p, nFreq * 8, hipMemcpyDeviceToHost, c->stream));
       // dropFreqSeedSet: minmerIndex without the frequent hashes, order kept
-      DevBuf& keep = *T.make(); DevBuf& pos = *T.make();
+      DevBuf keep, pos;
       MM_HIP(c, keep.ensure(nAll * 4 + 64)); MM_HIP(c, pos.ensure(nAll * 8 + 64));
       K_LAUNCH(k_keep_flags, nAll, nAll, sIdx.as<uint32_t>(), flags.as<uint64_t>(), pre.as<uint64_t>(), I.keyFreq.as<uint8_t>(), keep.as<int32_t>());
       MM_HIP(c, hipGetLastError());
@@ -570,8 +561,7 @@ int mm_mirror_minmers(mm_ctx* c) {
   const size_t nEv = 2 * I.nRec;
   c->hMinmers.resize(I.nRec);
   if (I.nRec) {
-    Tmp T;
-    DevBuf& f = *T.make(); DevBuf& pos = *T.make(); DevBuf& out = *T.make();
+    DevBuf f, pos, out;
     MM_HIP(c, f.ensure(nEv * 4)); MM_HIP(c, pos.ensure(nEv * 8)); MM_HIP(c, out.ensure(I.nRec * sizeof(mm_minmer)));
     K_LAUNCH(k_insert_flags, nEv, nEv, I.evKey.as<uint32_t>(), f.as<int32_t>());
     int64_t tot = 0;
@@ -593,8 +583,7 @@ int mm_mirror_map(mm_ctx* c) {
   if (I.nKeys) {
     MM_HIP(c, hipMemcpyAsync(c->hKeys.data(), I.keys.p, I.nKeys * 8, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipMemcpyAsync(c->hOffsets.data(), I.keyOff.p, (I.nKeys + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    Tmp T;
-    DevBuf& out = *T.make();
+    DevBuf out;
     MM_HIP(c, out.ensure(I.nPoints * sizeof(mm_interval_point) + 64));
     if (I.nPoints) K_LAUNCH(k_points_unpack, I.nPoints, I.nPoints, I.nKeys, I.keys.as<uint64_t>(), I.keyOff.as<uint64_t>(), I.ptKeys.as<uint64_t>(), out.as<mm_interval_point>());
     MM_HIP(c, hipGetLastError());

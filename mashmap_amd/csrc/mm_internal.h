@@ -10,39 +10,14 @@
 #include <utility>
 #include <vector>
 #include "../../include/mashmap_hip.h"
+#include "mm_devbuf.h"
 
 #define MM_WAVE 64
 
 // ---------------------------------------------------------------------------------------------
 // host-side helpers
 // ---------------------------------------------------------------------------------------------
-inline double g_mmAllocSeconds = 0.0;       // wall time inside hipMalloc / hipFree of DevBuf::ensure (MASHMAP_HIP_TIMING reports it per sized pass; one stream-ordered batch per context)
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipError_t ensure(size_t need) {          // grow-only; contents are NOT preserved
-    if (need <= bytes) return hipSuccess;
-    const auto t0 = std::chrono::steady_clock::now();
-    // the new buffer first, with an eighth of head room; the old one is given up only once the new one is there -- or, when the device
-    // cannot hold both, before a second attempt at the exact size (a failed growth leaves the buffer as it was whenever it can)
-    void* q = nullptr;
-    size_t cap = need + need / 8 + 256;
-    hipError_t e = hipMalloc(&q, cap);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-      e = hipMalloc(&q, cap);
-      if (e != hipSuccess) { (void)hipGetLastError(); cap = need + 256; e = hipMalloc(&q, cap); }
-    } else if (p) {
-      (void)hipFree(p);
-    }
-    if (e == hipSuccess) { p = q; bytes = cap; }
-    g_mmAllocSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
+// (DevBuf, the owner of every device allocation: mm_devbuf.h)
 
 // fragment descriptor on the device
 struct DFrag {
@@ -81,6 +56,12 @@ struct DeviceIndex {
   DevBuf keys, keyOff, keyFreq; // the lookup map's key table in the order of ptKeys: uint64 key, uint64 first point (nKeys + 1), uint8 isFrequent
   bool ready = false;
 };
+// what mm_index_replicate copies to another context.  The replica gets the device index only: neither keys / keyOff / keyFreq nor the
+// host mirrors behind mm_index_download, which stay with the source
+static constexpr DevBuf DeviceIndex::* const MM_REPLICATED_BUFS[] = {
+  &DeviceIndex::evKey, &DeviceIndex::evAux, &DeviceIndex::evHash, &DeviceIndex::contigOff, &DeviceIndex::opKey, &DeviceIndex::opAux, &DeviceIndex::opHash,
+  &DeviceIndex::blockOff, &DeviceIndex::evBlock, &DeviceIndex::contigBlock, &DeviceIndex::contigLen, &DeviceIndex::refGroup, &DeviceIndex::htSlots,
+  &DeviceIndex::htTags, &DeviceIndex::filter, &DeviceIndex::ptKeys};
 
 // ---------------------------------------------------------------------------------------------
 // mm_ctx::dCounters: ONE block of MM_CW_WORDS 64-bit words that the sketch launcher, the index build and every stage of a mapping
@@ -207,7 +188,18 @@ struct mm_env {
 };
 mm_env mm_read_env();
 
-struct mm_ctx {
+// A batch of reads on the device: everything an upload leaves behind.  mm_ctx IS its resident batch (c->nFrags, c->dFrags, ...) and
+// parks others beside it; mm_reads_exchange swaps two of these, by pointer.  Movable, not copyable (DevBuf).
+struct ReadBatch {
+  size_t nReads = 0, nFrags = 0, nPackedBases = 0;
+  int32_t seqCounterBase = 0, maxFragLen = 0;
+  bool windowed = false;                                // --noSplit: some fragment of the batch is longer than segLength (windowLen != 0, computeMap.hpp:933)
+  DevBuf dReadSrcOff, dReadPackOff, dReadLen, dReadGroup, dReadSelf, dReadHasN;
+  DevBuf dBases2, dNmask, dFrags;
+  std::vector<mm_fragment> hFrags;
+};
+
+struct mm_ctx : ReadBatch {                             // the resident reads: the base
   int device = 0;
   hipStream_t stream = nullptr;
   mm_params P{};
@@ -226,25 +218,14 @@ struct mm_ctx {
   DeviceIndex idx;
   DevBuf dMinHits, dCutoffs; size_t nMinHits = 0, nCutoffs = 0;
 
-  // resident reads
-  size_t nReads = 0, nFrags = 0, nPackedBases = 0;
-  int32_t seqCounterBase = 0, maxFragLen = 0;
-  DevBuf dAscii, dReadSrcOff, dReadPackOff, dReadLen, dReadGroup, dReadSelf, dReadHasN;
+  DevBuf dAscii;                                        // the resident batch's ASCII bytes as uploaded (an upload's scratch: not part of ReadBatch)
   // mm_reads_prefetch: the next batch's ASCII bytes, copied on a stream of their own while the current batch is mapped
   DevBuf dAsciiNext; hipStream_t copyStream = nullptr; hipEvent_t copyDone = nullptr;
   const void* prefetchPtr = nullptr; const void* prefetchPtr2 = nullptr; size_t prefetchBytes = 0; bool prefetchValid = false, prefetchPacked = false;
   struct StagedPart { const void* b2; const void* nm; size_t nPacked; size_t off; };   // packed parts sent ahead (mm_reads_prefetch_packed[_append]): [codes | mask] at dAsciiNext + off
   std::vector<StagedPart> staged; size_t stagedBytes = 0;
   std::mutex prefetchMu;                                // mm_reads_prefetch* may come from another thread than the uploads (a reader thread): the staging state is shared
-  DevBuf dBases2, dNmask, dFrags;
-  std::vector<mm_fragment> hFrags;
-  // batches parked beside the resident one (mm_reads_exchange): everything an upload leaves behind, swapped by pointer
-  struct ParkedReads {
-    size_t nReads = 0, nFrags = 0, nPackedBases = 0; int32_t seqCounterBase = 0, maxFragLen = 0; bool windowed = false;
-    DevBuf dReadSrcOff, dReadPackOff, dReadLen, dReadGroup, dReadSelf, dReadHasN, dBases2, dNmask, dFrags;
-    std::vector<mm_fragment> hFrags;
-  };
-  ParkedReads parked[MM_BATCH_SLOTS];
+  ReadBatch parked[MM_BATCH_SLOTS];                     // batches parked beside the resident one (mm_reads_exchange)
 
   // sketches: raw (a4) and after frequent-seed removal (a8)
   DevBuf dSkHash, dSkPos, dSkStrand, dSkCount;          // [nFrags*s] u64, int2, i8 ; [nFrags] u32
@@ -254,8 +235,7 @@ struct mm_ctx {
   DevBuf dStats;                                        // mm_frag_stats[nFrags]
   DevBuf dPtOff, dPts; size_t ptsCap = 0;               // per-fragment offset (int64) + sorted keys
   DevBuf dPtKept;                                       // int32[nFrags]: points of a queued fragment that reach the L1 kernels (k_gather_points, k_filter_points)
-  // --noSplit with reads longer than segLength (windowLen != 0, computeMap.hpp:933): the literal kernels' state
-  bool windowed = false;                                // some resident fragment is longer than segLength
+  // --noSplit with reads longer than segLength (ReadBatch::windowed): the literal kernels' state
   DevBuf dPtIds, dWinFreq, dWinExt, dWinHeap, dWinKeys, dWinVals, dWinOffH, dWinOffT, dWinCntH, dWinCntT;
   DevBuf dL1, dL1b, dL1Cursors; size_t l1Cap = 0, nL1 = 0;   // dL1b: the region-filled buffer k_l1_compact reads from
   DevBuf dL1Off;                                        // int64[nFrags] first candidate of a fragment
@@ -283,7 +263,6 @@ struct mm_ctx {
   // overlapped exchange (mm_allgatherv_mappings_begin / _end): a snapshot of the records, a stream of its own, the host thread that
   // runs the exchange while the caller maps the next batch
   DevBuf dGatherSrc; hipStream_t commStream = nullptr; std::thread gatherThread; int gatherRc = 0; std::string gatherErr;
-  std::vector<DevBuf*> allBufs();
   DevBuf dL2Info, dL2Cnt, dL2Off, dL2Ops, dScanTmp, dL2Tmp, dL2Wide, dL2Exact, dL2Cells, dListB, dListC, dBigList, dMidList, dGrpList;     // L2 staging: per-candidate stream extents, op counts/offsets, located ops
   DevBuf dL2InitCells, dL2InitState;                                 // per candidate of a chunk: the SlideMapper state after the pre-load, as k_l2_locate leaves it for the sweeps
   DevBuf dL2Sort[4], dL2Order, dL2OrderPos;                          // candidates of a chunk in order of descending stream length (mm_order_desc)

@@ -59,7 +59,6 @@ int mm_build_device_index(mm_ctx* c, const int32_t* contigLen, const int32_t* re
   if (np) MM_HIP(c, hipMemcpyAsync(I.ptKeys.p, pk.data(), np * 8, hipMemcpyHostToDevice, c->stream));
   MM_HIP(c, hipStreamSynchronize(c->stream));
   const int rc = mm_flatten_device_index(c, dRec.as<mm_minmer>(), n, nk, np, contigLen, refGroup, nContigs);
-  dRec.release();
   c->mirrorMinmers = c->mirrorMap = true;
   return rc;
 }
@@ -1885,7 +1884,7 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
     DevBuf nb; MM_HIP(c, nb.ensure(newCap * sizeof(mm_l1_candidate) + 64));
     if (fusedL1) MM_HIP(c, hipMemcpyAsync(nb.p, c->dL1.p, (size_t)fusedL1 * sizeof(mm_l1_candidate), hipMemcpyDeviceToDevice, c->stream));
     MM_SYNC(c);
-    c->dL1.release(); c->dL1 = nb; p.denseCap = newCap;
+    c->dL1 = std::move(nb); p.denseCap = newCap;
     if (c->l1Cap < newCap) c->l1Cap = newCap;                  // the next pass sizes both candidate buffers for it: no retry, no reallocation
   }
   c->err = "L1 candidate buffer overflow"; return MM_ERR_CAPACITY;

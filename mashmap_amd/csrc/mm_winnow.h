@@ -26,12 +26,7 @@ struct WinnowBuffers {       // grow-only device scratch shared by the contigs o
     hb = cap;
     return h;
   }
-  void release() {
-    for (int i = 0; i < 2; i++) if (hStage[i]) { (void)hipHostFree(hStage[i]); hStage[i] = nullptr; hStageBytes[i] = 0; }
-    DevBuf* all[] = {&blockCnt, &blockOff, &cPos, &cHash, &cSt, &out, &outCount, &outOff, &open, &openCount, &status, &dense,
-                     &redoList, &out2, &outCount2, &open2, &openCount2, &status2, &skScratch};
-    for (DevBuf* b : all) b->release();
-  }
+  ~WinnowBuffers() { for (void* h : hStage) if (h) (void)hipHostFree(h); }   // the two page-locked areas; the device buffers free themselves
 };
 
 // records in the reference's emission order (wpos == WN_CARRY where the run started before its tile), per-tile record counts,
