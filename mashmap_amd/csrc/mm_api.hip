@@ -89,14 +89,15 @@ int mm_synchronize(mm_ctx* c) { MM_HIP(c, hipStreamSynchronize(c->stream)); retu
 void* mm_stream(const mm_ctx* c) { return (void*)c->stream; }
 
 int mm_set_option(mm_ctx* c, int option, int value) {
-  if (option == MM_OPT_KEEP_POINTS) { c->keepPoints = value != 0; c->keepFiltered = value == 2; c->ptsCap = 0; return MM_OK; }
-  if (option == MM_OPT_KEEP_FULL_INDEX) { c->keepFullIndex = value != 0; return MM_OK; }
-  if (option == MM_OPT_RESERVE_FRAGMENTS) { c->reserveFrags = value > 0 ? (size_t)value : 0; return MM_OK; }
-  if (option == MM_OPT_L1_GROUP_STREAM) { c->l1GroupStream = value != 0; return MM_OK; }
-  if (option == MM_OPT_L1_GROUP_FUSED) { c->l1GroupFused = value != 0; return MM_OK; }
-  if (option == MM_OPT_L2_WINDOW_WAVE) { c->l2WindowWave = value != 0; return MM_OK; }
-  if (option == MM_OPT_L2_LARGE_WAVE) { c->l2LargeWave = value & 3; return MM_OK; }
-  if (option == MM_OPT_CHAIN_LONG) { c->chainLong = value != 0; return MM_OK; }
+  Options& o = c->opt;
+  if (option == MM_OPT_KEEP_POINTS) { o.keepPoints = value != 0; o.keepFiltered = value == 2; c->ptsCap = 0; return MM_OK; }
+  if (option == MM_OPT_KEEP_FULL_INDEX) { o.keepFullIndex = value != 0; return MM_OK; }
+  if (option == MM_OPT_RESERVE_FRAGMENTS) { o.reserveFrags = value > 0 ? (size_t)value : 0; return MM_OK; }
+  if (option == MM_OPT_L1_GROUP_STREAM) { o.l1GroupStream = value != 0; return MM_OK; }
+  if (option == MM_OPT_L1_GROUP_FUSED) { o.l1GroupFused = value != 0; return MM_OK; }
+  if (option == MM_OPT_L2_WINDOW_WAVE) { o.l2WindowWave = value != 0; return MM_OK; }
+  if (option == MM_OPT_L2_LARGE_WAVE) { o.l2LargeWave = value & 3; return MM_OK; }
+  if (option == MM_OPT_CHAIN_LONG) { o.chainLong = value != 0; return MM_OK; }
   c->err = "mm_set_option: unknown option"; return MM_ERR_ARG;
 }
 
@@ -228,9 +229,9 @@ static int finish_upload(mm_ctx* c, size_t nReads, int64_t pk, const std::vector
 
 static int ensure_read_buffers(mm_ctx* c, size_t nReads, int64_t pk, size_t nFrags) {
   // MM_OPT_RESERVE_FRAGMENTS: room for the largest announced batch right away (its fragments are full segments; a read has at least one)
-  if (c->reserveFrags > nFrags) {
-    const int64_t pkR = (int64_t)c->reserveFrags * (int64_t)c->P.segLength; pk = pkR > pk ? pkR + pkR / 64 : pk;
-    nReads = std::max(nReads, c->reserveFrags); nFrags = c->reserveFrags;
+  if (c->opt.reserveFrags > nFrags) {
+    const int64_t pkR = (int64_t)c->opt.reserveFrags * (int64_t)c->P.segLength; pk = pkR > pk ? pkR + pkR / 64 : pk;
+    nReads = std::max(nReads, c->opt.reserveFrags); nFrags = c->opt.reserveFrags;
   }
   MM_HIP(c, c->dReadSrcOff.ensure((nReads + 1) * 8)); MM_HIP(c, c->dReadPackOff.ensure((nReads + 1) * 8));
   MM_HIP(c, c->dReadLen.ensure(nReads * 4 + 4)); MM_HIP(c, c->dReadGroup.ensure(nReads * 4 + 4)); MM_HIP(c, c->dReadSelf.ensure(nReads * 4 + 4));
@@ -263,7 +264,7 @@ static int upload_reads_ascii(mm_ctx* c, const void* ascii, bool onDevice, const
   }
   srcOff[nReads] = readOffsets[nReads]; packOff[nReads] = pk;
   c->nReads = nReads; c->nFrags = dfr.size(); c->nPackedBases = (size_t)pk; c->seqCounterBase = seqCounterBase; c->maxFragLen = maxLen;
-  c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false;
+  mm_batch_changed(c);
   c->windowed = anyLong;
   const size_t srcBase = (size_t)readOffsets[0];
   const size_t nSrc = (size_t)(readOffsets[nReads] - readOffsets[0]);
@@ -333,7 +334,7 @@ static int upload_packed_parts(mm_ctx* c, const mm_packed_part* parts, size_t nP
   }
   partBase[nParts] = pk; packOff[nReads] = pk;
   c->nReads = nReads; c->nFrags = dfr.size(); c->nPackedBases = (size_t)pk; c->seqCounterBase = seqCounterBase; c->maxFragLen = maxLen;
-  c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false;
+  mm_batch_changed(c);
   c->windowed = anyLong;
   c->prefetchValid = false;                           // (an ASCII prefetch, if any, is not for this upload)
   { const int rc = ensure_read_buffers(c, nReads, pk, dfr.size()); if (rc != MM_OK) return rc; }
@@ -491,7 +492,7 @@ int mm_reads_exchange(mm_ctx* c, int slot) {
   MM_HIP(c, hipSetDevice(c->device));
   MM_HIP(c, hipStreamSynchronize(c->stream));                // nothing queued still reads the outgoing batch
   std::swap(static_cast<ReadBatch&>(*c), c->parked[slot]);
-  c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false;
+  mm_batch_changed(c);
   return MM_OK;
 }
 
@@ -545,87 +546,89 @@ int mm_map_fragments(mm_ctx* c) {
   if (!c->nMinHits) { c->err = "mm_map_fragments: mm_set_tables first"; return MM_ERR_STATE; }
   MM_HIP(c, hipSetDevice(c->device));
   const auto t0 = std::chrono::steady_clock::now();
-  const double a0 = g_mmAllocSeconds;
+  const uint64_t a0 = g_mmAllocNanos.load(std::memory_order_relaxed);
   int rc = mm_launch_sketch(c);
   if (rc != MM_OK) return rc;
   c->sketched = true;
   const auto t1 = std::chrono::steady_clock::now();
   rc = mm_launch_map(c);
   if (rc != MM_OK) return rc;
-  if (!c->lastSteady) { MM_HIP(c, hipStreamSynchronize(c->stream)); c->nSyncs++; }   // a steady-state pass ends with its one synchronisation
-  if (c->env.timing && !c->lastSteady) {
+  if (!c->rep.lastSteady) MM_SYNC(c);   // a steady-state pass ends with its one synchronisation
+  if (c->env.timing && !c->rep.lastSteady) {
     auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     fprintf(stderr, "[mashmap_hip::timing] sized pass (%zu fragments, %llu host waits): sketch launch %.4f s, lookup .. selection %.4f s, of both in hipMalloc / hipFree %.4f s\n",
-            c->nFrags, (unsigned long long)c->nSyncs, sec(t0, t1), sec(t1, std::chrono::steady_clock::now()), g_mmAllocSeconds - a0);
+            c->nFrags, (unsigned long long)c->rep.nSyncs, sec(t0, t1), sec(t1, std::chrono::steady_clock::now()), (double)(g_mmAllocNanos.load(std::memory_order_relaxed) - a0) * 1e-9);
   }
   if (c->profile) mm_profile_collect(c);
   c->mapped = true;
-  c->nPasses++; if (c->lastSteady) c->nSteadyPasses++;
+  c->tot.nPasses++; if (c->rep.lastSteady) c->tot.nSteadyPasses++;
   return MM_OK;
 }
 
 int mm_pass_totals(const mm_ctx* c, uint64_t* passes, uint64_t* steadyPasses, uint64_t* redonePasses) {
-  if (passes) *passes = c->nPasses;
-  if (steadyPasses) *steadyPasses = c->nSteadyPasses;
-  if (redonePasses) *redonePasses = c->nRedone;
+  if (passes) *passes = c->tot.nPasses;
+  if (steadyPasses) *steadyPasses = c->tot.nSteadyPasses;
+  if (redonePasses) *redonePasses = c->tot.nRedone;
   return MM_OK;
 }
 
 int mm_pass_redo_cause(const mm_ctx* c, uint64_t* cause) {
-  if (cause) *cause = c->redoCause;
+  if (cause) *cause = c->rep.redoCause;
   return MM_OK;
 }
 
 int mm_pass_l1_literal(const mm_ctx* c, uint64_t* queued, uint64_t* literal) {
-  if (queued) *queued = c->prevBig;
-  if (literal) *literal = c->prevLit;
+  if (queued) *queued = c->sized.seen.prevBig;
+  if (literal) *literal = c->sized.seen.prevLit;
   return MM_OK;
 }
 
 int mm_pass_l1_group_fused(const mm_ctx* c, uint64_t* offered, uint64_t* fused) {
-  if (offered) *offered = c->grpOffered;
-  if (fused) *fused = c->grpFused;
+  if (offered) *offered = c->sized.seen.grpOffered;
+  if (fused) *fused = c->sized.seen.grpFused;
   return MM_OK;
 }
 
 int mm_pass_l2_large(const mm_ctx* c, uint64_t* candidates, uint64_t* literal) {
-  if (candidates) *candidates = c->lwCands;
-  if (literal) *literal = c->lwLit;
+  if (candidates) *candidates = c->sized.seen.lwCands;
+  if (literal) *literal = c->sized.seen.lwLit;
   return MM_OK;
 }
 int mm_pass_l2_window(const mm_ctx* c, uint64_t* candidates, uint64_t* literal) {
-  if (candidates) *candidates = c->winCands;
-  if (literal) *literal = c->winLit;
+  if (candidates) *candidates = c->sized.seen.winCands;
+  if (literal) *literal = c->sized.seen.winLit;
   return MM_OK;
 }
 
 int mm_pass_stats(const mm_ctx* c, uint64_t* hostSyncs, int* steady, uint64_t* counts) {
   if (!c->mapped) return MM_ERR_STATE;
-  if (hostSyncs) *hostSyncs = c->nSyncs;
-  if (steady) *steady = c->lastSteady ? 1 : 0;
-  if (counts) { counts[0] = c->nL1; counts[1] = c->nL2; counts[2] = c->lastBig; counts[3] = c->lastOps; counts[4] = c->lastHard; }
+  const PassReport& r = c->rep;
+  if (hostSyncs) *hostSyncs = r.nSyncs;
+  if (steady) *steady = r.lastSteady ? 1 : 0;
+  if (counts) { counts[0] = r.nL1; counts[1] = r.nL2; counts[2] = r.lastBig; counts[3] = r.lastOps; counts[4] = r.lastHard; }
   return MM_OK;
 }
 
 int mm_result_counts(const mm_ctx* c, size_t* nL1, size_t* nL2) {
   if (!c->mapped) return MM_ERR_STATE;
-  if (nL1) *nL1 = c->nL1;
-  if (nL2) *nL2 = c->nL2;
+  if (nL1) *nL1 = c->rep.nL1;
+  if (nL2) *nL2 = c->rep.nL2;
   return MM_OK;
 }
 
 int mm_results_device(const mm_ctx* c, const mm_l2_locus** dL2, size_t* nL2) {
   if (!c->mapped) return MM_ERR_STATE;
   if (dL2) *dL2 = c->dL2.as<mm_l2_locus>();
-  if (nL2) *nL2 = c->nL2;
+  if (nL2) *nL2 = c->rep.nL2;
   return MM_OK;
 }
 
 int mm_results_copy_device(mm_ctx* c, mm_l2_locus* dDst, size_t cap, size_t* n) {
   if (!c->mapped) { c->err = "mm_results_copy_device: nothing mapped"; return MM_ERR_STATE; }
-  if (n) *n = c->nL2;
-  if (c->nL2 > cap) { c->err = "mm_results_copy_device: destination too small"; return MM_ERR_ARG; }
-  if (c->nL2) MM_HIP(c, hipMemcpyAsync(dDst, c->dL2.p, c->nL2 * sizeof(mm_l2_locus), hipMemcpyDeviceToDevice, c->stream));
+  const size_t nL2 = c->rep.nL2;
+  if (n) *n = nL2;
+  if (nL2 > cap) { c->err = "mm_results_copy_device: destination too small"; return MM_ERR_ARG; }
+  if (nL2) MM_HIP(c, hipMemcpyAsync(dDst, c->dL2.p, nL2 * sizeof(mm_l2_locus), hipMemcpyDeviceToDevice, c->stream));
   MM_HIP(c, hipStreamSynchronize(c->stream));
   return MM_OK;
 }

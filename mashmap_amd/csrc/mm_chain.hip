@@ -242,7 +242,7 @@ int mm_chain_reads(mm_ctx* c) {
   if (!c->haveChainTables) { c->err = "mm_chain_reads: mm_set_chain_tables was not called"; return MM_ERR_STATE; }
   if (!c->mapped || !c->haveReplayTables) { c->err = "mm_chain_reads: nothing mapped, or mm_set_replay_tables / mm_set_tables_default was not called"; return MM_ERR_STATE; }
   c->chOffered = c->chFinished = c->chRows = c->chLeft = 0; c->chLongOffered = c->chLongFinished = 0;
-  const size_t nR = c->nReads, nM = c->nMappings;
+  const size_t nR = c->nReads, nM = c->rep.nMappings;
   if (nM > (size_t)0x7fffffff || nR > (size_t)0x7fffffff) { c->err = "mm_chain_reads: more than 2^31 - 1 records in one batch"; return MM_ERR_CAPACITY; }
   if (nR && nM) {
     MM_HIP(c, hipSetDevice(c->device));
@@ -251,7 +251,7 @@ int mm_chain_reads(mm_ctx* c) {
     MM_HIP(c, c->dChainOffR.ensure(nR * 8 + 64)); MM_HIP(c, c->dChainOffL.ensure(nR * 8 + 64));
     MM_HIP(c, c->dChainRows.ensure(nM * sizeof(mm_chain_row) + 64)); MM_HIP(c, c->dChainLeft.ensure(nM * sizeof(mm_mapping) + 64));   // a read leaves at most as many rows as it has records
     MM_HIP(c, c->dChainTotals.ensure(MM_CT_WORDS * 8));
-    const int longOn = c->chainLong ? 1 : 0;
+    const int longOn = c->opt.chainLong ? 1 : 0;
     if (longOn) {
       MM_HIP(c, c->dChainLongList.ensure(nR * 4 + 64)); MM_HIP(c, c->dChainStage.ensure(nM * sizeof(mm_chain_row) + 64));
       if (!c->chainCUs) { int cus = 0; MM_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device)); c->chainCUs = cus > 0 ? cus : 1; }
@@ -297,11 +297,11 @@ int mm_chain_reads(mm_ctx* c) {
     if (h[MM_CT_BAD]) { c->err = "mm_chain_reads: corrupt record: a candidate mapping names a sketch size or shared count outside the identity table"; return MM_ERR_STATE; }
     if (c->chRows > nM || c->chLeft > nM) { c->err = "mm_chain_reads: internal error: more rows or left-over records than records"; return MM_ERR_CAPACITY; }
   }
-  c->chainPass = c->nPasses;
+  c->chainPass = c->tot.nPasses;
   return MM_OK;
 }
 
-static bool chain_valid(const mm_ctx* c) { return c->mapped && c->chainPass != 0 && c->chainPass == c->nPasses; }
+static bool chain_valid(const mm_ctx* c) { return c->mapped && c->chainPass != 0 && c->chainPass == c->tot.nPasses; }
 
 int mm_chain_counts(const mm_ctx* c, size_t* offered, size_t* finished, size_t* rows, size_t* leftover) {
   if (!chain_valid(c)) { const_cast<mm_ctx*>(c)->err = "mm_chain_counts: mm_chain_reads has not run on the mapped batch"; return MM_ERR_STATE; }

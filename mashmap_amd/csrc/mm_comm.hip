@@ -212,7 +212,7 @@ int mm_allgatherv_mappings(mm_ctx* c) {
   Rccl* R = rccl_open(c->env, c->err);
   if (!R) return MM_ERR_DEVICE;
   c->gathered = false;
-  const int rc = exchange(c, c, R, c->dMappings.p, c->nMappings, c->stream);
+  const int rc = exchange(c, c, R, c->dMappings.p, c->rep.nMappings, c->stream);
   if (rc != MM_OK) return rc;
   c->gathered = true;
   return MM_OK;
@@ -227,7 +227,7 @@ int mm_allgatherv_mappings_begin(mm_ctx* c) {
   MM_HIP(c, hipSetDevice(c->device));
   if (!c->commStream) MM_HIP(c, hipStreamCreateWithFlags(&c->commStream, hipStreamNonBlocking));
   // snapshot: the next mm_map_fragments overwrites dMappings while the exchange is in flight
-  const size_t n = c->nMappings;
+  const size_t n = c->rep.nMappings;
   MM_HIP(c, c->dGatherSrc.ensure(n * sizeof(mm_mapping) + 64));
   if (n) MM_HIP(c, hipMemcpyAsync(c->dGatherSrc.p, c->dMappings.p, n * sizeof(mm_mapping), hipMemcpyDeviceToDevice, c->stream));
   MM_HIP(c, hipStreamSynchronize(c->stream));
@@ -260,7 +260,7 @@ int mm_allgatherv_mappings_local(mm_ctx** ctxs, int n) {
   for (int i = 0; i < n; i++) {
     mm_ctx* c = ctxs[i];
     c->gatherCounts.resize(n);
-    for (int r = 0; r < n; r++) c->gatherCounts[r] = ctxs[r]->nMappings;
+    for (int r = 0; r < n; r++) c->gatherCounts[r] = ctxs[r]->rep.nMappings;
     place(c);
     MM_HIP(c, hipSetDevice(c->device));
     MM_HIP(c, c->dGathered.ensure(c->nGathered * sizeof(mm_mapping) + 64));

@@ -4,10 +4,12 @@
 #include <hip/hip_runtime_api.h>
 #include <atomic>
 #include <chrono>
+#include <stdint.h>
 #include <utility>
 
-inline double g_mmAllocSeconds = 0.0;       // wall time inside hipMalloc / hipFree of DevBuf::ensure (MASHMAP_HIP_TIMING reports it per sized pass; one stream-ordered batch per context)
-inline std::atomic<size_t> g_mmDeviceBytes{0};   // bytes all DevBufs of the process hold (mm_device_bytes); atomic: prefetch, upload and the gather thread run concurrently
+// both atomic: prefetch, upload and the gather thread run ensure() concurrently
+inline std::atomic<uint64_t> g_mmAllocNanos{0};  // nanoseconds of wall time inside hipMalloc / hipFree of DevBuf::ensure (MASHMAP_HIP_TIMING reports them per sized pass)
+inline std::atomic<size_t> g_mmDeviceBytes{0};   // bytes all DevBufs of the process hold (mm_device_bytes)
 
 // owns its allocation: freed by the destructor, moved but never copied
 struct DevBuf {
@@ -37,7 +39,7 @@ struct DevBuf {
       if (e != hipSuccess) { (void)hipGetLastError(); cap = need + 256; e = hipMalloc(&q, cap); }
     } else release();
     if (e == hipSuccess) { p = q; bytes = cap; g_mmDeviceBytes += cap; }
-    g_mmAllocSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    g_mmAllocNanos.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(), std::memory_order_relaxed);
     return e;
   }
   void release() {

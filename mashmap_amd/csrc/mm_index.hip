@@ -221,7 +221,7 @@ static int finalize_built_index(mm_ctx* c, std::vector<std::vector<mm_minmer>>& 
   for (const auto& v : per) parts.emplace_back(v.data(), v.size());
   const int rc = mm_finalize_index_device(c, parts, kmerPctThreshold, contigLen, refGroup, nContigs);
   std::vector<mm_minmer>().swap(c->hMinmersAll);
-  if (c->keepFullIndex) for (const auto& v : per) c->hMinmersAll.insert(c->hMinmersAll.end(), v.begin(), v.end());   // --saveIndex wants minmerIndex before the drop
+  if (c->opt.keepFullIndex) for (const auto& v : per) c->hMinmersAll.insert(c->hMinmersAll.end(), v.begin(), v.end());   // --saveIndex wants minmerIndex before the drop
   return rc;
 }
 
@@ -248,7 +248,7 @@ static int finalize_index(mm_ctx* c, std::vector<mm_minmer>& all, bool haveMap, 
   }
   for (size_t i = 0; i < nKeysAll; i++)
     if ((int64_t)(c->hOffsets[i + 1] - c->hOffsets[i]) >= (int64_t)freqThreshold) c->hFreq.push_back(c->hKeys[i]);
-  if (c->keepFullIndex) c->hMinmersAll = all; else std::vector<mm_minmer>().swap(c->hMinmersAll);
+  if (c->opt.keepFullIndex) c->hMinmersAll = all; else std::vector<mm_minmer>().swap(c->hMinmersAll);
   if (!c->hFreq.empty())
     all.erase(std::remove_if(all.begin(), all.end(), [&](const mm_minmer& m) { return std::binary_search(c->hFreq.begin(), c->hFreq.end(), m.hash); }), all.end());
   c->hMinmers.swap(all);
@@ -350,7 +350,7 @@ extern "C" int mm_index_upload_full(mm_ctx* c, const mm_minmer* minmersAll, size
 }
 
 extern "C" int mm_index_download_full(mm_ctx* c, mm_minmer* out, size_t* n) {
-  if (!c->idx.ready || !c->keepFullIndex) { c->err = "mm_index_download_full: needs MM_OPT_KEEP_FULL_INDEX before the index is built"; return MM_ERR_STATE; }
+  if (!c->idx.ready || !c->opt.keepFullIndex) { c->err = "mm_index_download_full: needs MM_OPT_KEEP_FULL_INDEX before the index is built"; return MM_ERR_STATE; }
   if (n) *n = c->hMinmersAll.size();
   if (out && !c->hMinmersAll.empty()) std::memcpy(out, c->hMinmersAll.data(), c->hMinmersAll.size() * sizeof(mm_minmer));
   return MM_OK;

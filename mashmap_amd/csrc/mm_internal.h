@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/mashmap_hip.h"
 #include "mm_devbuf.h"
+#include "mm_pass_state.h"
 
 #define MM_WAVE 64
 
@@ -91,8 +92,8 @@ enum : int {
 
 // Words of the mapping pass, relative to MM_CW_PASS.  Two of them are used twice, by stages that do not overlap in time: the L2 sweep
 // launcher resets them when the L1 stage is done with them.  A steady-state pass reads the block back once, at its end, and so sees
-// the L2 sweep's values there: it cannot report how many fragments went through the HBM point path, and mm_ctx::lastBig repeats the
-// figure of the last sized pass (prevBig) instead.
+// the L2 sweep's values there: it cannot report how many fragments went through the HBM point path, and PassReport::lastBig repeats the
+// figure of the last sized pass (SizedPass::Seen::prevBig) instead.
 enum : int {
   MM_PC_POINT_CURSOR   = 0,   // L1 stage: interval points handed out in dPts
   MM_PC_L2_EXACT_LEN   = 0,   // L2 sweep: candidates on the list of k_l2_sweep_exact (dL2Exact)
@@ -205,11 +206,15 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   mm_params P{};
   mm_env env;
   std::string err;
+  Options opt;                                          // mm_set_option
+  // a mapping pass's bookkeeping, by lifetime (mm_pass_state.h): the last mm_map_fragments, the last sized pass, the context
+  PassReport rep;
+  SizedPass sized;
+  PassTotals tot;
 
   // host mirrors needed for downloads in reference layout
   std::vector<mm_minmer> hMinmers;
-  std::vector<mm_minmer> hMinmersAll;                   // minmerIndex before dropFreqSeedSet (only with MM_OPT_KEEP_FULL_INDEX: --saveIndex)
-  bool keepFullIndex = false;
+  std::vector<mm_minmer> hMinmersAll;                   // minmerIndex before dropFreqSeedSet (only with Options::keepFullIndex: --saveIndex)
   std::vector<uint64_t> hKeys, hOffsets, hFreq;
   std::vector<mm_interval_point> hPoints;
   bool mirrorMinmers = false, mirrorMap = false;        // the host copies above are filled (a device-built index fills them on request)
@@ -237,23 +242,22 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   DevBuf dPtKept;                                       // int32[nFrags]: points of a queued fragment that reach the L1 kernels (k_gather_points, k_filter_points)
   // --noSplit with reads longer than segLength (ReadBatch::windowed): the literal kernels' state
   DevBuf dPtIds, dWinFreq, dWinExt, dWinHeap, dWinKeys, dWinVals, dWinOffH, dWinOffT, dWinCntH, dWinCntT;
-  DevBuf dL1, dL1b, dL1Cursors; size_t l1Cap = 0, nL1 = 0;   // dL1b: the region-filled buffer k_l1_compact reads from
+  DevBuf dL1, dL1b, dL1Cursors; size_t l1Cap = 0;   // dL1b: the region-filled buffer k_l1_compact reads from
   DevBuf dL1Off;                                        // int64[nFrags] first candidate of a fragment
   DevBuf dL1Regions;                                    // L1Regions: fill count + prefix position of the 64 output regions (k_l1_regions)
-  DevBuf dL2; size_t l2Cap = 0, nL2 = 0;
+  DevBuf dL2; size_t l2Cap = 0;
   DevBuf dL2First, dL2Num;                              // per L1 candidate: first locus in dL2 (int64) and count (int32)
   // candidate mappings (mm_select.hip)
   DevBuf dAccept, dMinIsz; bool haveReplayTables = false;
-  DevBuf dSelCnt, dSelOff, dSelHeap, dFragTab, dMappings; size_t nMappings = 0; bool fragTabStale = true;
+  DevBuf dSelCnt, dSelOff, dSelHeap, dFragTab, dMappings; bool fragTabStale = true;
   // chaining and filtering on the device (mm_chain.hip): the identity table and parameter block of mm_set_chain_tables; per read the
   // record range, row / left-over counts and their scans; the two output arrays; the four counts of the last mm_chain_reads
   DevBuf dChainIdent, dChainBegin, dChainEnd, dChainCntR, dChainCntL, dChainOffR, dChainOffL, dChainRows, dChainLeft, dChainTotals;
   mm_chain_params chainP{}; bool haveChainTables = false;
-  uint64_t chainPass = 0;                               // nPasses when mm_chain_reads last went through: its results belong to that pass (0: none)
+  uint64_t chainPass = 0;                               // tot.nPasses when mm_chain_reads last went through: its results belong to that pass (0: none)
   size_t chOffered = 0, chFinished = 0, chRows = 0, chLeft = 0;
   // MM_OPT_CHAIN_LONG: the list of reads with 17 .. 512 records (filled by the count pass), the rows k_chain_reads_long leaves at each
   // read's record offset, and the two counts of mm_chain_long_counts
-  bool chainLong = false;
   DevBuf dChainLongList, dChainStage;
   uint64_t chLongOffered = 0, chLongFinished = 0;
   int chainCUs = 0;                                     // compute units of the device (k_chain_reads_long's grid), asked for once
@@ -267,27 +271,8 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   DevBuf dL2InitCells, dL2InitState;                                 // per candidate of a chunk: the SlideMapper state after the pre-load, as k_l2_locate leaves it for the sweeps
   DevBuf dL2Sort[4], dL2Order, dL2OrderPos;                          // candidates of a chunk in order of descending stream length (mm_order_desc)
   bool sketched = false, mapped = false;
-  // steady state: the previous pass of this context went through and left every buffer sized (mm_launch_map); what it saw
-  bool steadyOk = false, lastSteady = false; size_t prevBig = 0, candCap = 0, l2Chunks = 1, sizedFrags = 0; int prevLocap = 0, steadyFails = 0;   // sizedFrags: fragments of the last sized pass
   unsigned long long* hPass = nullptr;                  // page-locked mirror of dCounters (MM_COUNTER_BYTES, word for word): the parts a pass reads back at its end
-  size_t lastHard = 0;                                  // fragments the fast sketch kernel handed to the hard list in the last pass
-  size_t prevMid = 0, lastMid = 0; bool midKnown = false;   // fragments k_lookup_mid took in the last sized pass (its grid in the steady-state passes behind it)
-  size_t lastOps = 0, lastBig = 0;                      // L2 stream entries reserved / fragments queued for the HBM point path in the last pass
-  size_t prevLit = 0;                                   // of prevBig, the fragments the literal k_l1_sweep took in the last sized pass (mm_pass_l1_literal)
-  size_t nSyncs = 0;                                    // host synchronisations inside the last mm_map_fragments (diagnostics: mm_pass_syncs)
-  uint64_t nPasses = 0, nSteadyPasses = 0, nRedone = 0; // mm_map_fragments calls of this context: all, those that went through as steady-state passes, steady attempts redone the sized way
-  uint64_t redoCause = 0;                               // MM_REDO_* of the steady attempt the last mm_map_fragments had redone, 0 when it had none (mm_pass_redo_cause)
-  bool keepFiltered = false;                            // MM_OPT_KEEP_POINTS = 2: ... and k_filter_points runs on them as it does on a queued fragment's (mm_points_download returns what it leaves)
-  bool keepPoints = false;                              // mm_set_option(MM_OPT_KEEP_POINTS): route every fragment through the HBM point list
-  bool l1GroupStream = false;                           // mm_set_option(MM_OPT_L1_GROUP_STREAM): under MM_FLAG_SKIP_PREFIX the queued fragments go to the grouped k_l1_stream first
-  bool l1GroupFused = false;                            // mm_set_option(MM_OPT_L1_GROUP_FUSED): under MM_FLAG_SKIP_PREFIX the queued fragments go through k_lookup_groups first; the HBM point path takes what it hands over
   bool refGroupMonotone = true;                         // the index's refGroup array is non-decreasing (checked where it arrives: mm_flatten_device_index; mm_index_replicate carries it)
-  size_t grpOffered = 0, grpFused = 0;                  // last sized pass: fragments offered to k_lookup_groups and those it finished (mm_pass_l1_group_fused); 0 / 0 when it was not launched
-  bool l2WindowWave = false;                            // mm_set_option(MM_OPT_L2_WINDOW_WAVE): the windowed L2 stage on k_l2_window_wave first, the literal k_l2_window takes what it hands over
-  int l2LargeWave = 0;                                  // mm_set_option(MM_OPT_L2_LARGE_WAVE): bit 0: split batches on the literal L2 route go to k_l2_large_wave first; bit 1: split batches take that route at any sketch size
-  size_t lwCands = 0, lwLit = 0;                        // candidates of a split batch the literal L2 route took in the last sized pass, and those k_l2_window swept (mm_pass_l2_large)
-  size_t winCands = 0, winLit = 0;                      // candidates the windowed L2 stage took in the last sized pass, and those k_l2_window swept (mm_pass_l2_window)
-  size_t reserveFrags = 0;                              // mm_set_option(MM_OPT_RESERVE_FRAGMENTS): fragments of the largest batch the caller will upload; sized passes size for it
 
   // profiling
   bool profile = false;
@@ -298,6 +283,9 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   std::vector<std::pair<int, size_t>> evPending;                              // (kernel, pool index)
 };
 
+// the resident batch changed (an upload, an exchange): nothing sketched, mapped or gathered belongs to it
+inline void mm_batch_changed(mm_ctx* c) { c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false; }
+
 #define MM_HIP(ctx, call)                                                                        \
   do {                                                                                           \
     hipError_t e__ = (call);                                                                     \
@@ -307,7 +295,7 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
     }                                                                                            \
   } while (0)
 // a host synchronisation of a mapping pass: counted (mm_pass_syncs)
-#define MM_SYNC(c) do { MM_HIP(c, hipStreamSynchronize((c)->stream)); (c)->nSyncs++; } while (0)
+#define MM_SYNC(c) do { MM_HIP(c, hipStreamSynchronize((c)->stream)); (c)->rep.nSyncs++; } while (0)
 
 // RAII hipEvent bracket on the ctx stream.  The two events are only RECORDED here (a pair out of a pool that grows with the number of
 // brackets in flight); their times are read by mm_profile_collect once the stream has been synchronised anyway -- measuring a pass does
@@ -344,14 +332,14 @@ inline void mm_profile_collect(mm_ctx* c) {
 // MM_OPT_RESERVE_FRAGMENTS: a sized pass over a small batch sizes every staging buffer for the largest batch the caller has announced, so
 // that the larger batches behind it are steady-state passes instead of being sized (and their buffers reallocated) again.
 //   mm_frag_cap: fragments to size per-fragment buffers for;  mm_scaled: a count of this pass scaled to what the announced batch would bring
-inline size_t mm_frag_cap(const mm_ctx* c, size_t nF) { return nF > c->reserveFrags ? nF : c->reserveFrags; }
+inline size_t mm_frag_cap(const mm_ctx* c, size_t nF) { return mm_frag_cap(c->opt, nF); }
 // A scaled count never claims more than an eighth of the device memory that is free when it is asked for (`bytesPer` = bytes the buffer
 // holds per counted item): the scaling is a convenience for the passes behind this one -- a repeat-rich first batch must not turn a pass
 // that fits into an out-of-memory error; a later, larger batch that outgrows the clamped buffer is redone the sized way, as without scaling.
 inline size_t mm_scaled(const mm_ctx* c, size_t count, size_t bytesPer) {
   const size_t nF = c->nFrags ? c->nFrags : 1;
-  if (c->reserveFrags <= nF) return count;
-  size_t scaled = (size_t)((double)count * (double)c->reserveFrags / (double)nF) + 1;
+  if (c->opt.reserveFrags <= nF) return count;
+  size_t scaled = (size_t)((double)count * (double)c->opt.reserveFrags / (double)nF) + 1;
   size_t freeB = 0, totalB = 0;
   if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { (void)hipGetLastError(); return count; }
   const size_t most = freeB / 8 / (bytesPer ? bytesPer : 1);
@@ -366,7 +354,7 @@ int mm_launch_pack_raw(mm_ctx* c, const uint8_t* dAscii, const int64_t* dSrcOff,
                        int64_t nChunks, uint32_t* dB, uint32_t* dM, uint32_t* dHasN);
 int mm_launch_sketch(mm_ctx* c);
 int mm_launch_sketch_global(mm_ctx* c);   // mm_sketch_global.hip: sketches no LDS table holds (sketchSize > MM_LDS_MAX_SKETCH)
-#define MM_LDS_MAX_SKETCH 8190             // beyond: the global-memory sketch kernel and the literal L2 kernels (any size up to MM_MAX_SKETCH)
+// (MM_LDS_MAX_SKETCH, beyond which the global-memory sketch kernel and the literal L2 kernels take over: mm_pass_state.h)
 #define MM_WINNOW_LDS_SKETCH 4096          // the device index build keeps a window's sketch as one sorted array in LDS up to here (k_winnow_tiles: an insert shifts half of it), and as
                                            // blocks of 64 entries in HBM under an LDS directory beyond (k_winnow_tiles<.., GSK>: 0.7 s against 8.7 s of index build at sketchSize 9 998,
                                            // profiles/r14_11; LDS itself would hold 10 000 entries)

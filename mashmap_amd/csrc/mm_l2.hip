@@ -1315,7 +1315,7 @@ static int mm_l2_verdict(mm_ctx* c, const unsigned long long* hc) {
   if (hc[MM_PC_L2_FLAGS] & MM_L2F_STREAM) { c->err = "internal: an L2 stream outgrew the reservation k_l2_extents made for it"; return MM_ERR_CAPACITY; }
   if (hc[MM_PC_L2_FLAGS] & MM_L2F_SLOTS) { c->err = "an L1 candidate with more tied L2 loci than 64 GiB of staging can hold"; return MM_ERR_CAPACITY; }
   if (hc[MM_PC_L2_OVERFLOW]) { c->err = "L2 locus buffer overflow"; return MM_ERR_CAPACITY; }
-  c->nL2 = (size_t)hc[MM_PC_L2_LOCI];
+  c->rep.nL2 = (size_t)hc[MM_PC_L2_LOCI];
   return MM_OK;
 }
 
@@ -1332,8 +1332,7 @@ static L2Retry l2_after_readback(mm_ctx* c, const unsigned long long* hc, int nC
     return L2Retry::MoreSlots;
   }
   if (!over) return L2Retry::Done;
-  const size_t need = mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus));
-  c->l2Cap = need + need / 8 + 1024;
+  c->l2Cap = mm_loci_cap_grown(mm_scaled(c, (size_t)hc[MM_PC_L2_LOCI], sizeof(mm_l2_locus)));
   return L2Retry::MoreLoci;
 }
 
@@ -1366,7 +1365,7 @@ static int l2w_extents(mm_ctx* c, int nC) {
   if ((size_t)totT * 12 + (size_t)totH * 4 > ((size_t)96 << 30)) { c->err = "windowLen != 0: the candidates of this batch need more than 96 GiB of scratch; use smaller batches (MASHMAP_HIP_BATCH_MBP)"; return MM_ERR_CAPACITY; }
   MM_HIP(c, c->dWinHeap.ensure((size_t)totH * 4 + 64)); MM_HIP(c, c->dWinKeys.ensure((size_t)totT * 8 + 64)); MM_HIP(c, c->dWinVals.ensure((size_t)totT * 4 + 64));
   MM_HIP(c, c->dL2Cells.ensure((size_t)nC * (size_t)(c->P.sketchSize + 1) * sizeof(ExactCell) + 64));
-  if (c->l2Cap < c->nL1 * 2 + 1024) c->l2Cap = c->nL1 * 2 + 1024;
+  c->l2Cap = std::max(c->l2Cap, mm_loci_cap0(c->rep.nL1));
   return MM_OK;
 }
 
@@ -1419,7 +1418,7 @@ static void l2w_launch_window(mm_ctx* c, unsigned long long* cnt, int nC, int lo
 
 static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
   const int s = c->P.sketchSize;
-  const int nC = (int)c->nL1;
+  const int nC = (int)c->rep.nL1;
   { const int rc = l2w_extents(c, nC); if (rc != MM_OK) return rc; }
   // MM_OPT_L2_WINDOW_WAVE: k_l2_window_wave takes every candidate first and leaves a list of those it cannot hold; k_l2_window then walks
   // that list, whose length stays on the device (the launch covers every candidate), so the stage waits for the host as often as without
@@ -1427,8 +1426,8 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
   // here as well), is the literal kernel's alone.
   // MM_OPT_L2_LARGE_WAVE, bit 0: a split batch (it is here for its sketch size, or for bit 1 of the option) goes to k_l2_large_wave first, in
   // the same place and with the same hand-over, from the slices k_l2_extents computes; beyond MM_LW_MAX_SKETCH the literal kernel alone.
-  const bool winWave = c->l2WindowWave && c->windowed && s <= MM_WW_MAX_SKETCH && nC > 0;
-  const bool large = (c->l2LargeWave & 1) && !c->windowed && s <= MM_LW_MAX_SKETCH && nC > 0;
+  const bool winWave = c->opt.l2WindowWave && c->windowed && s <= MM_WW_MAX_SKETCH && nC > 0;
+  const bool large = (c->opt.l2LargeWave & 1) && !c->windowed && s <= MM_LW_MAX_SKETCH && nC > 0;
   const bool wave = winWave || large;
   if (wave) MM_HIP(c, c->dL2Wide.ensure((size_t)nC * 4 + 64));
   if (large) {
@@ -1462,12 +1461,13 @@ static int mm_launch_l2_window(mm_ctx* c, unsigned long long* cnt) {
     if (r == L2Retry::MoreLoci) waveDone = false;                          // the locus buffer moves: the wave kernel runs again as well
     if (r == L2Retry::Done || r == L2Retry::GiveUp) break;
   }
-  c->winCands = c->windowed ? (size_t)nC : 0;
-  c->winLit = !c->windowed ? 0 : wave ? (size_t)hc[MM_PC_L2_WIDE_LEN] : (size_t)nC;
-  if (c->env.debug && c->windowed) fprintf(stderr, "[mm] L2: of %d windowed candidates the literal L2 kernel took %zu\n", nC, c->winLit);
-  c->lwCands = c->windowed ? 0 : (size_t)nC;
-  c->lwLit = c->windowed ? 0 : large ? (size_t)hc[MM_PC_L2_LARGE_LEN] : (size_t)nC;
-  if (c->env.debug && !c->windowed) fprintf(stderr, "[mm] L2: of %d candidates of a split batch on the literal route k_l2_window took %zu\n", nC, c->lwLit);
+  SizedPass::Seen& seen = c->sized.seen;
+  seen.winCands = c->windowed ? (size_t)nC : 0;
+  seen.winLit = !c->windowed ? 0 : wave ? (size_t)hc[MM_PC_L2_WIDE_LEN] : (size_t)nC;
+  if (c->env.debug && c->windowed) fprintf(stderr, "[mm] L2: of %d windowed candidates the literal L2 kernel took %zu\n", nC, seen.winLit);
+  seen.lwCands = c->windowed ? 0 : (size_t)nC;
+  seen.lwLit = c->windowed ? 0 : large ? (size_t)hc[MM_PC_L2_LARGE_LEN] : (size_t)nC;
+  if (c->env.debug && !c->windowed) fprintf(stderr, "[mm] L2: of %d candidates of a split batch on the literal route k_l2_window took %zu\n", nC, seen.lwLit);
   return mm_l2_verdict(c, hc);
 }
 
@@ -1515,11 +1515,12 @@ struct L2Pass {
 // stage 1: the candidate-indexed buffers, every candidate's slice of the event stream (k_l2_extents) and the scan of the stream lengths --
 // read back by a sized pass, left on the device (and checked against dL2Ops by k_l2_gate) by a steady-state one
 static int l2_extents(mm_ctx* c, L2Pass& p) {
-  // sized pass: the candidates are counted (c->nL1) and the candidate-indexed buffers get an eighth of head room, which is what a
+  // sized pass: the candidates are counted (rep.nL1) and the candidate-indexed buffers get an eighth of head room, which is what a
   // steady-state pass (count on the device: MM_PC_L1_CAND) launches against
-  if (!p.steady) { const size_t n1 = mm_scaled(c, c->nL1, 96 + 2 * (size_t)((c->P.sketchSize + 3) & ~1)); c->candCap = n1 + n1 / 8 + 1024; }
-  p.nC = p.steady ? (int)c->candCap : (int)c->nL1;
-  p.nCbuf = (int)c->candCap;
+  size_t& candCap = c->sized.steady.candCap;
+  if (!p.steady) candCap = mm_cand_cap(mm_scaled(c, c->rep.nL1, 96 + 2 * (size_t)((c->P.sketchSize + 3) & ~1)));
+  p.nC = p.steady ? (int)candCap : (int)c->rep.nL1;
+  p.nCbuf = (int)candCap;
   p.nDev = p.steady ? p.cnt + MM_PC_L1_CAND : nullptr;
   MM_HIP(c, c->dL2Info.ensure((size_t)p.nCbuf * sizeof(L2Info) + 64));
   MM_HIP(c, c->dL2Cnt.ensure((size_t)p.nCbuf * 4 + 64));
@@ -1536,8 +1537,8 @@ static int l2_extents(mm_ctx* c, L2Pass& p) {
     MM_HIP(c, hipGetLastError());
     return MM_OK;
   }
-  const int rc = mm_scan_i32_to_i64(c, p.nC, c->dL2Cnt.as<int32_t>(), c->dL2Off.as<int64_t>(), &p.totalOps); c->nSyncs++; if (rc != MM_OK) return rc;
-  c->lastOps = (size_t)p.totalOps;
+  const int rc = mm_scan_i32_to_i64(c, p.nC, c->dL2Cnt.as<int32_t>(), c->dL2Off.as<int64_t>(), &p.totalOps); c->rep.nSyncs++; if (rc != MM_OK) return rc;
+  c->rep.lastOps = (size_t)p.totalOps;
   return MM_OK;
 }
 
@@ -1575,10 +1576,10 @@ static int l2_plan(mm_ctx* c, L2Pass& p) {
     const int rc = mm_l2_plan_chunks(nC, totalOps, l2_stream_budget(c), offAt, p.chunks, maxChunkOps); if (rc != MM_OK) return rc;
     if (c->env.debug && p.chunks.size() > 1) fprintf(stderr, "[mm] L2: %lld stream entries of %d candidates in %zu chunks of at most %lld\n", (long long)totalOps, nC, p.chunks.size(), (long long)maxChunkOps);
     const size_t opsFor = p.chunks.size() == 1 ? mm_scaled(c, (size_t)maxChunkOps, 4) : (size_t)maxChunkOps;
-    MM_HIP(c, c->dL2Ops.ensure((opsFor + opsFor / 16) * 4 + 256));   // a sixteenth of head room for the steady-state passes behind this one
-    c->l2Chunks = p.chunks.size();                                                        // a batch that needs several chunks stays with the sized passes
+    MM_HIP(c, c->dL2Ops.ensure(mm_l2_ops_bytes(opsFor)));
+    c->sized.steady.l2Chunks = p.chunks.size();                                                       // a batch that needs several chunks stays with the sized passes
   }
-  if (p.steady && c->dL2Ops.bytes == 0) { c->redoCause = MM_REDO_NO_STREAM_BUFFER; return MM_PASS_REDO; }
+  if (p.steady && c->dL2Ops.bytes == 0) { c->rep.redoCause = MM_REDO_NO_STREAM_BUFFER; return MM_PASS_REDO; }
   p.oneChunk = p.chunks.size() == 1;
   // the pre-load states k_l2_locate leaves for the sweeps: a row of s + 2 cells and four integers per candidate of a chunk
   size_t rows = 0;
@@ -1717,8 +1718,7 @@ static int l2_chunk_sized(mm_ctx* c, L2Pass& p, const L2Chunk& ch) {
 }
 
 int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
-  if (!steady) { c->winCands = 0; c->winLit = 0; c->lwCands = 0; c->lwLit = 0; }   // mm_pass_l2_window, mm_pass_l2_large: as of the last sized pass
-  if (c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH || (c->l2LargeWave & 2)) return mm_launch_l2_window(c, cnt);   // fragments longer than segLength (--noSplit), a sketch no LDS state holds, or bit 1 of MM_OPT_L2_LARGE_WAVE: the literal route
+  if (mm_l2_literal_route(c->opt, c->windowed, c->P.sketchSize)) return mm_launch_l2_window(c, cnt);
   L2Pass p;
   p.steady = steady; p.cnt = cnt; p.geom = mm_l2_geom(c->P.sketchSize);
   int rc = l2_extents(c, p); if (rc != MM_OK) return rc;
@@ -1726,8 +1726,8 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
   if (p.oneChunk) { rc = l2_locate(c, p, p.chunks[0]); if (rc != MM_OK) return rc; }      // its streams stay put over the retries below
   MM_HIP(c, c->dL2Wide.ensure((size_t)p.nCbuf * 4 + 64)); MM_HIP(c, c->dL2Exact.ensure((size_t)p.nCbuf * 4 + 64));
   MM_HIP(c, c->dL2First.ensure((size_t)p.nCbuf * 8 + 64)); MM_HIP(c, c->dL2Num.ensure((size_t)p.nCbuf * 4 + 64));
-  if (c->l2Cap < (size_t)p.nCbuf * 2 + 1024) c->l2Cap = (size_t)p.nCbuf * 2 + 1024;
-  if (steady && c->prevLocap) p.locap = c->prevLocap;
+  c->l2Cap = std::max(c->l2Cap, mm_loci_cap0((size_t)p.nCbuf));
+  if (steady && c->sized.steady.prevLocap) p.locap = c->sized.steady.prevLocap;
   for (int attempt = 0; attempt < 24; attempt++) {
     MM_HIP(c, c->dL2.ensure(c->l2Cap * sizeof(mm_l2_locus) + 64));
     MM_HIP(c, c->dL2Tmp.ensure((size_t)p.nCbuf * p.locap * sizeof(L2Tmp) + 64));
@@ -1746,6 +1746,6 @@ int mm_launch_l2(mm_ctx* c, unsigned long long* cnt, bool steady) {
     if (r == L2Retry::Done || r == L2Retry::GiveUp) break;
   }
   rc = mm_l2_verdict(c, p.hc);
-  if (rc == MM_OK) c->prevLocap = p.locap;
+  if (rc == MM_OK) c->sized.steady.prevLocap = p.locap;
   return rc;
 }

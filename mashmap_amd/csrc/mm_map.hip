@@ -1621,7 +1621,7 @@ k_l1_window(int nList, const int32_t* __restrict__ list, const DFrag* __restrict
 //                    outgrew a buffer has its overflow flag set there and is redone the sized way (MM_PASS_REDO).
 // What the stages of a pass hand on (map_pass calls them in order; each one is a sequence of operations on c->stream).
 struct MapPass {
-  bool steady, windowed, allSlow, useMid;
+  bool steady, windowed, useMid;
   bool useGroups = false;                  // k_lookup_groups runs behind k_lookup_l1 (MM_OPT_L1_GROUP_FUSED under -Y): bigList is what it handed over
   const int32_t* bigList = nullptr;        // the fragments of the HBM point path: dBigList, or dGrpList behind k_lookup_groups
   unsigned long long nOffered = 0;         // sized pass with useGroups: fragments k_lookup_l1 queued (all of them offered to k_lookup_groups)
@@ -1649,18 +1649,18 @@ static int pass_prepare(mm_ctx* c, MapPass& p) {
   // fragments longer than segLength (--noSplit): windowLen != 0 -- every fragment takes the literal path with its points (and their
   // seeds' numbers) in HBM: k_l1_window here, k_l2_window in mm_l2.hip
   p.windowed = c->windowed;
-  p.allSlow = c->keepPoints || p.fl.skipPrefix || p.windowed;
+  const bool pointsInHbm = mm_points_in_hbm(c->opt, p.fl.skipPrefix, p.windowed);
   const size_t cF = mm_frag_cap(c, (size_t)p.nF);
-  if (c->ptsCap == 0) c->ptsCap = p.allSlow ? cF * 128 + 4096 : cF * 8 + 65536;
-  if (c->l1Cap < cF * 2 + 1024) c->l1Cap = cF * 2 + 1024;
+  if (c->ptsCap == 0) c->ptsCap = mm_pts_cap0(cF, pointsInHbm);
+  c->l1Cap = std::max(c->l1Cap, mm_l1_cap0(cF));
   MM_HIP(c, c->dListB.ensure(cF * 4 + 16)); MM_HIP(c, c->dListC.ensure(cF * 4 + 16)); MM_HIP(c, c->dBigList.ensure(cF * 4 + 16));
   // fragments with more interval points than k_lookup_l1 sorts go through k_lookup_mid first
-  p.useMid = !p.allSlow && p.s <= MM_MID_MAXSKETCH;
+  p.useMid = !pointsInHbm && p.s <= MM_MID_MAXSKETCH;
   if (p.useMid) MM_HIP(c, c->dMidList.ensure(cF * 4 + 16));
   // -Y reference groups with MM_OPT_L1_GROUP_FUSED: the queued fragments go through k_lookup_groups first.  Not for a windowed batch, not
   // when the points are to stay in HBM, not for a sketch its seed list does not hold, and only where an extent of the sorted points is
-  // a whole group (refGroup non-decreasing).  Such a pass is never a steady-state one (mm_launch_map: allSlow)
-  p.useGroups = c->l1GroupFused && p.fl.skipPrefix && !p.steady && !p.windowed && !c->keepPoints && p.s <= MM_GRP_MAXSEEDS && c->refGroupMonotone;
+  // a whole group (refGroup non-decreasing).  Such a pass is never a steady-state one (mm_never_steady)
+  p.useGroups = c->opt.l1GroupFused && p.fl.skipPrefix && !p.steady && !p.windowed && !c->opt.keepPoints && p.s <= MM_GRP_MAXSEEDS && c->refGroupMonotone;
   if (p.useGroups) MM_HIP(c, c->dGrpList.ensure(cF * 4 + 16));
   p.bigList = p.useGroups ? c->dGrpList.as<int32_t>() : c->dBigList.as<int32_t>();
   MM_HIP(c, c->dL1Regions.ensure(sizeof(L1Regions)));
@@ -1679,11 +1679,11 @@ static int pass_lookup(mm_ctx* c, MapPass& p) {
   unsigned long long* const cnt = p.cnt;
   unsigned long long* const all = c->dCounters.as<unsigned long long>();
   for (int attempt = 0; attempt < 10; attempt++) {          // grow-and-retry on capacity overflow (points or L1 candidates)
-    p.regionCap = (c->l1Cap + MM_L1_REGIONS - 1) / MM_L1_REGIONS + 64;
+    p.regionCap = mm_region_cap(c->l1Cap, MM_L1_REGIONS);
     MM_HIP(c, c->dPts.ensure(c->ptsCap * 8 + 64));
     MM_HIP(c, c->dPtIds.ensure(p.windowed ? c->ptsCap * 2 + 64 : 64));
-    MM_HIP(c, c->dL1.ensure(p.regionCap * MM_L1_REGIONS * sizeof(mm_l1_candidate) + 64));
-    MM_HIP(c, c->dL1b.ensure(p.regionCap * MM_L1_REGIONS * sizeof(mm_l1_candidate) + 64));
+    MM_HIP(c, c->dL1.ensure(mm_l1_bytes(p.regionCap, MM_L1_REGIONS, sizeof(mm_l1_candidate))));
+    MM_HIP(c, c->dL1b.ensure(mm_l1_bytes(p.regionCap, MM_L1_REGIONS, sizeof(mm_l1_candidate))));
     MM_HIP(c, c->dL1Cursors.ensure(sizeof p.hcur));
     // the sketch launcher's hard-list length (32 bits of its first word) survives the reset below
     if (attempt == 0) MM_HIP(c, hipMemcpyAsync(all + MM_CW_HARD_COPY, all + MM_CW_SKETCH, 8, hipMemcpyDeviceToDevice, c->stream));
@@ -1699,7 +1699,7 @@ static int pass_lookup(mm_ctx* c, MapPass& p) {
                            : (fuse == 512 ? k_lookup_l1<512, false> : fuse == 256 ? k_lookup_l1<256, false> : k_lookup_l1<128, false>);
       hipLaunchKernelGGL(kern, dim3((nF + MM_LOOKUP_WPB - 1) / MM_LOOKUP_WPB), dim3(MM_LOOKUP_WPB * 64), 0, c->stream, nF, s, c->dFrags.as<DFrag>(),
                          c->dSkHash.as<uint64_t>(), c->dSkStrand.as<int8_t>(), c->dSkCount.as<uint32_t>(), p.seedTab, I.ptKeys.as<uint64_t>(),
-                         c->dReadSelf.as<int32_t>(), c->seqCounterBase, p.fl, p.windowed ? 2 : (c->keepPoints ? 1 : 0),
+                         c->dReadSelf.as<int32_t>(), c->seqCounterBase, p.fl, p.windowed ? 2 : (c->opt.keepPoints ? 1 : 0),
                          c->dQHash.as<uint64_t>(), c->dQStrand.as<int8_t>(),
                          c->dStats.as<mm_frag_stats>(), c->dPtOff.as<int64_t>(), (unsigned long long)c->ptsCap,
                          c->dMinHits.as<int32_t>(), c->dCutoffs.as<int32_t>(), (int)c->nCutoffs, c->P.segLength,
@@ -1711,8 +1711,7 @@ static int pass_lookup(mm_ctx* c, MapPass& p) {
       // its list's length stays on the device (MM_PC_MID_LEN); the grid is what the last sized pass saw plus a half (the kernel walks the
       // list with whatever grid it gets), every fragment when nothing is known yet
       KernelTimer t(c, MM_K_SORT);
-      const size_t guess = c->midKnown ? c->prevMid + c->prevMid / 2 + 256 : (size_t)nF;
-      const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(guess, (size_t)nF));
+      const unsigned grid = (unsigned)mm_mid_grid_guess(c->sized.seen, (size_t)nF);
       auto mk = I.tagged ? k_lookup_mid<true> : k_lookup_mid<false>;
       hipLaunchKernelGGL(mk, dim3(grid), dim3(64), 0, c->stream, 0, cnt + MM_PC_MID_LEN, c->dMidList.as<int32_t>(), s, c->dFrags.as<DFrag>(), c->dSkHash.as<uint64_t>(),
                          c->dSkCount.as<uint32_t>(), p.seedTab, I.ptKeys.as<uint64_t>(), c->dReadSelf.as<int32_t>(), c->seqCounterBase, p.fl, c->dStats.as<mm_frag_stats>(),
@@ -1739,13 +1738,12 @@ static int pass_lookup(mm_ctx* c, MapPass& p) {
     MM_HIP(c, hipMemcpyAsync(p.hcur, c->dL1Cursors.p, sizeof p.hcur, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_HARD_COPY, all + MM_CW_HARD_COPY, 8, hipMemcpyDeviceToHost, c->stream));
     MM_SYNC(c);
-    c->lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
-    if (p.hc[MM_PC_POINT_OVERFLOW]) { const size_t need = mm_scaled(c, (size_t)p.hc[MM_PC_POINT_CURSOR], 16); c->ptsCap = need + need / 8 + 4096; continue; }
+    c->rep.lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
+    if (p.hc[MM_PC_POINT_OVERFLOW]) { c->ptsCap = mm_pts_cap_grown(mm_scaled(c, (size_t)p.hc[MM_PC_POINT_CURSOR], 16)); continue; }
     if (p.hc[MM_PC_L1_OVERFLOW]) {                            // some region overflowed: size for the largest one seen
       unsigned long long mx = 0;
       for (int r = 0; r < MM_L1_REGIONS; r++) mx = std::max(mx, p.hcur[(size_t)r * MM_L1_CURSOR_STRIDE]);
-      mx = (unsigned long long)mm_scaled(c, (size_t)mx, sizeof(mm_l1_candidate) * MM_L1_REGIONS);
-      c->l1Cap = (size_t)(mx + mx / 4 + 256) * MM_L1_REGIONS; continue;
+      c->l1Cap = mm_l1_cap_grown(mm_scaled(c, (size_t)mx, sizeof(mm_l1_candidate) * MM_L1_REGIONS), MM_L1_REGIONS); continue;
     }
     break;
   }
@@ -1788,7 +1786,7 @@ static int pass_point_path(mm_ctx* c, MapPass& p) {
   const int nBig = p.nBig, s = p.s;
   // grids over the queued fragments: exact when their number is known, otherwise sized by what the previous pass saw (the kernels
   // walk the list with whatever grid they get)
-  const int nB = p.steady ? (int)std::min<size_t>(c->prevBig + c->prevBig / 2 + 1024, (size_t)p.nF) : nBig;
+  const int nB = p.steady ? (int)mm_big_grid_guess(c->sized.seen, (size_t)p.nF) : nBig;
   p.gWave = (unsigned)((nB + 3) / 4); p.gThread = (unsigned)((nB + 255) / 256);
   KernelTimer t(c, MM_K_SORT);
   uint16_t* sortIds = p.windowed ? c->dPtIds.as<uint16_t>() : (uint16_t*)nullptr;
@@ -1799,7 +1797,7 @@ static int pass_point_path(mm_ctx* c, MapPass& p) {
                      c->dPts.as<uint64_t>(), sortIds, c->dPtKept.as<int32_t>(), p.nBigDev);
   MM_HIP(c, hipGetLastError());
   // split mode, plain L1: the points that cannot reach minimumHits go before the sort (k_filter_points)
-  if (!p.windowed && (!c->keepPoints || c->keepFiltered) && !p.fl.skipPrefix) {
+  if (!p.windowed && (!c->opt.keepPoints || c->opt.keepFiltered) && !p.fl.skipPrefix) {
     hipLaunchKernelGGL(k_filter_points, dim3(p.gWave), dim3(256), 0, c->stream, nBig, p.bigList, c->dStats.as<mm_frag_stats>(), c->dMinHits.as<int32_t>(),
                        c->dPtOff.as<int64_t>(), c->dPts.as<uint64_t>(), c->dPtKept.as<int32_t>(), p.nBigDev);
     MM_HIP(c, hipGetLastError());
@@ -1830,7 +1828,7 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
   // a wave per fragment streams the sorted points; what it cannot take (a position group across two contigs, minimumHits 0) and
   // every fragment under -Y reference groups goes to the literal one-thread-per-fragment kernel -- unless MM_OPT_L1_GROUP_STREAM: then
   // the grouped form of the wave kernel comes first there too
-  const bool stream = (!p.fl.skipPrefix || c->l1GroupStream) && !c->env.l1Literal && !p.windowed;
+  const bool stream = (!p.fl.skipPrefix || c->opt.l1GroupStream) && !c->env.l1Literal && !p.windowed;
   for (int attempt = 0; attempt < 8; attempt++) {
     if (!p.steady) {
       MM_HIP(c, hipMemcpyAsync(cnt + MM_PC_L1_CAND, &fusedL1, 8, hipMemcpyHostToDevice, c->stream));
@@ -1880,7 +1878,7 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
     if (c->env.debug && stream && p.fl.skipPrefix) fprintf(stderr, "[mm] point path: of %d queued fragments the literal L1 kernel took %llu (reference groups on the wave kernel)\n", nBig, p.nLit);
     if (!p.hc[MM_PC_L1_OVERFLOW]) return MM_OK;
     // grow, keeping the fused candidates already in the buffer
-    const size_t newCap = (size_t)p.hc[MM_PC_L1_CAND] + (size_t)p.hc[MM_PC_L1_CAND] / 8 + 1024;
+    const size_t newCap = mm_cand_cap((size_t)p.hc[MM_PC_L1_CAND]);
     DevBuf nb; MM_HIP(c, nb.ensure(newCap * sizeof(mm_l1_candidate) + 64));
     if (fusedL1) MM_HIP(c, hipMemcpyAsync(nb.p, c->dL1.p, (size_t)fusedL1 * sizeof(mm_l1_candidate), hipMemcpyDeviceToDevice, c->stream));
     MM_SYNC(c);
@@ -1895,7 +1893,7 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
 static int pass_finish(mm_ctx* c, MapPass& p) {
   if (p.steady) {
     // candidates the buffers of this pass hold: what the previous (sized) pass left of candidate-indexed staging, and the dense L1 buffer itself
-    const unsigned long long cap = (unsigned long long)std::min(c->candCap, p.denseCap);
+    const unsigned long long cap = (unsigned long long)std::min(c->sized.steady.candCap, p.denseCap);
     hipLaunchKernelGGL(k_l1_gate, dim3(1), dim3(1), 0, c->stream, p.cnt, cap);
     MM_HIP(c, hipGetLastError());
   }
@@ -1910,10 +1908,11 @@ static int pass_finish(mm_ctx* c, MapPass& p) {
   MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_HARD_COPY, all + MM_CW_HARD_COPY, 8, hipMemcpyDeviceToHost, c->stream));
   MM_SYNC(c);
   const unsigned long long* h = c->hPass + MM_CW_PASS; const unsigned long long* hm = c->hPass + MM_CW_MAP;
-  c->lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
-  if (mm_pass_incomplete(h) || hm[MM_MC_OVERFLOW]) { c->redoCause = mm_redo_cause(h, hm); return MM_PASS_REDO; }   // some buffer was too small for this batch: the sized pass grows it
-  c->nL1 = (size_t)h[MM_PC_L1_CAND]; c->nL2 = (size_t)h[MM_PC_L2_LOCI]; c->nMappings = c->haveReplayTables ? (size_t)hm[MM_MC_MAPPINGS] : 0;
-  c->lastOps = (size_t)hm[MM_MC_L2_OPS]; c->lastBig = c->prevBig;         // (MM_PC_BIG_LEN holds MM_PC_L2_WIDE_LEN by now: the sized pass's figure stands in)
+  PassReport& r = c->rep;
+  r.lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
+  if (mm_pass_incomplete(h) || hm[MM_MC_OVERFLOW]) { r.redoCause = mm_redo_cause(h, hm); return MM_PASS_REDO; }   // some buffer was too small for this batch: the sized pass grows it
+  r.nL1 = (size_t)h[MM_PC_L1_CAND]; r.nL2 = (size_t)h[MM_PC_L2_LOCI]; r.nMappings = c->haveReplayTables ? (size_t)hm[MM_MC_MAPPINGS] : 0;
+  r.lastOps = (size_t)hm[MM_MC_L2_OPS]; r.lastBig = c->sized.seen.prevBig;        // (MM_PC_BIG_LEN holds MM_PC_L2_WIDE_LEN by now: the sized pass's figure stands in)
   return MM_OK;
 }
 
@@ -1928,13 +1927,13 @@ static int map_pass(mm_ctx* c, const bool steady) {
   }
   if (rc != MM_OK) return rc;
   if (!steady) {
-    c->nL1 = (size_t)p.hc[MM_PC_L1_CAND];
-    c->prevBig = c->lastBig = (size_t)p.nBig; c->prevLit = (size_t)p.nLit;
-    c->prevMid = c->lastMid = (size_t)p.hMid; c->midKnown = p.useMid;
-    c->grpOffered = (size_t)p.nOffered; c->grpFused = p.useGroups ? (size_t)p.nOffered - (size_t)p.nBig : 0;
-    c->winCands = 0; c->winLit = 0;                        // (mm_launch_l2 counts the windowed candidates of a sized pass)
-    c->lwCands = 0; c->lwLit = 0;
-    if (c->nL1 == 0) { c->nL2 = 0; return MM_OK; }
+    c->rep.nL1 = (size_t)p.hc[MM_PC_L1_CAND]; c->rep.lastBig = (size_t)p.nBig; c->rep.lastMid = (size_t)p.hMid;
+    // as of this sized pass; the four L2 figures are zero until mm_launch_l2_window counts its candidates
+    SizedPass::Seen seen;
+    seen.prevBig = (size_t)p.nBig; seen.prevLit = (size_t)p.nLit; seen.prevMid = (size_t)p.hMid; seen.midKnown = p.useMid;
+    seen.grpOffered = (size_t)p.nOffered; seen.grpFused = p.useGroups ? (size_t)p.nOffered - (size_t)p.nBig : 0;
+    c->sized.seen = seen;
+    if (c->rep.nL1 == 0) return MM_OK;
   }
   return pass_finish(c, p);
 }
@@ -1947,19 +1946,17 @@ int mm_launch_map(mm_ctx* c) {
   MM_HIP(c, c->dPtOff.ensure(cF * 16 + 64)); MM_HIP(c, c->dL1Off.ensure(cF * 8 + 64)); MM_HIP(c, c->dPtKept.ensure(cF * 4 + 64));
   MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
   if (!c->hPass) { MM_HIP(c, hipHostMalloc((void**)&c->hPass, MM_COUNTER_BYTES, hipHostMallocDefault)); }
-  c->nL1 = c->nL2 = 0; c->nMappings = 0; c->nSyncs = 0; c->lastSteady = false; c->redoCause = 0;
+  c->rep = PassReport{};
   if (nF == 0) return MM_OK;
-  const bool allSlow = c->keepPoints || (c->P.flags & MM_FLAG_SKIP_PREFIX) || c->windowed || c->P.sketchSize > MM_LDS_MAX_SKETCH || (c->l2LargeWave & 2);
-  // (a batch with a tenth more fragments than the one the buffers were sized for would only fail and be redone: it is sized right away)
-  if (c->steadyOk && c->steadyFails < 3 && !allSlow && (size_t)nF <= c->sizedFrags + c->sizedFrags / 10) {
+  const bool neverSteady = mm_never_steady(c->opt, (c->P.flags & MM_FLAG_SKIP_PREFIX) != 0, c->windowed, s);
+  if (mm_may_try_steady(c->sized.steady, (size_t)nF, neverSteady)) {
     const int rc = map_pass(c, true);
-    if (rc == MM_OK) { c->lastSteady = true; c->steadyFails = 0; return MM_OK; }
+    if (rc == MM_OK) { mm_steady_stood(c->sized.steady, c->rep); return MM_OK; }
     if (rc != MM_PASS_REDO) return rc;
-    c->steadyOk = false; c->steadyFails++; c->nRedone++;                        // three redone passes in a row: this context's batches keep outgrowing what the one before left
+    mm_steady_redone(c->sized.steady, c->tot);
   }
   const int rc = map_pass(c, false);
-  c->sizedFrags = mm_frag_cap(c, (size_t)nF);
-  c->steadyOk = rc == MM_OK && !allSlow && c->nL1 > 0 && c->l2Chunks == 1;   // (a batch whose L2 streams go through in chunks needs the host between them)
+  mm_sized_pass_done(c->sized.steady, mm_frag_cap(c, (size_t)nF), rc == MM_OK, neverSteady, c->rep.nL1);
   return rc;
 }
 
@@ -1978,9 +1975,10 @@ int mm_results_download(mm_ctx* c, mm_frag_stats* stats, mm_l1_candidate* l1, mm
     MM_HIP(c, hipMemcpyAsync(st.data(), c->dStats.p, nF * sizeof(mm_frag_stats), hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipMemcpyAsync(l1off.data(), c->dL1Off.p, nF * 8, hipMemcpyDeviceToHost, c->stream));
   }
-  std::vector<mm_l1_candidate> h1(c->nL1); std::vector<mm_l2_locus> h2(c->nL2);
-  if (c->nL1) MM_HIP(c, hipMemcpyAsync(h1.data(), c->dL1.p, c->nL1 * sizeof(mm_l1_candidate), hipMemcpyDeviceToHost, c->stream));
-  if (c->nL2) MM_HIP(c, hipMemcpyAsync(h2.data(), c->dL2.p, c->nL2 * sizeof(mm_l2_locus), hipMemcpyDeviceToHost, c->stream));
+  const size_t nL1 = c->rep.nL1, nL2 = c->rep.nL2;
+  std::vector<mm_l1_candidate> h1(nL1); std::vector<mm_l2_locus> h2(nL2);
+  if (nL1) MM_HIP(c, hipMemcpyAsync(h1.data(), c->dL1.p, nL1 * sizeof(mm_l1_candidate), hipMemcpyDeviceToHost, c->stream));
+  if (nL2) MM_HIP(c, hipMemcpyAsync(h2.data(), c->dL2.p, nL2 * sizeof(mm_l2_locus), hipMemcpyDeviceToHost, c->stream));
   MM_HIP(c, hipStreamSynchronize(c->stream));
   if (stats && nF) std::memcpy(stats, st.data(), nF * sizeof(mm_frag_stats));
   // fragment-major order: candidates of fragment f are contiguous on the device at l1off[f]
@@ -1990,14 +1988,14 @@ int mm_results_download(mm_ctx* c, mm_frag_stats* stats, mm_l1_candidate* l1, mm
     newBase[f] = (int64_t)w;
     for (int i = 0; i < st[f].nL1; i++) { if (l1) l1[w] = h1[(size_t)l1off[f] + i]; w++; }
   }
-  if (l2 && c->nL2) {
+  if (l2 && nL2) {
     // device order keeps every candidate's loci contiguous and in emission order; a stable sort by (frag, cand) finishes the job
-    std::vector<uint32_t> ord(c->nL2);
+    std::vector<uint32_t> ord(nL2);
     std::iota(ord.begin(), ord.end(), 0u);
     std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
       if (h2[a].frag != h2[b].frag) return h2[a].frag < h2[b].frag;
       return h2[a].cand < h2[b].cand; });
-    for (size_t i = 0; i < c->nL2; i++) { mm_l2_locus o = h2[ord[i]]; o.cand = (int32_t)(newBase[o.frag] + o.cand); l2[i] = o; }
+    for (size_t i = 0; i < nL2; i++) { mm_l2_locus o = h2[ord[i]]; o.cand = (int32_t)(newBase[o.frag] + o.cand); l2[i] = o; }
   }
   return MM_OK;
 }
@@ -2028,14 +2026,14 @@ int mm_query_sketch_download(mm_ctx* c, mm_minmer* out) {
 
 int mm_points_download(mm_ctx* c, size_t frag, mm_interval_point* out, size_t cap, size_t* n) {
   if (!c->mapped || frag >= c->nFrags) { c->err = "mm_points_download: bad state / fragment"; return MM_ERR_STATE; }
-  if (!c->keepPoints && !(c->P.flags & MM_FLAG_SKIP_PREFIX)) { c->err = "mm_points_download: interval points are not kept in HBM (mm_set_option MM_OPT_KEEP_POINTS)"; return MM_ERR_STATE; }
-  if (!c->keepPoints && c->l1GroupFused) { c->err = "mm_points_download: with MM_OPT_L1_GROUP_FUSED the interval points of a fused fragment never reach HBM (mm_set_option MM_OPT_KEEP_POINTS keeps them)"; return MM_ERR_STATE; }
+  if (!c->opt.keepPoints && !(c->P.flags & MM_FLAG_SKIP_PREFIX)) { c->err = "mm_points_download: interval points are not kept in HBM (mm_set_option MM_OPT_KEEP_POINTS)"; return MM_ERR_STATE; }
+  if (!c->opt.keepPoints && c->opt.l1GroupFused) { c->err = "mm_points_download: with MM_OPT_L1_GROUP_FUSED the interval points of a fused fragment never reach HBM (mm_set_option MM_OPT_KEEP_POINTS keeps them)"; return MM_ERR_STATE; }
   MM_HIP(c, hipSetDevice(c->device));
   int64_t po[2]; mm_frag_stats fs;
   MM_HIP(c, hipMemcpy(po, c->dPtOff.as<int64_t>() + 2 * frag, 16, hipMemcpyDeviceToHost));
   MM_HIP(c, hipMemcpy(&fs, c->dStats.as<mm_frag_stats>() + frag, sizeof fs, hipMemcpyDeviceToHost));
   size_t np = (size_t)fs.nPoints;
-  if (c->keepFiltered) {                                            // the head of the sorted list k_filter_points left (dropped points sort behind it)
+  if (c->opt.keepFiltered) {                                            // the head of the sorted list k_filter_points left (dropped points sort behind it)
     int32_t kept = 0;
     MM_HIP(c, hipMemcpy(&kept, c->dPtKept.as<int32_t>() + frag, 4, hipMemcpyDeviceToHost));
     if (po[1] > 0) np = (size_t)kept;

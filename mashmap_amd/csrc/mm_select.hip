@@ -66,12 +66,11 @@ k_l2_select(SelectArgs A, int32_t* __restrict__ counts, const int64_t* __restric
 int mm_scan_i32_to_i64(mm_ctx* c, int64_t n, const int32_t* dIn, int64_t* dOut, int64_t* total);   // mm_l2.hip
 
 int mm_launch_select(mm_ctx* c, bool steady) {
-  c->nMappings = 0;
   const int nF = (int)c->nFrags;
-  if (!c->haveReplayTables || nF == 0 || (!steady && c->nL1 == 0)) return MM_OK;
+  if (!c->haveReplayTables || nF == 0 || (!steady && c->rep.nL1 == 0)) return MM_OK;
   const size_t cF = mm_frag_cap(c, (size_t)nF);
   MM_HIP(c, c->dSelCnt.ensure(cF * 4 + 64)); MM_HIP(c, c->dSelOff.ensure(cF * 8 + 64));
-  MM_HIP(c, c->dSelHeap.ensure((steady ? c->candCap : std::max(c->nL1, c->candCap)) * 4 + 64));
+  MM_HIP(c, c->dSelHeap.ensure((steady ? c->sized.steady.candCap : std::max(c->rep.nL1, c->sized.steady.candCap)) * 4 + 64));
   MM_HIP(c, c->dFragTab.ensure(cF * sizeof(mm_fragment) + 64));
   if (c->fragTabStale) {
     MM_HIP(c, hipMemcpyAsync(c->dFragTab.p, c->hFrags.data(), (size_t)nF * sizeof(mm_fragment), hipMemcpyHostToDevice, c->stream));
@@ -103,15 +102,15 @@ int mm_launch_select(mm_ctx* c, bool steady) {
   }
   int64_t total = 0;
   const int rc = mm_scan_i32_to_i64(c, nF, c->dSelCnt.as<int32_t>(), c->dSelOff.as<int64_t>(), &total);
-  c->nSyncs++;
+  c->rep.nSyncs++;
   if (rc != MM_OK) return rc;
-  { const size_t tot = mm_scaled(c, (size_t)total, sizeof(mm_mapping)); MM_HIP(c, c->dMappings.ensure((tot + tot / 16) * sizeof(mm_mapping) + 4096)); }   // head room for the steady-state passes behind this one
+  MM_HIP(c, c->dMappings.ensure(mm_mappings_bytes(mm_scaled(c, (size_t)total, sizeof(mm_mapping)), sizeof(mm_mapping))));
   if (total) {
     hipLaunchKernelGGL((k_l2_select<true>), dim3((nF + 255) / 256), dim3(256), 0, c->stream, A, (int32_t*)nullptr, c->dSelOff.as<int64_t>(), c->dMappings.as<mm_mapping>(),
                        (const int64_t*)nullptr, 0ll, (unsigned long long*)nullptr, (const unsigned long long*)nullptr);
     MM_HIP(c, hipGetLastError());
   }
-  c->nMappings = (size_t)total;
+  c->rep.nMappings = (size_t)total;
   return MM_OK;
 }
 
@@ -130,17 +129,17 @@ int mm_set_replay_tables(mm_ctx* c, const uint8_t* accept, const int16_t* minIsz
 
 int mm_mappings_count(const mm_ctx* c, size_t* n) {
   if (!c->mapped || !c->haveReplayTables) return MM_ERR_STATE;
-  if (n) *n = c->nMappings;
+  if (n) *n = c->rep.nMappings;
   return MM_OK;
 }
 
 int mm_mappings_download(mm_ctx* c, mm_mapping* out, size_t cap, size_t* n) {
   if (!c->mapped || !c->haveReplayTables) { c->err = "mm_mappings_download: nothing mapped, or mm_set_replay_tables / mm_set_tables_default was not called"; return MM_ERR_STATE; }
-  if (n) *n = c->nMappings;
-  if (c->nMappings > cap) { c->err = "mm_mappings_download: destination too small"; return MM_ERR_ARG; }
+  if (n) *n = c->rep.nMappings;
+  if (c->rep.nMappings > cap) { c->err = "mm_mappings_download: destination too small"; return MM_ERR_ARG; }
   MM_HIP(c, hipSetDevice(c->device));
-  if (c->nMappings) {
-    MM_HIP(c, hipMemcpyAsync(out, c->dMappings.p, c->nMappings * sizeof(mm_mapping), hipMemcpyDeviceToHost, c->stream));
+  if (c->rep.nMappings) {
+    MM_HIP(c, hipMemcpyAsync(out, c->dMappings.p, c->rep.nMappings * sizeof(mm_mapping), hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipStreamSynchronize(c->stream));
   }
   return MM_OK;
@@ -149,7 +148,7 @@ int mm_mappings_download(mm_ctx* c, mm_mapping* out, size_t cap, size_t* n) {
 int mm_mappings_device(const mm_ctx* c, const mm_mapping** dMappings, size_t* n) {
   if (!c->mapped || !c->haveReplayTables) return MM_ERR_STATE;
   if (dMappings) *dMappings = c->dMappings.as<mm_mapping>();
-  if (n) *n = c->nMappings;
+  if (n) *n = c->rep.nMappings;
   return MM_OK;
 }
 

@@ -205,7 +205,7 @@ int main() {
   // at exit: the counter is back at zero and every pointer the fake handed out came back exactly once
   CHECK(g_mmDeviceBytes.load() == 0, "counter at exit %zu", g_mmDeviceBytes.load());
   CHECK(live.empty() && liveBytes == 0 && nAlloc == nFree && nStrayFree == 0, "at exit: %zu blocks outstanding, %zu allocations, %zu frees, %zu stray frees", live.size(), nAlloc, nFree, nStrayFree);
-  CHECK(g_mmAllocSeconds >= 0.0, "time inside ensure");
+  CHECK(g_mmAllocNanos.load() > 0, "time inside ensure: %llu ns over %zu allocations", (unsigned long long)g_mmAllocNanos.load(), nAlloc);
   printf("cases %d\nmismatches %d\nallocations %zu frees %zu\n", cases, failures, nAlloc, nFree);
   return failures ? 1 : 0;
 }

@@ -211,7 +211,7 @@ def test_candidates_outgrow_the_buffer_inside_the_grouped_wave_kernel(oracle):
     queued) and none from the literal one, against the dense buffer a pass over 120 fragments starts with (tests/mmutil.py: dense_cap):
     the kernel's first launch raises MM_PC_L1_OVERFLOW and the sweep is launched again -- the pass closes more MM_K_L1 timer brackets than a
     second pass of the same batch on the same context, which finds the grown buffer.
-    FINDING: there is no MM_REDO_L1 to expect.  mm_launch_map makes no steady attempt under MM_FLAG_SKIP_PREFIX (allSlow), so the batch is
+    FINDING: there is no MM_REDO_L1 to expect.  mm_launch_map makes no steady attempt under MM_FLAG_SKIP_PREFIX (mm_never_steady), so the batch is
     a sized pass, and a sized pass absorbs the flag itself: pass_l1_sweeps grows the buffer to the cursor's demand, rewinds the cursor
     and launches the kernel again.  Pinned: no attempt, nothing redone, cause 0 -- and the bytes of a fresh context with the option and
     of one without it (the literal kernel)."""
