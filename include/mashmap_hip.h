@@ -329,6 +329,13 @@ int mm_pass_l2_window(const mm_ctx* ctx, uint64_t* candidates, uint64_t* literal
  * longer than segLength or one that took the fast kernels.  Read back with the words the stage reads anyway: no host wait more.  Either
  * pointer may be NULL.  Purely additive: MM_ABI_VERSION stays 2. */
 int mm_pass_l2_large(const mm_ctx* ctx, uint64_t* candidates, uint64_t* literal);
+/* MM_OPT_SKETCH_LARGE, as of the context's last sketch launch (mm_sketch_fragments, or the one inside mm_map_fragments): *fragments =
+ * fragments k_sketch_large sketched -- 0 without the option or at sketchSize <= 8190 --, *uncut = those of them whose final sort ran
+ * without a cut: a fragment with no more k-mer positions than the s + 5 sqrt(s) + 64 hashes the cut aims for, or one with fewer than s
+ * distinct hashes below the cut, which the kernel does again without one.  The kernel's two counts are copied to the host right behind
+ * it; this call waits for that copy if it is still in flight, mm_map_fragments never does.  Either pointer may be NULL.  MM_ERR_STATE
+ * before the context's first sketch launch.  Purely additive: MM_ABI_VERSION stays 2. */
+int mm_sketch_large_counts(mm_ctx* ctx, uint64_t* fragments, uint64_t* uncut);
 /* MM_OPT_L1_GROUP_FUSED, as of the context's last SIZED pass: *offered = fragments the lookup kernel queued under MM_FLAG_SKIP_PREFIX (every
  * fragment with an interval point), *fused = those of them k_lookup_groups finished without the HBM point path; the rest it handed over
  * to that path (mm_pass_l1_literal's *queued).  0 / 0 when the kernel was not launched: the option off, no MM_FLAG_SKIP_PREFIX, sketchSize
@@ -458,8 +465,13 @@ int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
  * read order among the others'.  Reads above 512 records are handed over as before -- the single hand-over cause left.  Rows of every
  * other read, the refusals and the one host wait of the stage are unchanged; mm_chain_long_counts reports what the kernel took.  Purely
  * additive: MM_ABI_VERSION stays 2.
+ * MM_OPT_SKETCH_LARGE (default 0): with 1, mm_sketch_fragments / mm_map_fragments of a context with sketchSize above 8190 sketch on
+ * k_sketch_large instead of the global-memory sketch kernel: one workgroup per fragment, the hashes from the strip hashers of the LDS
+ * sketch kernels, the survivors of the same cut sorted in LDS tiles of 4096 entries with sweeps through HBM only between tiles, the same
+ * emission.  Same sketch bytes; mm_sketch_large_counts reports what the kernel took.  At sketchSize <= 8190 the option does nothing.
+ * Purely additive: MM_ABI_VERSION stays 2.
  */
-enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6, MM_OPT_L2_LARGE_WAVE = 7, MM_OPT_CHAIN_LONG = 8 };
+enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6, MM_OPT_L2_LARGE_WAVE = 7, MM_OPT_CHAIN_LONG = 8, MM_OPT_SKETCH_LARGE = 9 };
 int mm_set_option(mm_ctx* ctx, int option, int value);
 /* sorted interval points of fragment f after the seqId filters of computeMap.hpp:891-896 (needs MM_OPT_KEEP_POINTS; (seqId,pos,side) only, hash = 0).
  * Under MM_FLAG_SKIP_PREFIX the points are in HBM without that option too -- unless MM_OPT_L1_GROUP_FUSED is set: then MM_ERR_STATE. */

@@ -17,6 +17,7 @@ MM_OPT_KEEP_POINTS, MM_OPT_KEEP_FULL_INDEX, MM_OPT_RESERVE_FRAGMENTS, MM_OPT_L1_
 MM_OPT_L1_GROUP_FUSED = 6
 MM_OPT_L2_LARGE_WAVE = 7
 MM_OPT_CHAIN_LONG = 8
+MM_OPT_SKETCH_LARGE = 9
 # bits of Context.pass_redo_cause() (include/mashmap_hip.h: MM_REDO_*)
 (MM_REDO_POINTS, MM_REDO_L1, MM_REDO_L2_LOCI, MM_REDO_L2_SLOTS, MM_REDO_L2_STREAM, MM_REDO_L2_OPS, MM_REDO_L2_LIST, MM_REDO_L2_CANDS,
  MM_REDO_MAPPINGS, MM_REDO_NO_STREAM_BUFFER) = (1 << i for i in range(10))
@@ -155,6 +156,7 @@ def load():
         "mm_pass_l1_group_fused": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_l2_window": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_l2_large": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_sketch_large_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_reads_exchange": (C.c_int, [vp, C.c_int]),
         "mm_reads_upload_packed_parts": (C.c_int, [vp, vp, sz, C.c_int32]),
         "mm_reads_prefetch_packed_append": (C.c_int, [vp, vp, vp, sz, sz, C.POINTER(C.c_int)]),
@@ -197,7 +199,8 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
            "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
            "mm_stat_identity_table", "mm_set_chain_tables", "mm_chain_reads", "mm_chain_counts", "mm_chain_download",
-           "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts", "mm_device_bytes"]
+           "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts", "mm_device_bytes",
+           "mm_sketch_large_counts"]
 
 
 def device_bytes():
@@ -542,6 +545,18 @@ class Context:
         n, l = C.c_uint64(), C.c_uint64()
         self._ck(self.lib.mm_pass_l2_large(self.h, C.byref(n), C.byref(l)), "mm_pass_l2_large")
         return int(n.value), int(l.value)
+
+    def sketch_large(self, on=True):
+        """MM_OPT_SKETCH_LARGE: a context with sketchSize above 8190 sketches on k_sketch_large (strip hashers, the sort in LDS tiles) instead
+        of the global-memory sketch kernel; same bytes.  Does nothing at smaller sketch sizes"""
+        self._ck(self.lib.mm_set_option(self.h, MM_OPT_SKETCH_LARGE, 1 if on else 0), "mm_set_option")
+
+    def sketch_large_counts(self):
+        """(fragments, uncut) of the last sketch launch (sketch(), or the one inside map()): fragments k_sketch_large sketched -- 0 without
+        sketch_large() or at sketchSize <= 8190 -- and those of them whose final sort ran without a cut"""
+        n, u = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.mm_sketch_large_counts(self.h, C.byref(n), C.byref(u)), "mm_sketch_large_counts")
+        return int(n.value), int(u.value)
 
     def l1_group_fused(self, on=True):
         """MM_OPT_L1_GROUP_FUSED: under MM_FLAG_SKIP_PREFIX the queued fragments go through the wave-per-fragment k_lookup_groups first (a

@@ -78,6 +78,8 @@ void mm_destroy(mm_ctx* c) {
   if (c->copyStream) { (void)hipStreamSynchronize(c->copyStream); (void)hipStreamDestroy(c->copyStream); }
   if (c->copyDone) (void)hipEventDestroy(c->copyDone);
   if (c->hPass) (void)hipHostFree(c->hPass);
+  if (c->hSkLarge) (void)hipHostFree(c->hSkLarge);
+  if (c->skLargeDone) (void)hipEventDestroy(c->skLargeDone);
   for (auto& pr : c->evPool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   if (c->evA) (void)hipEventDestroy(c->evA);
   if (c->evB) (void)hipEventDestroy(c->evB);
@@ -98,6 +100,7 @@ int mm_set_option(mm_ctx* c, int option, int value) {
   if (option == MM_OPT_L2_WINDOW_WAVE) { o.l2WindowWave = value != 0; return MM_OK; }
   if (option == MM_OPT_L2_LARGE_WAVE) { o.l2LargeWave = value & 3; return MM_OK; }
   if (option == MM_OPT_CHAIN_LONG) { o.chainLong = value != 0; return MM_OK; }
+  if (option == MM_OPT_SKETCH_LARGE) { o.sketchLarge = value != 0; return MM_OK; }
   c->err = "mm_set_option: unknown option"; return MM_ERR_ARG;
 }
 

@@ -296,6 +296,15 @@ __device__ __forceinline__ void mm_strip_hashes_wide(const uint32_t (&w)[MMWideK
 #pragma unroll
   for (int j = 0; j < 16; j++) use(j, mm_murmur_kmer<K>(F, j), mm_murmur_kmer<K>(R, W - K - j));
 }
+// OR of every K-wide window: bit j of the result = any of bits j..j+K-1 of x (the N test of a strip, K <= 32)
+template <int K>
+__device__ __forceinline__ uint64_t mm_window_or(uint64_t x) {
+  constexpr int P = K >= 32 ? 32 : K >= 16 ? 16 : K >= 8 ? 8 : K >= 4 ? 4 : K >= 2 ? 2 : 1;
+  uint64_t w = x;
+#pragma unroll
+  for (int d = 1; d < P; d <<= 1) w |= w >> d;
+  return w | (w >> (K - P));
+}
 // bit j (j = 0..15) of the result: any of the mask bits j .. j+K-1 of the 128-bit value hi:lo is set (the N test of a wide strip)
 template <int K>
 __device__ __forceinline__ uint32_t mm_window_or_wide(uint64_t lo, uint64_t hi) {

@@ -72,7 +72,8 @@ static constexpr DevBuf DeviceIndex::* const MM_REPLICATED_BUFS[] = {
 // ---------------------------------------------------------------------------------------------
 enum : int {
   MM_CW_SKETCH        = 0,    //  0..7  the sketch launcher's (reset by it before its kernels).  In use: the low 32 bits of word 0, the
-  MM_CW_SKETCH_END    = 8,    //        length of the hard list, which the sketch kernels take as a uint32_t* to the start of the block
+  MM_CW_SKETCH_END    = 8,    //        length of the hard list, which the sketch kernels take as a uint32_t* to the start of the block;
+                              //        words 1 and 2, k_sketch_large's counts (MM_SKW_*)
   MM_CW_PASS          = 8,    //  8..   the mapping pass: `counters` of its kernels, `cnt` of its launchers, `passCnt` of k_l2_select (MM_PC_*)
   MM_CW_PASS_END      = 16,   //        ... the words a stage reads back in one copy (MM_PC_READ of them)
   MM_CW_SORT_LENS     = 16,   // 16..17 mapping pass, as 32-bit words: the lengths of the point path's lists (MM_SL_*)
@@ -111,6 +112,11 @@ enum : int {
   MM_PC_GRP_LEN        = MM_PC_MID_LEN // L1 stage under MM_OPT_L1_GROUP_FUSED: fragments k_lookup_groups handed over (dGrpList).  k_lookup_mid never runs in such a
                               // pass (-Y: useMid is off), and a sized pass reads the word back behind the lookup kernels either way (mm_pass_l1_group_fused)
 };
+enum : int {                  // relative to MM_CW_SKETCH: what k_sketch_large counts (mm_sketch_large_counts)
+  MM_SKW_LARGE_FRAGS = 1,     // fragments it sketched
+  MM_SKW_LARGE_UNCUT = 2      // ... whose final sort ran without a cut
+};
+static_assert(MM_CW_SKETCH + MM_SKW_LARGE_UNCUT < MM_CW_SKETCH_END, "k_sketch_large counts inside the sketch launcher's words");
 constexpr unsigned long long MM_OVERFLOWED = 1ull;   // what the kernels raise an overflow word to
 // bits of MM_PC_L2_FLAGS; any of them set in a steady-state pass has it redone the sized way
 constexpr unsigned long long MM_L2F_SLOTS  = 1ull;   // a candidate has more tied loci than the staging slots per candidate (the sized pass doubles them)
@@ -236,6 +242,10 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   DevBuf dSkHash, dSkPos, dSkStrand, dSkCount;          // [nFrags*s] u64, int2, i8 ; [nFrags] u32
   DevBuf dHardList, dCounters, dSketchSpill;            // dSketchSpill: first / last / strand-sum arrays of k_sketch_hard<K, true> (large sketches)
   DevBuf dSketchTabs; int sketchTabsK = 0;        // strip-hasher tables for kmerSize sketchTabsK (built once, copied into LDS by every workgroup)
+  // MM_OPT_SKETCH_LARGE: the two counts of k_sketch_large as of the last sketch launch -- copied to the page-locked hSkLarge behind the
+  // kernel (the mapping pass resets the words they are counted in); mm_sketch_large_counts waits for skLargeDone when the copy is pending
+  unsigned long long* hSkLarge = nullptr; hipEvent_t skLargeDone = nullptr;
+  int skLargeState = 0; uint64_t skLargeFrags = 0, skLargeUncut = 0;   // MM_SKL_STATE_*
   DevBuf dQHash, dQStrand;                              // post-removal sketch (written only for fragments that lose a frequent seed)
   DevBuf dStats;                                        // mm_frag_stats[nFrags]
   DevBuf dPtOff, dPts; size_t ptsCap = 0;               // per-fragment offset (int64) + sorted keys
@@ -354,6 +364,8 @@ int mm_launch_pack_raw(mm_ctx* c, const uint8_t* dAscii, const int64_t* dSrcOff,
                        int64_t nChunks, uint32_t* dB, uint32_t* dM, uint32_t* dHasN);
 int mm_launch_sketch(mm_ctx* c);
 int mm_launch_sketch_global(mm_ctx* c);   // mm_sketch_global.hip: sketches no LDS table holds (sketchSize > MM_LDS_MAX_SKETCH)
+int mm_launch_sketch_large(mm_ctx* c);    // mm_sketch_large.hip: the same sketches under MM_OPT_SKETCH_LARGE (strip hashers, LDS tiles)
+enum : int { MM_SKL_STATE_NONE = 0, MM_SKL_STATE_KNOWN = 1, MM_SKL_STATE_PENDING = 2 };   // mm_ctx::skLargeState: no sketch launch yet / counts on the host / their copy in flight
 // (MM_LDS_MAX_SKETCH, beyond which the global-memory sketch kernel and the literal L2 kernels take over: mm_pass_state.h)
 #define MM_WINNOW_LDS_SKETCH 4096          // the device index build keeps a window's sketch as one sorted array in LDS up to here (k_winnow_tiles: an insert shifts half of it), and as
                                            // blocks of 64 entries in HBM under an LDS directory beyond (k_winnow_tiles<.., GSK>: 0.7 s against 8.7 s of index build at sketchSize 9 998,

@@ -16,6 +16,7 @@ struct Options {                            // written by mm_set_option alone
   bool l1GroupFused = false;                // MM_OPT_L1_GROUP_FUSED: ... through k_lookup_groups first; the HBM point path takes what it hands over
   bool l2WindowWave = false;                // MM_OPT_L2_WINDOW_WAVE: the windowed L2 stage on k_l2_window_wave first, the literal k_l2_window takes what it hands over
   int l2LargeWave = 0;                      // MM_OPT_L2_LARGE_WAVE: bit 0: split batches on the literal L2 route go to k_l2_large_wave first; bit 1: they take that route at any sketch size
+  bool sketchLarge = false;                 // MM_OPT_SKETCH_LARGE: sketches beyond MM_LDS_MAX_SKETCH on k_sketch_large instead of k_sketch_global
   bool chainLong = false;                   // MM_OPT_CHAIN_LONG: reads of 17 .. 512 records are chained on the device as well
 };
 

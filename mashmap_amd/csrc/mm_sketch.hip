@@ -99,16 +99,6 @@ struct SkTable {                  // the hard kernel's table: every occurrence i
 // words of the fast kernel's position queue: the per-wave queues, but at least the table's load limit (the memory lists the occupied slots later)
 __host__ __device__ static inline int sketch_fast_queue_total(int QC, int nWaves, int HT) { const int a = QC * nWaves, b = HT * 5 / 8 + 1; return ((a > b ? a : b) + 3) & ~3; }
 
-// OR of every K-wide window: bit j of the result = any of bits j..j+K-1 of x
-template <int K>
-__device__ __forceinline__ uint64_t mm_window_or(uint64_t x) {
-  constexpr int P = K >= 32 ? 32 : K >= 16 ? 16 : K >= 8 ? 8 : K >= 4 ? 4 : K >= 2 ? 2 : 1;
-  uint64_t w = x;
-#pragma unroll
-  for (int d = 1; d < P; d <<= 1) w |= w >> d;
-  return w | (w >> (K - P));
-}
-
 // ---------------------------------------------------------------------------------------------
 // k_sketch_hard<K>: the fragments k_sketch_fast gave up on -- tandem repeats, low complexity, N-rich -- exact for any input.
 //   Survivors go straight from the hash loop into a larger table (duplicates collapse there, however many), and the cut T is
@@ -926,13 +916,14 @@ extern "C" int mm_bench_hash_only(mm_ctx* c, int reps, double* msAvg) {
 int mm_launch_sketch(mm_ctx* c) {
   const size_t nF = c->nFrags, s = (size_t)c->P.sketchSize;
   const size_t cF = mm_frag_cap(c, nF);               // (the largest batch the caller has announced: no reallocation when it comes)
+  c->skLargeState = MM_SKL_STATE_KNOWN; c->skLargeFrags = c->skLargeUncut = 0;   // mm_sketch_large_counts: 0 / 0 unless k_sketch_large runs below
   if (s > MM_LDS_MAX_SKETCH) {
     MM_HIP(c, c->dSkHash.ensure(nF * s * 8 + 64)); MM_HIP(c, c->dSkPos.ensure(nF * s * 8 + 64));
     MM_HIP(c, c->dSkStrand.ensure(nF * s + 64)); MM_HIP(c, c->dSkCount.ensure(nF * 4 + 64));
     MM_HIP(c, c->dHardList.ensure(nF * 4 + 64)); MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
     // no hard list here, and its length is read all the same (mm_pass_stats): the words every other sketch launch resets
     MM_HIP(c, hipMemsetAsync(c->dCounters.as<unsigned long long>() + MM_CW_SKETCH, 0, (size_t)(MM_CW_SKETCH_END - MM_CW_SKETCH) * 8, c->stream));
-    return mm_launch_sketch_global(c);
+    return c->opt.sketchLarge ? mm_launch_sketch_large(c) : mm_launch_sketch_global(c);
   }
   MM_HIP(c, c->dSkHash.ensure(cF * s * 8 + 64));
   MM_HIP(c, c->dSkPos.ensure(cF * s * 8 + 64));

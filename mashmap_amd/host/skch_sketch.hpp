@@ -150,6 +150,11 @@ class Sketch {
         std::cerr << "[mashmap_hip::skch::Sketch] ERROR: mm_set_option: " << mm_last_error(c) << std::endl;
         exit(1);
       }
+      // ... and its sketches on k_sketch_large instead of the global-memory sketch kernel (profiles/NOTES.md: the probe that decided it)
+      if (p.sketchSize > 8190 && mm_set_option(c, MM_OPT_SKETCH_LARGE, 1) != MM_OK) {
+        std::cerr << "[mashmap_hip::skch::Sketch] ERROR: mm_set_option: " << mm_last_error(c) << std::endl;
+        exit(1);
+      }
       ctxs_.push_back(c);
     }
     ctx_ = ctxs_[0];

@@ -14,7 +14,15 @@ process; "spread" is the parent's largest minus smallest figure over its three r
   1. With the option, MM_K_L2 + MM_K_L2_LOCATE is below the parent's by more than the parent's spread of that sum, in every pair.
   2. With the option, the whole pass is not slower than the parent's by more than the parent's spread of the whole pass, in every pair.
   3. Without the option this tree equals the parent within the spread, compared on the medians over the three rounds.
-skch::Sketch sets the option for sketchSize > 8190 if 1 and 2 hold on both rows; 3 is reported either way."""
+skch::Sketch sets the option for sketchSize > 8190 if 1 and 2 hold on both rows; 3 is reported either way.
+
+--sketch-large sets MM_OPT_SKETCH_LARGE (k_sketch_large instead of the global-memory sketch kernel); the line then carries (fragments,
+uncut) of mm_sketch_large_counts as well.  Its rule, stated before the first run, on the same two rows and the same three rounds of
+(parent, this tree with --sketch-large, this tree without), MM_OPT_L2_LARGE_WAVE = 1 (--option 1) in all three:
+  1. With the option, MM_K_SKETCH + MM_K_SKETCH_HARD (k_sketch_ms) is below the parent's in every pair, by more than the parent's spread.
+  2. With the option, the whole pass is below the parent's by more than the parent's spread of the whole pass, in every pair.
+  3. Without the option, both figures equal the parent's within its spread (medians over the three rounds).
+skch::Sketch sets MM_OPT_SKETCH_LARGE for sketchSize > 8190 if 1 and 2 hold on both rows."""
 import argparse
 import json
 import os
@@ -31,6 +39,7 @@ ap.add_argument("--reads", type=int, default=40)
 ap.add_argument("--read-len", type=int, default=450000)
 ap.add_argument("--err", type=float, default=0.03)
 ap.add_argument("--option", type=int, default=0)
+ap.add_argument("--sketch-large", action="store_true")
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--tag", default="")
@@ -53,6 +62,7 @@ for i in range(a.reads):
 
 ctx = capi.Context(k=K, segLength=a.seg, sketchSize=a.sketch, flags=0)
 if a.option: ctx.l2_large_wave(a.option)
+if a.sketch_large: ctx.sketch_large()
 t0 = time.perf_counter()
 ctx.index_build(contigs)
 lib = capi.load()
@@ -71,10 +81,11 @@ for it in range(a.warmup + a.reps):
     pr = ctx.profile_read(True)
     if it >= a.warmup: rows.append((pr["sketch"][0] + pr["sketch_hard"][0], pr["lookup"][0] + pr["sort"][0], pr["l1"][0], pr["l2_locate"][0], pr["l2"][0], ms))
 cands, literal = ctx.pass_l2_large() if hasattr(ctx, "pass_l2_large") else (None, None)
+sk_large = ctx.sketch_large_counts() if hasattr(ctx, "sketch_large_counts") else None
 nL1, nL2 = ctx.result_counts()
 med = [float(np.median([r[i] for r in rows])) for i in range(6)]
-print(json.dumps(dict(tag=a.tag, option=a.option, seg=a.seg, sketch=a.sketch, fragments=nF, candidates=cands, literal=literal, nL1=nL1, nL2=nL2,
+print(json.dumps(dict(tag=a.tag, option=a.option, sketch_large=bool(a.sketch_large), sketch_large_counts=sk_large, seg=a.seg, sketch=a.sketch, fragments=nF, candidates=cands, literal=literal, nL1=nL1, nL2=nL2,
                       k_sketch_ms=round(med[0], 3), k_lookup_sort_ms=round(med[1], 3), k_l1_ms=round(med[2], 3), k_l2_locate_ms=round(med[3], 3),
                       k_l2_ms=round(med[4], 3), pass_ms=round(med[5], 3), pass_ms_min=round(min(r[5] for r in rows), 3),
-                      k_l2_ms_all=[round(r[4], 3) for r in rows], setup_s=round(t_setup, 2))))
+                      k_l2_ms_all=[round(r[4], 3) for r in rows], k_sketch_ms_all=[round(r[0], 3) for r in rows], setup_s=round(t_setup, 2))))
 ctx.close()
