@@ -7,6 +7,7 @@
 // packed input is only 0.25 B/bp (+0.125 B/bp N mask).  See DESIGN.md for the roofline terms.
 #include "mm_internal.h"
 #include "mm_device.h"
+#include "mm_sketch_dev.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -54,26 +55,16 @@ __global__ void k_pack2bit(const uint8_t* __restrict__ ascii, const int64_t* __r
 //   so rank(key) = occupied slots before its cluster + keys of its own cluster that are smaller:
 //   the table scan replaces compaction + sort.
 // ---------------------------------------------------------------------------------------------
-#define MM_SK_PAD 64               // spill slots behind the ordered tables (no wrap-around): fast kernel
-#define MM_SK_PADH 256             // hard kernel
-#define MM_SK_DUPCAP 256          // repeat occurrences a fast-kernel fragment may defer (more: the hard kernel takes the fragment)
-#define MM_SK_GUARD 4             // always-empty slots on either side of the table: the ranking reads windows of that many neighbours
+// (MM_SK_PAD, MM_SK_PADH, MM_SK_DUPCAP, MM_SK_GUARD and the LDS layouts: mm_sketch_plan.h; the cut's M / sh / home, SkCut: mm_sketch_dev.h)
+static_assert(sizeof(MMTables) == MM_SK_TABLE_BYTES && sizeof(MMProdTables) == MM_SK_PROD_TABLE_BYTES, "mm_sketch_plan.h sizes the LDS with these tables");
+static_assert(MM_SK_HASH_MAX == MM_HASH_MAX, "one value for `no cut`");
 // slots of `counters`, the four LDS words each sketch table keeps beside itself (not mm_ctx::dCounters)
 enum : int { MM_TC_KEYS = 0 /* distinct keys */, MM_TC_OVERFLOW = 1 /* load limit passed, spill area or duplicate list full */, MM_TC_OCCUPIED = 2 /* occupied slots */, MM_TC_DUPS = 3 /* deferred duplicates (fast kernel) */ };
-struct SkTable {                  // the hard kernel's table: every occurrence is folded in with atomics as it is hashed
+struct SkTable : SkCut {          // the hard kernel's table: every occurrence is folded in with atomics as it is hashed
   uint64_t* key; int32_t* first; int32_t* last; int32_t* sum;
   uint32_t* counters;            // MM_TC_KEYS, MM_TC_OVERFLOW, MM_TC_OCCUPIED
   uint64_t* occW; uint32_t* occP; // occupancy bit words and their exclusive prefix counts
-  uint32_t nSlots, maxLoad, M; int sh;
-
-  // slots for hashes in [0, T): x = top 32 bits of h after normalising T to bit 63, home = x * M >> 32 with
-  // M <= 2^32 * HT / (x_max + 1)  (any smaller M keeps home < HT and monotone; the float estimate is shaded down)
-  __device__ __forceinline__ void set_cut(uint64_t T, uint32_t HT) {
-    sh = (T == MM_HASH_MAX) ? 0 : __clzll((long long)T);
-    const uint64_t t32 = ((T << sh) >> 32) + 1ull;
-    M = (uint32_t)((float)HT * 4294967296.0f / (float)t32 * 0.99999f);
-  }
-  __device__ __forceinline__ uint32_t home(uint64_t h) const { return __umulhi((uint32_t)((h << sh) >> 32), M); }
+  uint32_t nSlots, maxLoad;
 
   // the number of distinct keys is kept in counters[MM_TC_KEYS] and the load limit flagged as it is passed: the kernel inserts straight from
   // the hash loop and must notice a flooded table early
@@ -95,9 +86,6 @@ struct SkTable {                  // the hard kernel's table: every occurrence i
     }
   }
 };
-
-// words of the fast kernel's position queue: the per-wave queues, but at least the table's load limit (the memory lists the occupied slots later)
-__host__ __device__ static inline int sketch_fast_queue_total(int QC, int nWaves, int HT) { const int a = QC * nWaves, b = HT * 5 / 8 + 1; return ((a > b ? a : b) + 3) & ~3; }
 
 // ---------------------------------------------------------------------------------------------
 // k_sketch_hard<K>: the fragments k_sketch_fast gave up on -- tandem repeats, low complexity, N-rich -- exact for any input.
@@ -123,59 +111,42 @@ mm_sketch_hard(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   const bool hasN = readHasN[fr.readId] != 0;
   const uint32_t hint = skCount[f];                 // distinct survivors under the fast kernel's cut, or MM_SK_HINT_OVERFLOW
 
-  // ---- LDS carve (every offset a multiple of 16) ----
-  const int nW = stream ? 0 : (len + 15) / 16 + 3;  // code words incl. 2 words of run-off for the last strip
-  const int nM = stream ? 0 : (len + 31) / 32 + 2;
-  const int NS = HT + PAD;                          // table slots (multiple of 64)
-  const int nOcc = NS >> 6;
-  size_t off = 0;
+  // ---- LDS carve: sketch_hard_layout (mm_sketch_plan.h), which sized the launch at the longest fragment ----
   using Tabs = typename MMTabsFor<K>::type;
-  Tabs* tabs = (Tabs*)(smem + off); off += sizeof(Tabs);
+  const SkHardLayout lay = sketch_hard_layout(sizeof(Tabs), len, HT, PAD, SPILL, stream);
+  const int nW = lay.nW, nM = lay.nM, NS = lay.NS, nOcc = lay.nOcc;   // NS: table slots (multiple of 64)
+  Tabs* tabs = (Tabs*)(smem + lay.tabs);
   static_assert(sizeof(Tabs) % 16 == 0, "tables are copied in 16-byte pieces");
   for (int i = tid; i < (int)(sizeof(Tabs) / 16); i += nthr) ((uint4*)tabs)[i] = gTabs[i];   // visible after the first __syncthreads() below
-  uint32_t* sW = (uint32_t*)(smem + off); off += (((size_t)nW * 4 + 15) / 16) * 16;
-  uint32_t* sM = (uint32_t*)(smem + off); off += (((size_t)nM * 4 + 15) / 16) * 16;
+  uint32_t* sW = (uint32_t*)(smem + lay.sW);
+  uint32_t* sM = (uint32_t*)(smem + lay.sM);
   SkTable tab;
-  tab.key = (uint64_t*)(smem + off) + MM_SK_GUARD; off += (size_t)(NS + 2 * MM_SK_GUARD) * 8;   // MM_SK_GUARD always-empty slots on either side: the ranking reads windows
-  tab.occW = (uint64_t*)(smem + off); off += (size_t)nOcc * 8;
+  tab.key = (uint64_t*)(smem + lay.key) + MM_SK_GUARD;   // MM_SK_GUARD always-empty slots on either side: the ranking reads windows
+  tab.occW = (uint64_t*)(smem + lay.occW);
   if constexpr (SPILL) {
     int32_t* g = spill + (size_t)blockIdx.x * 3 * (size_t)NS;
     tab.first = g; tab.last = g + NS; tab.sum = g + 2 * (size_t)NS;
   } else {
-    tab.first = (int32_t*)(smem + off); off += (size_t)NS * 4;
-    tab.last = (int32_t*)(smem + off); off += (size_t)NS * 4;
-    tab.sum = (int32_t*)(smem + off); off += (size_t)NS * 4;
+    tab.first = (int32_t*)(smem + lay.first); tab.last = (int32_t*)(smem + lay.last); tab.sum = (int32_t*)(smem + lay.sum);
   }
-  tab.occP = (uint32_t*)(smem + off); off += (((size_t)nOcc * 4 + 15) / 16) * 16;
-  tab.counters = (uint32_t*)(smem + off); off += 16;
+  tab.occP = (uint32_t*)(smem + lay.occP);
+  tab.counters = (uint32_t*)(smem + lay.counters);
   tab.nSlots = (uint32_t)NS; tab.maxLoad = (uint32_t)HT * 5u / 8u;
 
   // ---- stage the fragment, re-aligned so that LDS word j holds bases 16j..16j+15 ----
   const int64_t gw0 = fr.base >> 4; const int gsh = (int)(fr.base & 15) * 2;
   const int64_t gm0 = fr.base >> 5; const int gmsh = (int)(fr.base & 31);
-  {
-    for (int j = tid; j < nW; j += nthr) {
-      const uint32_t a = bases2[gw0 + j], b = bases2[gw0 + j + 1];
-      sW[j] = gsh ? __builtin_amdgcn_alignbit(b, a, gsh) : a;
-    }
-    if (hasN) {
-      for (int j = tid; j < nM; j += nthr) {
-        const uint32_t a = nmask[gm0 + j], b = nmask[gm0 + j + 1];
-        sM[j] = gmsh ? __builtin_amdgcn_alignbit(b, a, gmsh) : a;
-      }
-    }
-  }
+  mm_sk_stage(sW, nW, bases2, gw0, gsh, tid, nthr);
+  if (hasN) mm_sk_stage(sM, nM, nmask, gm0, gmsh, tid, nthr);
   // word j of the re-aligned fragment / of its N mask: from the LDS copy, or -- a fragment longer than the LDS (a whole contig under
   // --noSplit) -- straight from the packed batch, realigned on the fly (neighbouring strips share their words in the caches)
   auto wordAt = [&](int j) -> uint32_t {
     if (!stream) return sW[j];
-    const uint32_t a = bases2[gw0 + j], b = bases2[gw0 + j + 1];
-    return gsh ? __builtin_amdgcn_alignbit(b, a, gsh) : a;
+    return mm_sk_word_at(bases2, gw0, gsh, j);
   };
   auto maskAt = [&](int j) -> uint32_t {
     if (!stream) return sM[j];
-    const uint32_t a = nmask[gm0 + j], b = nmask[gm0 + j + 1];
-    return gmsh ? __builtin_amdgcn_alignbit(b, a, gmsh) : a;
+    return mm_sk_word_at(nmask, gm0, gmsh, j);
   };
 
   // Any cut gives the exact sketch as long as >= s distinct hashes survive it (checked below), so float estimates are enough.
@@ -187,7 +158,7 @@ mm_sketch_hard(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
     const float t = (float)T * r;
     return t >= 1.8e19f ? MM_HASH_MAX : (uint64_t)t;
   };
-  uint64_t T = ((uint32_t)wantFast >= (uint32_t)n) ? MM_HASH_MAX : (uint64_t)((float)wantFast / (float)(2 * n) * 18446744073709551616.0f);   // the fast kernel's cut
+  uint64_t T = mm_sketch_fast_cut(wantFast, n);     // the fast kernel's cut
   if (hint != MM_SK_HINT_OVERFLOW && T != MM_HASH_MAX) T = scaled(T, hint);
   uint64_t lo = 0, hi = MM_HASH_MAX; bool hiInf = true;   // bisection state (uniform across the block)
   const int nStrips = (n + 15) >> 4;
@@ -207,14 +178,7 @@ mm_sketch_hard(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
       // bit j: position strip*16+j exists and its k-mer holds no N
       const int rem = n - strip * 16;
       uint32_t ok = rem >= 16 ? 0xFFFFu : ((1u << rem) - 1u);
-      if (hasN) {
-        const uint64_t m64 = (uint64_t)maskAt(strip >> 1) | ((uint64_t)maskAt((strip >> 1) + 1) << 32);
-        if constexpr (MMWideK<K>::value) {
-          const uint64_t h64 = (uint64_t)maskAt((strip >> 1) + 2) | ((uint64_t)maskAt((strip >> 1) + 3) << 32);
-          const int sh = (strip & 1) * 16;
-          ok &= ~mm_window_or_wide<K>(sh ? ((m64 >> sh) | (h64 << (64 - sh))) : m64, sh ? (h64 >> sh) : h64);
-        } else ok &= ~(uint32_t)mm_window_or<K>(m64 >> ((strip & 1) * 16));
-      }
+      if (hasN) ok &= ~mm_sk_strip_has_n<K>(strip, maskAt);
       auto onPos = [&](int j, uint64_t hf, uint64_t hr) {
         const int pos = strip * 16 + j;
         const uint64_t h = hf < hr ? hf : hr;
@@ -232,26 +196,8 @@ mm_sketch_hard(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
     if constexpr (SPILL) __threadfence();                 // the atomics on the spilled arrays, before the ranking threads read them
     __syncthreads();
 
-    // ---- occupancy words, their prefix counts (wave 0: one DPP scan per 64 words), number of distinct keys ----
-    for (int base = 0; base < NS; base += nthr) {
-      const int slot = base + tid;                  // NS and nthr are multiples of 64: a wave is in or out as a whole
-      if (slot < NS) {
-        const uint64_t m = __ballot(tab.key[slot] != MM_HASH_MAX);
-        if (mm_lane() == 0) tab.occW[slot >> 6] = m;
-      }
-    }
-    __syncthreads();
-    if (tid < 64) {
-      int carry = 0;
-      for (int w0 = 0; w0 < nOcc; w0 += 64) {
-        const int w = w0 + tid;
-        const int v = w < nOcc ? (int)__popcll(tab.occW[w]) : 0;
-        const int ex = mm_wave_excl_scan(v);
-        if (w < nOcc) tab.occP[w] = (uint32_t)(carry + ex);
-        carry += mm_wave_sum(v);
-      }
-      if (tid == 0) tab.counters[MM_TC_OCCUPIED] = (uint32_t)carry;
-    }
+    // ---- occupancy words, their prefix counts, number of distinct keys ----
+    mm_sk_occupancy(tab.key, tab.occW, tab.occP, NS, nOcc, tid, nthr, [&](int total) { tab.counters[MM_TC_OCCUPIED] = (uint32_t)total; });
     __syncthreads();
 
     D = tab.counters[MM_TC_OCCUPIED];
@@ -268,23 +214,8 @@ mm_sketch_hard(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   for (int slot = tid; slot < NS; slot += nthr) {
     const uint64_t k = tab.key[slot];
     if (k == MM_HASH_MAX) continue;
-    // the cluster around the slot: MM_SK_GUARD neighbours on either side are fetched at once (independent LDS reads, one latency);
-    // only a cluster that reaches further is walked slot by slot.  The guard slots beyond the table are always empty.
-    uint64_t L[MM_SK_GUARD], Rr[MM_SK_GUARD];
-#pragma unroll
-    for (int i = 0; i < MM_SK_GUARD; i++) { L[i] = tab.key[slot - 1 - i]; Rr[i] = tab.key[slot + 1 + i]; }
-    uint32_t smaller = 0;
-    int q = slot;                                   // -> first slot of the cluster
-    bool openL = true, openR = true;
-#pragma unroll
-    for (int i = 0; i < MM_SK_GUARD; i++) {
-      openL = openL && L[i] != MM_HASH_MAX;
-      openR = openR && Rr[i] != MM_HASH_MAX;
-      if (openL) { smaller += L[i] < k ? 1u : 0u; q = slot - 1 - i; }
-      if (openR) smaller += Rr[i] < k ? 1u : 0u;
-    }
-    if (openL) { while (q > 0) { const uint64_t o = tab.key[q - 1]; if (o == MM_HASH_MAX) break; smaller += o < k ? 1u : 0u; q--; } }
-    if (openR) { for (int r = slot + 1 + MM_SK_GUARD; r < NS; r++) { const uint64_t o = tab.key[r]; if (o == MM_HASH_MAX) break; smaller += o < k ? 1u : 0u; } }
+    int q;                                          // -> first slot of the cluster
+    const uint32_t smaller = mm_sk_cluster_smaller(tab.key, slot, k, NS, q);
     const uint64_t below = tab.occW[q >> 6] & ((1ull << (q & 63)) - 1ull);
     const uint32_t rank = tab.occP[q >> 6] + (uint32_t)__popcll(below) + smaller;
     if (rank < (uint32_t)s) {
@@ -297,9 +228,7 @@ mm_sketch_hard(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
         vs = __hip_atomic_load(&tab.sum[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       } else { vf = tab.first[slot]; vl = tab.last[slot]; vs = tab.sum[slot]; }
       skPos[o] = make_int2(vf, vl);
-      // the reference accumulates the strand in an int16 (base_types.hpp:24, commonFunc.hpp:268)
-      const int16_t acc = (int16_t)vs;
-      skStrand[o] = acc > 0 ? 1 : (acc == 0 ? 0 : -1);
+      skStrand[o] = mm_sk_strand(vs);
     }
   }
   if (tid == 0) skCount[f] = D < (uint32_t)s ? D : (uint32_t)s;
@@ -340,17 +269,11 @@ k_sketch_all_hard(int nF, int32_t* __restrict__ hardList, uint32_t* __restrict__
 // A fragment that overflows any of it (queue, table, duplicate list) or keeps fewer than s distinct survivors goes to the hard list.
 // ---------------------------------------------------------------------------------------------
 #define MM_SKF_FLAG 0x80000000u
-struct SkFast {
+struct SkFast : SkCut {
   uint64_t* key; uint32_t* meta;      // meta: bit 31 = has entries on the duplicate list, low bits = pos << 1 | (strand > 0) of the owner
   uint32_t* dup; uint32_t* counters;  // counters: MM_TC_OVERFLOW, MM_TC_OCCUPIED, MM_TC_DUPS
   uint64_t* occW; uint32_t* occP;
-  uint32_t nSlots, maxLoad, M; int sh;
-  __device__ __forceinline__ void set_cut(uint64_t T, uint32_t HT) {
-    sh = (T == MM_HASH_MAX) ? 0 : __clzll((long long)T);
-    const uint64_t t32 = ((T << sh) >> 32) + 1ull;
-    M = (uint32_t)((float)HT * 4294967296.0f / (float)t32 * 0.99999f);
-  }
-  __device__ __forceinline__ uint32_t home(uint64_t h) const { return __umulhi((uint32_t)((h << sh) >> 32), M); }
+  uint32_t nSlots, maxLoad;
   __device__ __forceinline__ void insert(uint64_t h, uint32_t m) {
     uint32_t slot = home(h);
     for (;;) {
@@ -385,49 +308,33 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   if (n <= 0) { if (tid == 0) skCount[f] = 0; return; }
   const bool hasN = readHasN[fr.readId] != 0;
 
-  // ---- LDS carve (every offset a multiple of 16) ----
-  const int nW = (len + 15) / 16 + 4;               // code words incl. run-off for the last strip's window
-  const int nM = (len + 31) / 32 + 3;
-  const int NS = HT + PAD;                          // table slots (multiple of 64)
-  const int nOcc = NS >> 6;
-  const int nWaves = nthr >> 6;
-  const int QTOT = sketch_fast_queue_total(QC, nWaves, HT);   // >= the table's load limit: the memory serves as the list of occupied slots later
-  size_t off = 0;
+  // ---- LDS carve: sketch_fast_layout (mm_sketch_plan.h), which sized the launch at the longest fragment ----
   using Tabs = typename MMTabsFor<K>::type;
-  Tabs* tabs = (Tabs*)(smem + off); off += sizeof(Tabs);
+  const int nWaves = nthr >> 6;
+  const SkFastLayout lay = sketch_fast_layout(sizeof(Tabs), len, HT, PAD, QC, nWaves);
+  const int nW = lay.nW, nM = lay.nM, NS = lay.NS, nOcc = lay.nOcc;   // NS: table slots (multiple of 64)
+  Tabs* tabs = (Tabs*)(smem + lay.tabs);
   for (int i = tid; i < (int)(sizeof(Tabs) / 16); i += nthr) ((uint4*)tabs)[i] = gTabs[i];   // visible after the first __syncthreads() below
-  uint32_t* sW = (uint32_t*)(smem + off); off += (((size_t)nW * 4 + 15) / 16) * 16;
-  uint32_t* sM = (uint32_t*)(smem + off); off += (((size_t)nM * 4 + 15) / 16) * 16;
-  uint64_t* qH = (uint64_t*)(smem + off); off += (size_t)QC * nWaves * 8;        // per-wave queues: hashes
-  uint32_t* qM = (uint32_t*)(smem + off); off += (size_t)QTOT * 4;               //                  pos<<1 | (strand > 0)
+  uint32_t* sW = (uint32_t*)(smem + lay.sW);
+  uint32_t* sM = (uint32_t*)(smem + lay.sM);
+  uint64_t* qH = (uint64_t*)(smem + lay.qH);        // per-wave queues: hashes
+  uint32_t* qM = (uint32_t*)(smem + lay.qM);        //                  pos<<1 | (strand > 0); >= the table's load limit: the memory serves as the list of occupied slots later
   SkFast tab;
-  tab.key = (uint64_t*)(smem + off) + MM_SK_GUARD; off += (size_t)(NS + 2 * MM_SK_GUARD) * 8;
-  tab.occW = (uint64_t*)(smem + off); off += (size_t)nOcc * 8;
-  tab.meta = (uint32_t*)(smem + off); off += (size_t)NS * 4;
-  tab.occP = (uint32_t*)(smem + off); off += (((size_t)nOcc * 4 + 15) / 16) * 16;
-  uint32_t* qCnt = (uint32_t*)(smem + off); off += 64;
-  tab.dup = (uint32_t*)(smem + off); off += (size_t)MM_SK_DUPCAP * 4;
-  tab.counters = (uint32_t*)(smem + off); off += 16;
+  tab.key = (uint64_t*)(smem + lay.key) + MM_SK_GUARD;
+  tab.occW = (uint64_t*)(smem + lay.occW);
+  tab.meta = (uint32_t*)(smem + lay.meta);
+  tab.occP = (uint32_t*)(smem + lay.occP);
+  uint32_t* qCnt = (uint32_t*)(smem + lay.qCnt);
+  tab.dup = (uint32_t*)(smem + lay.dup);
+  tab.counters = (uint32_t*)(smem + lay.counters);
   tab.nSlots = (uint32_t)NS; tab.maxLoad = (uint32_t)HT * 5u / 8u;
 
   // ---- stage the fragment, re-aligned so that LDS word j holds bases 16j..16j+15 ----
-  {
-    const int64_t w0 = fr.base >> 4; const int sh = (int)(fr.base & 15) * 2;
-    for (int j = tid; j < nW; j += nthr) {
-      const uint32_t a = bases2[w0 + j], b = bases2[w0 + j + 1];
-      sW[j] = sh ? __builtin_amdgcn_alignbit(b, a, sh) : a;
-    }
-    if (hasN) {
-      const int64_t m0 = fr.base >> 5; const int msh = (int)(fr.base & 31);
-      for (int j = tid; j < nM; j += nthr) {
-        const uint32_t a = nmask[m0 + j], b = nmask[m0 + j + 1];
-        sM[j] = msh ? __builtin_amdgcn_alignbit(b, a, msh) : a;
-      }
-    }
-  }
+  mm_sk_stage(sW, nW, bases2, fr.base >> 4, (int)(fr.base & 15) * 2, tid, nthr);
+  if (hasN) mm_sk_stage(sM, nM, nmask, fr.base >> 5, (int)(fr.base & 31), tid, nthr);
   // threshold: the canonical hash is the smaller of two uniform 64-bit values, so P[h < T] ~ 2T / 2^64; the cut is placed where
   // `wantFast` (> s) survivors are expected.  Any T gives the exact sketch as long as >= s distinct hashes survive (checked below).
-  const uint64_t T = ((uint32_t)wantFast >= (uint32_t)n) ? MM_HASH_MAX : (uint64_t)((float)wantFast / (float)(2 * n) * 18446744073709551616.0f);
+  const uint64_t T = mm_sketch_fast_cut(wantFast, n);
   const int nStrips = (n + SL - 1) / SL;
   tab.set_cut(T, (uint32_t)HT);
   for (int i = tid; i < NS; i += nthr) tab.key[i] = MM_HASH_MAX;
@@ -523,26 +430,9 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
     const uint32_t nd = tab.counters[MM_TC_DUPS] < MM_SK_DUPCAP ? tab.counters[MM_TC_DUPS] : MM_SK_DUPCAP;
     for (uint32_t i = (uint32_t)tid; i < nd; i += (uint32_t)nthr) atomicOr(&tab.meta[tab.dup[i] & 0x1FFFu], MM_SKF_FLAG);
   }
-  // ---- occupancy words, their prefix counts (wave 0: one DPP scan per 64 words), number of distinct keys ----
-  for (int base = 0; base < NS; base += nthr) {
-    const int slot = base + tid;                    // NS and nthr are multiples of 64: a wave is in or out as a whole
-    if (slot < NS) {
-      const uint64_t m = __ballot(tab.key[slot] != MM_HASH_MAX);
-      if (mm_lane() == 0) tab.occW[slot >> 6] = m;
-    }
-  }
-  __syncthreads();
-  if (tid < 64) {
-    int carry = 0;
-    for (int w0 = 0; w0 < nOcc; w0 += 64) {
-      const int w = w0 + tid;
-      const int v = w < nOcc ? (int)__popcll(tab.occW[w]) : 0;
-      const int ex = mm_wave_excl_scan(v);
-      if (w < nOcc) tab.occP[w] = (uint32_t)(carry + ex);
-      carry += mm_wave_sum(v);
-    }
-    if (tid == 0) { tab.counters[MM_TC_OCCUPIED] = (uint32_t)carry; if ((uint32_t)carry > tab.maxLoad) tab.counters[MM_TC_OVERFLOW] = 1u; }
-  }
+  // ---- occupancy words, their prefix counts, number of distinct keys ----
+  mm_sk_occupancy(tab.key, tab.occW, tab.occP, NS, nOcc, tid, nthr,
+                  [&](int total) { tab.counters[MM_TC_OCCUPIED] = (uint32_t)total; if ((uint32_t)total > tab.maxLoad) tab.counters[MM_TC_OVERFLOW] = 1u; });
   __syncthreads();
   const uint32_t D = tab.counters[MM_TC_OCCUPIED];
   if (tab.counters[MM_TC_OVERFLOW] != 0 || (D < (uint32_t)s && T != MM_HASH_MAX)) {
@@ -565,23 +455,8 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   for (int it = tid; it < (int)D; it += nthr) {
     const int slot = (int)occList[it];
     const uint64_t k = tab.key[slot];
-    // the cluster around the slot: MM_SK_GUARD neighbours on either side are fetched at once (independent LDS reads, one latency);
-    // only a cluster that reaches further is walked slot by slot.  The guard slots beyond the table are always empty.
-    uint64_t L[MM_SK_GUARD], Rr[MM_SK_GUARD];
-#pragma unroll
-    for (int i = 0; i < MM_SK_GUARD; i++) { L[i] = tab.key[slot - 1 - i]; Rr[i] = tab.key[slot + 1 + i]; }
-    uint32_t smaller = 0;
-    int q = slot;                                   // -> first slot of the cluster
-    bool openL = true, openR = true;
-#pragma unroll
-    for (int i = 0; i < MM_SK_GUARD; i++) {
-      openL = openL && L[i] != MM_HASH_MAX;
-      openR = openR && Rr[i] != MM_HASH_MAX;
-      if (openL) { smaller += L[i] < k ? 1u : 0u; q = slot - 1 - i; }
-      if (openR) smaller += Rr[i] < k ? 1u : 0u;
-    }
-    if (openL) { while (q > 0) { const uint64_t o = tab.key[q - 1]; if (o == MM_HASH_MAX) break; smaller += o < k ? 1u : 0u; q--; } }
-    if (openR) { for (int r = slot + 1 + MM_SK_GUARD; r < NS; r++) { const uint64_t o = tab.key[r]; if (o == MM_HASH_MAX) break; smaller += o < k ? 1u : 0u; } }
+    int q;                                          // -> first slot of the cluster
+    const uint32_t smaller = mm_sk_cluster_smaller(tab.key, slot, k, NS, q);
     const uint32_t rank = (uint32_t)(it - (slot - q)) + smaller;               // every slot of [q, slot) is occupied
     if (rank < (uint32_t)s) {
       const uint32_t m = tab.meta[slot];
@@ -597,9 +472,7 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
       const size_t o = (size_t)f * s + rank;
       skHash[o] = k;
       skPos[o] = make_int2(first, last);
-      // the reference accumulates the strand in an int16 (base_types.hpp:24, commonFunc.hpp:268)
-      const int16_t acc = (int16_t)sum;
-      skStrand[o] = acc > 0 ? 1 : (acc == 0 ? 0 : -1);
+      skStrand[o] = mm_sk_strand(sum);
     }
   }
   if (tid == 0) skCount[f] = D < (uint32_t)s ? D : (uint32_t)s;
@@ -634,23 +507,19 @@ k_hash_only(const uint4* __restrict__ gTabs, const uint32_t* __restrict__ bases2
   const int tid = threadIdx.x, nthr = blockDim.x;
   if (n <= 0) return;
   using Tabs = typename MMTabsFor<K>::type;
-  Tabs* tabs = (Tabs*)smem;
+  // the front of the fast kernel's carve, [0, sM): tables and staged code words, which the table's and the queues' sizes do not move
+  const SkFastLayout lay = sketch_fast_layout(sizeof(Tabs), len, 0, 0, 0, 0);
+  Tabs* tabs = (Tabs*)(smem + lay.tabs);
   for (int i = tid; i < (int)(sizeof(Tabs) / 16); i += nthr) ((uint4*)tabs)[i] = gTabs[i];
-  uint32_t* sW = (uint32_t*)(smem + sizeof(Tabs));
-  const int nW = (len + 15) / 16 + 4;
-  {
-    const int64_t w0 = fr.base >> 4; const int sh = (int)(fr.base & 15) * 2;
-    for (int j = tid; j < nW; j += nthr) {
-      const uint32_t a = bases2[w0 + j], b = bases2[w0 + j + 1];
-      sW[j] = sh ? __builtin_amdgcn_alignbit(b, a, sh) : a;
-    }
-  }
+  uint32_t* sW = (uint32_t*)(smem + lay.sW);
+  mm_sk_stage(sW, lay.nW, bases2, fr.base >> 4, (int)(fr.base & 15) * 2, tid, nthr);
   __syncthreads();
   const int nStrips = (n + SL - 1) / SL;
   uint64_t acc = 0;
   for (int strip = tid; strip < nStrips; strip += nthr) {
     const int b0 = strip * SL;
     const int wi = b0 >> 4, bsh = (b0 & 15) * 2;
+    // (the fast kernel's lines, word for word: as a shared helper they cost this kernel an instruction per strip, so they are stated twice)
     uint32_t w0 = sW[wi], w1 = sW[wi + 1], w2 = sW[wi + 2];
     if (SL % 16 != 0) {
       const uint32_t w3 = sW[wi + 3];
@@ -665,131 +534,46 @@ k_hash_only(const uint4* __restrict__ gTabs, const uint32_t* __restrict__ bases2
 template <int K>
 __global__ void k_sketch_tables(typename MMTabsFor<K>::type* out) { mm_tables_init<K>(*out, (int)threadIdx.x, (int)blockDim.x); }
 
-// ---------------------------------------------------------------------------------------------
-static size_t sketch_hard_lds(size_t tabBytes, int maxLen, int HT, int PAD) {      // the carve of mm_sketch_hard
-  const size_t nW = (size_t)(maxLen + 15) / 16 + 3, nM = (size_t)(maxLen + 31) / 32 + 2;
-  const size_t NS = (size_t)HT + PAD, nOcc = NS / 64;
-  return tabBytes + ((nW * 4 + 15) / 16) * 16 + ((nM * 4 + 15) / 16) * 16 + NS * (8 + 4 + 4 + 4) + 2 * MM_SK_GUARD * 8 + nOcc * 8 +
-         ((nOcc * 4 + 15) / 16) * 16 + 16;
-}
-static int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
-// geometry of the fast kernel for fragments of up to maxLen bases: positions per thread, threads, table and queue sizes
-struct FastGeom { int SL, threads, HT, QC, wantFast; size_t lds; };
-static size_t sketch_fast_lds(size_t tabBytes, int maxLen, int HT, int PAD, int QC, int nWaves) {
-  const size_t nW = (size_t)(maxLen + 15) / 16 + 4, nM = (size_t)(maxLen + 31) / 32 + 3;
-  const size_t NS = (size_t)HT + PAD, nOcc = NS / 64;
-  return tabBytes + ((nW * 4 + 15) / 16) * 16 + ((nM * 4 + 15) / 16) * 16 + (size_t)QC * nWaves * 8 + (size_t)sketch_fast_queue_total(QC, nWaves, HT) * 4 +
-         (NS + 2 * MM_SK_GUARD) * 8 + nOcc * 8 + NS * 4 + ((nOcc * 4 + 15) / 16) * 16 + 64 + (size_t)MM_SK_DUPCAP * 4 + 16;
-}
-static FastGeom sketch_fast_geom(int K, int s, int maxLen, size_t tabBytes, bool sl20Built) {
-  FastGeom g;
-  // survivors the fast kernel aims for: s + 4.2 sqrt(s) (their count is ~Poisson, so s stays about 4 sigma away): fewer = less queue /
-  // table work and less LDS, more fragments redone by k_sketch_hard (measured, profiles/r02v_sketch_geometry.txt: 0.007 % of random
-  // fragments at s = 130, 0.008 % at 310, 0.02 % at 498, at 44 ns each).
-  g.wantFast = (int)(s + 4.2 * sqrt((double)s) + 0.999);
-  int n = maxLen - K + 1; if (n < 1) n = 1;
-  // positions per thread: 16, or 20 where that fills whole waves better (the workgroup's critical path is ceil(waves / 4 SIMDs) strips)
-  auto wavesFor = [&](int SL) { int st = (n + SL - 1) / SL; int w = (st + 63) / 64; return w < 1 ? 1 : (w > 16 ? 16 : w); };
-  g.SL = 16;
-  if (sl20Built && 20 + K - 1 <= 48) {
-    const int w16 = wavesFor(16), w20 = wavesFor(20);
-    const int c16 = ((w16 + 3) / 4) * 16, c20 = ((w20 + 3) / 4) * 20;
-    if (c20 < c16 || (c20 == c16 && w20 < w16)) g.SL = 20;
-  }
-  g.threads = wavesFor(g.SL) * 64;
-  const int nWaves = g.threads / 64;
-  // a wave queues the survivors of its 64 threads' strips: their expectation + qsig standard deviations; the table has htf slots per
-  // wanted survivor (load limit = 5/8 of them).  The kernel's table phases wait on LDS latency and are hidden by the other workgroups
-  // of the CU, whose number the LDS footprint decides (allocated in 1280-byte units out of 160 KB): the roomy geometry is kept unless a
-  // tighter one lets one more workgroup in (s = 130: 7 instead of 6, s = 310: 5 instead of 4, s = 498: 4 instead of 3 -- 49 -> 42 ms per
-  // 1.6 M fragments there).
-  int nStrips = (n + g.SL - 1) / g.SL; if (nStrips < 1) nStrips = 1;
-  const int passes = (nStrips + g.threads - 1) / g.threads;
-  double ex = 64.0 * passes * g.SL * (double)g.wantFast / (double)n; if (ex > g.wantFast) ex = g.wantFast;
-  auto shape = [&](double htf, double qsig) {
-    int HT = (int)(htf * g.wantFast + 63) / 64 * 64; if (HT < 256) HT = 256;
-    g.HT = HT;
-    g.QC = ((int)(ex + qsig * sqrt(ex) + 8.0) + 3) & ~3;
-    g.lds = sketch_fast_lds(tabBytes, maxLen, g.HT, MM_SK_PAD, g.QC, nWaves);
-    const size_t unit = 1280, alloc = (g.lds + unit - 1) / unit * unit;
-    return (int)((size_t)160 * 1024 / alloc);      // workgroups a CU holds
-  };
-  const double cand[3][2] = {{2.4, 6.0}, {2.2, 6.0}, {2.2, 5.0}};
-  int best = 0, bestWg = shape(cand[0][0], cand[0][1]);
-  for (int i = 1; i < 3; i++) { const int wg = shape(cand[i][0], cand[i][1]); if (wg > bestWg) { bestWg = wg; best = i; } }
-  (void)shape(cand[best][0], cand[best][1]);
-  return g;
-}
-// hard kernel's table: the load limit, 5/8 of it, stays >= 2 s (the window [s, limit] the cut must hit is an octave wide); no larger
-// than that needs, because its LDS sets how many listed fragments a CU works on at once (s = 130: 4 workgroups)
-static int sketch_ht_hard(int s) { const int w = (s * 16 + 4) / 5; return next_pow2(w < 1024 ? 1024 : w); }
-
-// How the two sketch kernels are run for (k, s, fragment length): the fast kernel when its geometry fits (LDS, and table slots that fit
-// the 13-bit field of its duplicate list), otherwise every fragment goes down the hard list; the hard kernel with its whole table in
-// LDS when that fits, otherwise with the first / last / strand-sum arrays spilled to HBM scratch and, if the power-of-two table still
-// does not fit, the smallest table that keeps its load limit (5/8) at 2 s.  ok == false: not even that fits (the message says why).
-struct SketchPlan { bool ok, useFast, spill, stream = false; FastGeom g; int HTH; size_t ldsFast, ldsHard; };
-static size_t sketch_hard_lds_spill(size_t tabBytes, int maxLen, int HT, int PAD) {
-  const size_t nW = (size_t)(maxLen + 15) / 16 + 3, nM = (size_t)(maxLen + 31) / 32 + 2;
-  const size_t NS = (size_t)HT + PAD, nOcc = NS / 64;
-  return tabBytes + ((nW * 4 + 15) / 16) * 16 + ((nM * 4 + 15) / 16) * 16 + NS * 8 + 2 * MM_SK_GUARD * 8 + nOcc * 8 + ((nOcc * 4 + 15) / 16) * 16 + 16;
-}
-static SketchPlan sketch_plan(int K, int s, int maxLen, size_t tabBytes, bool sl20Built) {
-  const size_t lim = 160 * 1024;
-  SketchPlan P;
-  P.g = sketch_fast_geom(K, s, maxLen, tabBytes, sl20Built);
-  P.ldsFast = P.g.lds;
-  P.useFast = P.ldsFast <= lim && P.g.HT + MM_SK_PAD <= 8192 && maxLen < (1 << 18);
-  P.HTH = sketch_ht_hard(s);
-  P.ldsHard = sketch_hard_lds(tabBytes, maxLen, P.HTH, MM_SK_PADH);
-  P.spill = P.ldsHard > lim;
-  if (P.spill) {
-    P.ldsHard = sketch_hard_lds_spill(tabBytes, maxLen, P.HTH, MM_SK_PADH);
-    if (P.ldsHard > lim) {                          // not a power of two then: load limit 5/8 HT >= 2 s
-      P.HTH = (((s * 16 + 4) / 5) + 63) / 64 * 64;
-      P.ldsHard = sketch_hard_lds_spill(tabBytes, maxLen, P.HTH, MM_SK_PADH);
-    }
-  }
-  if (P.ldsHard > lim) {                            // the staged fragment is what does not fit (a whole contig as one fragment under --noSplit):
-    P.stream = true;                                // the exact kernel reads its words from global memory instead
-    P.HTH = sketch_ht_hard(s);
-    P.ldsHard = sketch_hard_lds_spill(tabBytes, 0, P.HTH, MM_SK_PADH);
-    if (P.ldsHard > lim) { P.HTH = (((s * 16 + 4) / 5) + 63) / 64 * 64; P.ldsHard = sketch_hard_lds_spill(tabBytes, 0, P.HTH, MM_SK_PADH); }
-  }
-  P.ok = P.ldsHard <= lim;
-  return P;
-}
+// (sketch_fast_geom, sketch_ht_hard, sketch_plan -- how the two kernels are run for (k, s, fragment length) -- and the layouts that size
+// their LDS: mm_sketch_plan.h)
 
 // Parameter combinations the LDS-resident kernels cannot hold are refused when the context is created (not after the reference
 // index has been built): the sketch tables + a staged fragment of segLength bases.  (The L2 kernels hold every sketch of up to
 // MM_LDS_MAX_SKETCH entries in LDS, whatever the other parameters: mm_l2_plan.h asserts it.)
 int mm_check_params(const mm_params* p, std::string& err) {
   const int s = p->sketchSize, L = p->segLength;
-  const size_t tabBytes = (p->kmerSize >= 16 && p->kmerSize <= 32) ? sizeof(MMProdTables) : sizeof(MMTables);
-  const SketchPlan P = sketch_plan(p->kmerSize, s, L, tabBytes, false);
-  const size_t lim = 160 * 1024;
-  if (s > MM_LDS_MAX_SKETCH) {
+  const SketchParamCheck chk = sketch_check_params(p->kmerSize, s, L, MM_LDS_MAX_SKETCH, MM_MAX_SKETCH);
+  switch (chk.cls) {
+    case MM_SKP_FITS: return MM_OK;
     // no LDS kernel holds this sketch: the global-memory sketch kernel (mm_sketch_global.hip) and the literal L2 kernels take every
     // fragment -- exact, slow; the stock binary runs these sizes (--dense at segments of 100 kbp), so they run here too
     // ... and so does the index build: k_winnow_tiles (mm_winnow.hip) keeps the sketch of a reference window in LDS up to
     // MM_WINNOW_LDS_SKETCH entries and in HBM beyond
-    if (s > MM_MAX_SKETCH) {
+    case MM_SKP_BEYOND_LDS: return MM_OK;
+    case MM_SKP_BEYOND_MAX:
       err = "mm_create: sketchSize " + std::to_string(s) + " is beyond " + std::to_string(MM_MAX_SKETCH) + " (seeds are numbered in 16 bits by the literal mapping kernels)";
       return MM_ERR_ARG;
-    }
-    return MM_OK;
+    case MM_SKP_REFUSED: break;
   }
-  if (!P.ok) {
-    char b[400];
-    snprintf(b, sizeof b, "mm_create: segLength %d with sketchSize %d needs %zu bytes of LDS in the sketch kernel (table of the exact path, spilled form); a CU has %zu",
-             L, s, P.ldsHard, lim);
-    err = b; return MM_ERR_ARG;
-  }
-  return MM_OK;
+  char b[400];
+  snprintf(b, sizeof b, "mm_create: segLength %d with sketchSize %d needs %zu bytes of LDS in the sketch kernel (table of the exact path, spilled form); a CU has %zu",
+           L, s, chk.ldsBytes, (size_t)MM_SK_LDS_LIMIT);
+  err = b; return MM_ERR_ARG;
 }
 
 template <int K> struct MMHasSL20 { static constexpr bool value = (K >= 16 && K <= 21); };   // strips of 20 positions are built for these k-mer sizes
+
+// the strip-hasher tables for kmerSize K in c->dSketchTabs (kept until another k-mer size asks)
+template <int K>
+static int ensure_sketch_tables(mm_ctx* c) {
+  using Tabs = typename MMTabsFor<K>::type;
+  if (c->sketchTabsK == K) return MM_OK;
+  MM_HIP(c, c->dSketchTabs.ensure(sizeof(Tabs)));
+  hipLaunchKernelGGL((k_sketch_tables<K>), dim3(1), dim3(256), 0, c->stream, c->dSketchTabs.as<Tabs>());
+  MM_HIP(c, hipGetLastError());
+  c->sketchTabsK = K;
+  return MM_OK;
+}
 
 template <int K>
 static int launch_sketch_k(mm_ctx* c) {
@@ -805,12 +589,7 @@ static int launch_sketch_k(mm_ctx* c) {
   if (!plan.ok) { c->err = "fragment too long / sketch too large for the LDS-resident sketch kernel"; return MM_ERR_ARG; }
   int nStrips = (maxLen - K + 1 + 15) / 16; if (nStrips < 1) nStrips = 1;
   int threadsHard = ((nStrips + 63) / 64) * 64; if (threadsHard > 1024) threadsHard = 1024;
-  if (c->sketchTabsK != K) {
-    MM_HIP(c, c->dSketchTabs.ensure(sizeof(Tabs)));
-    hipLaunchKernelGGL((k_sketch_tables<K>), dim3(1), dim3(256), 0, c->stream, c->dSketchTabs.as<Tabs>());
-    MM_HIP(c, hipGetLastError());
-    c->sketchTabsK = K;
-  }
+  if (const int rc = ensure_sketch_tables<K>(c)) return rc;
   MM_HIP(c, hipMemsetAsync(c->dCounters.as<unsigned long long>() + MM_CW_SKETCH, 0, (size_t)(MM_CW_SKETCH_END - MM_CW_SKETCH) * 8, c->stream));
   unsigned long long* phaseStats = nullptr;
   if (c->env.sketchStats) { phaseStats = c->dCounters.as<unsigned long long>() + MM_CW_SKETCH_PHASES; MM_HIP(c, hipMemsetAsync(phaseStats, 0, (size_t)(MM_CW_SKETCH_PHASES_END - MM_CW_SKETCH_PHASES) * 8, c->stream)); }
@@ -873,14 +652,10 @@ static int launch_hash_only_k(mm_ctx* c, int reps, double* msAvg) {
   const int maxLen = c->maxFragLen;
   // the sketch kernel's geometry for these fragments: positions per thread, threads per workgroup, LDS per workgroup
   const FastGeom g = sketch_fast_geom(K, c->P.sketchSize, maxLen, sizeof(Tabs), MMHasSL20<K>::value);
-  const size_t need = sizeof(Tabs) + (((size_t)(maxLen + 15) / 16 + 4) * 4 + 15) / 16 * 16;
-  const size_t lds = (g.lds > need && g.lds <= 160 * 1024) ? g.lds : need;
-  if (c->sketchTabsK != K) {
-    MM_HIP(c, c->dSketchTabs.ensure(sizeof(Tabs)));
-    hipLaunchKernelGGL((k_sketch_tables<K>), dim3(1), dim3(256), 0, c->stream, c->dSketchTabs.as<Tabs>());
-    MM_HIP(c, hipGetLastError());
-    c->sketchTabsK = K;
-  }
+  // ... and where that claim cannot be made, what the kernel itself uses: the front of the carve, up to the end of the staged words
+  const size_t need = sketch_fast_layout(sizeof(Tabs), maxLen, g.HT, MM_SK_PAD, g.QC, g.threads / 64).sM;
+  const size_t lds = (g.lds > need && g.lds <= MM_SK_LDS_LIMIT) ? g.lds : need;
+  if (const int rc = ensure_sketch_tables<K>(c)) return rc;
   MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
   float total = 0;
   for (int r = 0; r <= reps; r++) {                 // launch 0 is a warm-up
@@ -913,30 +688,32 @@ extern "C" int mm_bench_hash_only(mm_ctx* c, int reps, double* msAvg) {
   }
 }
 
+// the sketch's output arrays, the hard list and the counter block, for nF fragments of s entries
+static int ensure_sketch_buffers(mm_ctx* c, size_t nF, size_t s) {
+  MM_HIP(c, c->dSkHash.ensure(nF * s * 8 + 64));
+  MM_HIP(c, c->dSkPos.ensure(nF * s * 8 + 64));
+  MM_HIP(c, c->dSkStrand.ensure(nF * s + 64));
+  MM_HIP(c, c->dSkCount.ensure(nF * 4 + 64));
+  MM_HIP(c, c->dHardList.ensure(nF * 4 + 64));
+  MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
+  return MM_OK;
+}
+
 int mm_launch_sketch(mm_ctx* c) {
   const size_t nF = c->nFrags, s = (size_t)c->P.sketchSize;
-  const size_t cF = mm_frag_cap(c, nF);               // (the largest batch the caller has announced: no reallocation when it comes)
   c->skLargeState = MM_SKL_STATE_KNOWN; c->skLargeFrags = c->skLargeUncut = 0;   // mm_sketch_large_counts: 0 / 0 unless k_sketch_large runs below
   if (s > MM_LDS_MAX_SKETCH) {
-    MM_HIP(c, c->dSkHash.ensure(nF * s * 8 + 64)); MM_HIP(c, c->dSkPos.ensure(nF * s * 8 + 64));
-    MM_HIP(c, c->dSkStrand.ensure(nF * s + 64)); MM_HIP(c, c->dSkCount.ensure(nF * 4 + 64));
-    MM_HIP(c, c->dHardList.ensure(nF * 4 + 64)); MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
+    if (const int rc = ensure_sketch_buffers(c, nF, s)) return rc;
     // no hard list here, and its length is read all the same (mm_pass_stats): the words every other sketch launch resets
     MM_HIP(c, hipMemsetAsync(c->dCounters.as<unsigned long long>() + MM_CW_SKETCH, 0, (size_t)(MM_CW_SKETCH_END - MM_CW_SKETCH) * 8, c->stream));
     return c->opt.sketchLarge ? mm_launch_sketch_large(c) : mm_launch_sketch_global(c);
   }
-  MM_HIP(c, c->dSkHash.ensure(cF * s * 8 + 64));
-  MM_HIP(c, c->dSkPos.ensure(cF * s * 8 + 64));
-  MM_HIP(c, c->dSkStrand.ensure(cF * s + 64));
-  MM_HIP(c, c->dSkCount.ensure(cF * 4 + 64));
-  MM_HIP(c, c->dHardList.ensure(cF * 4 + 64));
-  MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
+  // (for the largest batch the caller has announced: no reallocation when it comes)
+  if (const int rc = ensure_sketch_buffers(c, mm_frag_cap(c, nF), s)) return rc;
   if (nF == 0) return MM_OK;
   switch (c->P.kmerSize) {
 #define MM_CASE(KK) case KK: return launch_sketch_k<KK>(c);
-    MM_CASE(1) MM_CASE(2) MM_CASE(3) MM_CASE(4) MM_CASE(5) MM_CASE(6) MM_CASE(7) MM_CASE(8) MM_CASE(9) MM_CASE(10) MM_CASE(11) MM_CASE(12) MM_CASE(13) MM_CASE(14) MM_CASE(15) MM_CASE(16) MM_CASE(17) MM_CASE(18) MM_CASE(19) MM_CASE(20) MM_CASE(21) MM_CASE(22) MM_CASE(23) MM_CASE(24) MM_CASE(25) MM_CASE(26) MM_CASE(27) MM_CASE(28) MM_CASE(29) MM_CASE(30) MM_CASE(31) MM_CASE(32)
-    MM_CASE(33) MM_CASE(34) MM_CASE(35) MM_CASE(36) MM_CASE(37) MM_CASE(38) MM_CASE(39) MM_CASE(40) MM_CASE(41) MM_CASE(42) MM_CASE(43) MM_CASE(44) MM_CASE(45) MM_CASE(46) MM_CASE(47) MM_CASE(48)
-    MM_CASE(49) MM_CASE(50) MM_CASE(51) MM_CASE(52) MM_CASE(53) MM_CASE(54) MM_CASE(55) MM_CASE(56) MM_CASE(57) MM_CASE(58) MM_CASE(59) MM_CASE(60) MM_CASE(61) MM_CASE(62) MM_CASE(63) MM_CASE(64)
+    MM_FOR_EACH_K(MM_CASE)
 #undef MM_CASE
     default: c->err = "kmerSize outside 1..64"; return MM_ERR_ARG;
   }

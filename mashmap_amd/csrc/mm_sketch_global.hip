@@ -11,6 +11,7 @@
 // combinations far from the reference's defaults, so that they run instead of being refused.
 #include "mm_internal.h"
 #include "mm_device.h"
+#include "mm_sketch_dev.h"
 #include <algorithm>
 
 namespace {
@@ -40,17 +41,15 @@ __device__ uint64_t g_murmur(const uint32_t* __restrict__ bases2, int64_t b0, in
   return h1 + h2;
 }
 
-// one entry of the sort: the hash, then position << 1 | (forward strand is the smaller one)
-struct GEnt { uint64_t h; uint32_t m; uint32_t pad; };
-__device__ __forceinline__ bool g_less(const GEnt& a, const GEnt& b) { return a.h != b.h ? a.h < b.h : a.m < b.m; }
+// (the entry of the sort, SkEnt, its order, the compaction and the emission: mm_sketch_dev.h, shared with k_sketch_large)
 
 __global__ void __launch_bounds__(1024)
 k_sketch_global(int nF, int K, int s, int64_t slice /* entries per workgroup, a power of two >= the longest fragment's positions */,
                 const uint32_t* __restrict__ bases2, const uint32_t* __restrict__ nmask, const DFrag* __restrict__ frags, const uint32_t* __restrict__ readHasN,
-                GEnt* __restrict__ scratch, uint64_t* __restrict__ skHash, int2* __restrict__ skPos, int8_t* __restrict__ skStrand, uint32_t* __restrict__ skCount) {
+                SkEnt* __restrict__ scratch, uint64_t* __restrict__ skHash, int2* __restrict__ skPos, int8_t* __restrict__ skStrand, uint32_t* __restrict__ skCount) {
   __shared__ int sCount[1024];
   __shared__ int sTotal;
-  GEnt* e = scratch + (size_t)blockIdx.x * (size_t)slice;
+  SkEnt* e = scratch + (size_t)blockIdx.x * (size_t)slice;
   const int tid = threadIdx.x, nthr = blockDim.x;
   for (int f = blockIdx.x; f < nF; f += gridDim.x) {
     const DFrag fr = frags[f];
@@ -60,8 +59,7 @@ k_sketch_global(int nF, int K, int s, int64_t slice /* entries per workgroup, a 
     // A cut first: only hashes below T go into the sort, T placed where s + 5 sqrt(s) + 64 of the ~2n uniform strand hashes are expected
     // (any T gives the exact sketch as long as s distinct hashes survive -- counted below; a fragment where they do not, a repeat, is done
     // again without a cut).  At sketchSize 9 998 over 100 kbp segments that is a sort of 16 384 entries instead of 131 072.
-    const double want = (double)s + 5.0 * sqrt((double)s) + 64.0;
-    uint64_t T = want >= (double)n ? MM_HASH_MAX : (uint64_t)(want / (2.0 * (double)n) * 18446744073709551616.0);
+    uint64_t T = mm_sketch_cut(s, n);
     int64_t N2 = 2;
     for (int attempt = 0; attempt < 2; attempt++) {
     // ---- 1. hashes below the cut, compacted (wave-aggregated cursor) ----
@@ -69,26 +67,22 @@ k_sketch_global(int nF, int K, int s, int64_t slice /* entries per workgroup, a 
     __syncthreads();
     for (int64_t p0 = 0; p0 < n; p0 += nthr) {
       const int64_t p = p0 + tid;
-      GEnt x; x.h = MM_HASH_MAX; x.m = 0xFFFFFFFFu; x.pad = 0;
+      uint64_t h = MM_HASH_MAX; uint32_t m32 = 0xFFFFFFFFu;
       bool keep = false;
       if (p < n) {
         bool ok = true;
         if (hasN) for (int i = 0; i < K && ok; i++) { const int64_t b = fr.base + p + i; if ((nmask[b >> 5] >> (int)(b & 31)) & 1u) ok = false; }
         if (ok) {
           const uint64_t hf = g_murmur(bases2, fr.base + p, K, false), hr = g_murmur(bases2, fr.base + p, K, true);
-          if (hf != hr) { x.h = hf < hr ? hf : hr; x.m = ((uint32_t)p << 1) | (hf < hr ? 1u : 0u); keep = T == MM_HASH_MAX || x.h < T; }
+          if (hf != hr) { h = hf < hr ? hf : hr; m32 = ((uint32_t)p << 1) | (hf < hr ? 1u : 0u); keep = T == MM_HASH_MAX || h < T; }
         }
       }
-      const uint64_t m = mm_ballot(keep);
-      int base = 0;
-      if (m && mm_lane() == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(&sTotal, (int)__popcll(m));
-      if (m) base = __shfl(base, (int)__builtin_ctzll(m));
-      if (keep) e[base + (int)mm_popc_below(m)] = x;
+      mm_sk_append(e, &sTotal, keep, h, m32);
     }
     __syncthreads();
     const int nSurv = sTotal;
     N2 = 2; while (N2 < nSurv) N2 <<= 1;
-    for (int64_t p = nSurv + tid; p < N2; p += nthr) { GEnt x; x.h = MM_HASH_MAX; x.m = 0xFFFFFFFFu; x.pad = 0; e[p] = x; }
+    for (int64_t p = nSurv + tid; p < N2; p += nthr) e[p] = mm_sk_ent_padding();
     __threadfence_block();
     __syncthreads();
     // ---- 2. bitonic sort, ascending by (hash, position) ----
@@ -97,36 +91,17 @@ k_sketch_global(int nF, int K, int s, int64_t slice /* entries per workgroup, a 
         for (int64_t i = tid; i < N2; i += nthr) {
           const int64_t q = i ^ j;
           if (q > i) {
-            const GEnt a = e[i], b = e[q];
-            if (g_less(b, a) == ((i & k2) == 0)) { e[i] = b; e[q] = a; }
+            const SkEnt a = e[i], b = e[q];
+            if (mm_sk_ent_less(b, a) == ((i & k2) == 0)) { e[i] = b; e[q] = a; }
           }
         }
         __threadfence_block();
         __syncthreads();
       }
-    // ---- 3. distinct hashes in order: every thread owns a contiguous chunk; a run belongs to the chunk its first entry lies in ----
-    const int64_t chunk = (N2 + nthr - 1) / nthr;
-    const int64_t c0 = (int64_t)tid * chunk, c1 = c0 + chunk < N2 ? c0 + chunk : N2;
-    int mine = 0;
-    for (int64_t i = c0; i < c1; i++) { const uint64_t h = e[i].h; if (h != MM_HASH_MAX && (i == 0 || e[i - 1].h != h)) mine++; }
-    sCount[tid] = mine;
-    __syncthreads();
-    if (tid == 0) { int acc = 0; for (int t = 0; t < nthr; t++) { const int v = sCount[t]; sCount[t] = acc; acc += v; } sTotal = acc; }
-    __syncthreads();
-    if (sTotal < s && T != MM_HASH_MAX) { T = MM_HASH_MAX; __syncthreads(); continue; }     // fewer than s distinct hashes below the cut: once more without one
-    int rank = sCount[tid];
-    for (int64_t i = c0; i < c1 && rank < s; i++) {
-      const uint64_t h = e[i].h;
-      if (h == MM_HASH_MAX || (i != 0 && e[i - 1].h == h)) continue;
-      int first = (int)(e[i].m >> 1), last = first, sum = 0;
-      for (int64_t r = i; r < N2 && e[r].h == h; r++) { last = (int)(e[r].m >> 1); sum += (e[r].m & 1u) ? 1 : -1; }
-      const size_t o = (size_t)f * s + rank;
-      skHash[o] = h; skPos[o] = make_int2(first, last);
-      const int16_t acc = (int16_t)sum;                                    // the reference accumulates the strand in an int16 (base_types.hpp:24)
-      skStrand[o] = acc > 0 ? 1 : (acc == 0 ? 0 : -1);
-      rank++;
+    // ---- 3. one entry per distinct hash in order, the s smallest: mm_sk_emit_sorted ----
+    if (mm_sk_emit_sorted(e, N2, s, T != MM_HASH_MAX, f, sCount, &sTotal, skHash, skPos, skStrand, skCount)) {
+      T = MM_HASH_MAX; __syncthreads(); continue;     // fewer than s distinct hashes below the cut: once more without one
     }
-    if (tid == 0) skCount[f] = (uint32_t)(sTotal < s ? sTotal : s);
     __syncthreads();
     break;
     }  // attempt
@@ -139,13 +114,13 @@ k_sketch_global(int nF, int K, int s, int64_t slice /* entries per workgroup, a 
 int mm_launch_sketch_global(mm_ctx* c) {
   const int nF = (int)c->nFrags, K = c->P.kmerSize, s = c->P.sketchSize;
   if (nF == 0) return MM_OK;
-  int64_t slice = 2; while (slice < c->maxFragLen) slice <<= 1;
-  // as many workgroups as ~8 GiB of scratch allow, at most 1024 (a CU runs two of them at a time)
-  int grid = (int)std::min<int64_t>(std::min<int64_t>(nF, 1024), std::max<int64_t>(1, ((int64_t)8 << 30) / (slice * (int64_t)sizeof(GEnt))));
-  MM_HIP(c, c->dSketchSpill.ensure((size_t)grid * (size_t)slice * sizeof(GEnt) + 64));
+  const int64_t slice = sketch_scratch_slice(c->maxFragLen);
+  // as many workgroups as the scratch cap allows, at most 1024 (a CU runs two of them at a time)
+  int grid = (int)std::min<int64_t>(std::min<int64_t>(nF, 1024), sketch_scratch_grid_cap(slice, sizeof(SkEnt)));
+  MM_HIP(c, c->dSketchSpill.ensure((size_t)grid * (size_t)slice * sizeof(SkEnt) + 64));
   KernelTimer t(c, MM_K_SKETCH_HARD);
   hipLaunchKernelGGL(k_sketch_global, dim3(grid), dim3(1024), 0, c->stream, nF, K, s, slice, c->dBases2.as<uint32_t>(), c->dNmask.as<uint32_t>(), c->dFrags.as<DFrag>(),
-                     c->dReadHasN.as<uint32_t>(), c->dSketchSpill.as<GEnt>(), c->dSkHash.as<uint64_t>(), c->dSkPos.as<int2>(), c->dSkStrand.as<int8_t>(),
+                     c->dReadHasN.as<uint32_t>(), c->dSketchSpill.as<SkEnt>(), c->dSkHash.as<uint64_t>(), c->dSkPos.as<int2>(), c->dSkStrand.as<int8_t>(),
                      c->dSkCount.as<uint32_t>());
   MM_HIP(c, hipGetLastError());
   return MM_OK;

@@ -10,24 +10,22 @@
 // same workgroup without one.
 #include "mm_internal.h"
 #include "mm_device.h"
+#include "mm_sketch_dev.h"
 #include "mm_sketch_large_plan.h"
 #include <algorithm>
 
 namespace {
 
-// one entry of the sort: the hash, then position << 1 | (forward strand is the smaller one) -- GEnt of mm_sketch_global.hip
-struct __attribute__((aligned(16))) LEnt { uint64_t h; uint32_t m; uint32_t pad; };
-static_assert(sizeof(LEnt) == MM_SKL_ENTRY_BYTES, "mm_sketch_large_plan.h sizes the tile by this entry");
+// (the entry of the sort, SkEnt, its order, the compaction and the emission: mm_sketch_dev.h, shared with k_sketch_global)
+static_assert(sizeof(SkEnt) == MM_SKL_ENTRY_BYTES, "mm_sketch_large_plan.h sizes the tile by this entry");
 static_assert(sizeof(MMProdTables) == MM_SKL_TABLE_BYTES && sizeof(MMTables) <= MM_SKL_TABLE_BYTES, "mm_sketch_large_plan.h sums the LDS with the larger table");
 static_assert(MM_SKL_HASH_MAX == MM_HASH_MAX, "one value for `no cut`");
-__device__ __forceinline__ bool l_less(const LEnt& a, const LEnt& b) { return a.h != b.h ? a.h < b.h : a.m < b.m; }
-__device__ __forceinline__ LEnt l_padding() { LEnt x; x.h = MM_HASH_MAX; x.m = 0xFFFFFFFFu; x.pad = 0; return x; }
 
 template <int K>
 __global__ void __launch_bounds__(1024)
 k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of two >= the longest fragment's positions */,
                const uint32_t* __restrict__ bases2, const uint32_t* __restrict__ nmask, const DFrag* __restrict__ frags, const uint32_t* __restrict__ readHasN,
-               LEnt* scratch, uint64_t* __restrict__ skHash, int2* __restrict__ skPos, int8_t* __restrict__ skStrand, uint32_t* __restrict__ skCount,
+               SkEnt* scratch, uint64_t* __restrict__ skHash, int2* __restrict__ skPos, int8_t* __restrict__ skStrand, uint32_t* __restrict__ skCount,
                unsigned long long* __restrict__ sketchWords /* dCounters + MM_CW_SKETCH */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int sCount[1024];
@@ -35,11 +33,11 @@ k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of
   static_assert(sizeof(sCount) + 16 == MM_SKL_STATIC_BYTES, "mm_sketch_large_plan.h sums the LDS with the counts and 16 bytes for the cursor");
   using Tabs = typename MMTabsFor<K>::type;
   Tabs* tabs = (Tabs*)smem;
-  LEnt* tileE = (LEnt*)(smem + MM_SKL_TABLE_BYTES);                         // MM_SKL_TILE entries
+  SkEnt* tileE = (SkEnt*)(smem + MM_SKL_TABLE_BYTES);                         // MM_SKL_TILE entries
   const int tid = threadIdx.x, nthr = blockDim.x;
   mm_tables_init<K>(*tabs, tid, nthr);                                      // once per workgroup: every fragment it takes hashes through them
   __syncthreads();
-  LEnt* e = scratch + (size_t)blockIdx.x * (size_t)slice;
+  SkEnt* e = scratch + (size_t)blockIdx.x * (size_t)slice;
   for (int f = blockIdx.x; f < nF; f += gridDim.x) {
     const DFrag fr = frags[f];
     const int n = fr.len - K + 1;
@@ -49,14 +47,8 @@ k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of
     // neighbouring strips share their words in the caches; the run-off words behind the batch are there and zero)
     const int64_t gw0 = fr.base >> 4; const int gsh = (int)(fr.base & 15) * 2;
     const int64_t gm0 = fr.base >> 5; const int gmsh = (int)(fr.base & 31);
-    auto wordAt = [&](int j) -> uint32_t {
-      const uint32_t a = bases2[gw0 + j], b = bases2[gw0 + j + 1];
-      return gsh ? __builtin_amdgcn_alignbit(b, a, gsh) : a;
-    };
-    auto maskAt = [&](int j) -> uint32_t {
-      const uint32_t a = nmask[gm0 + j], b = nmask[gm0 + j + 1];
-      return gmsh ? __builtin_amdgcn_alignbit(b, a, gmsh) : a;
-    };
+    auto wordAt = [&](int j) -> uint32_t { return mm_sk_word_at(bases2, gw0, gsh, j); };
+    auto maskAt = [&](int j) -> uint32_t { return mm_sk_word_at(nmask, gm0, gmsh, j); };
     // any T gives the exact sketch as long as s distinct hashes survive it -- counted below; a fragment where they do not, a repeat, is
     // done again without a cut
     uint64_t T = mm_sketch_cut(s, n);
@@ -73,23 +65,12 @@ k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of
       // bit j: position strip*16+j exists and its k-mer holds no N
       const int rem = n - strip * 16;
       uint32_t ok = !live ? 0u : rem >= 16 ? 0xFFFFu : ((1u << rem) - 1u);
-      if (hasN) {
-        const uint64_t m64 = (uint64_t)maskAt(strip >> 1) | ((uint64_t)maskAt((strip >> 1) + 1) << 32);
-        if constexpr (MMWideK<K>::value) {
-          const uint64_t h64 = (uint64_t)maskAt((strip >> 1) + 2) | ((uint64_t)maskAt((strip >> 1) + 3) << 32);
-          const int sh = (strip & 1) * 16;
-          ok &= ~mm_window_or_wide<K>(sh ? ((m64 >> sh) | (h64 << (64 - sh))) : m64, sh ? (h64 >> sh) : h64);
-        } else ok &= ~(uint32_t)mm_window_or<K>(m64 >> ((strip & 1) * 16));
-      }
+      if (hasN) ok &= ~mm_sk_strip_has_n<K>(strip, maskAt);
       auto onPos = [&](int j, uint64_t hf, uint64_t hr) {
         const uint64_t h = hf < hr ? hf : hr;
         bool keep = false;                          // no N, the two strands differ (commonFunc.hpp:207-240), below the cut
         if ((ok & (1u << j)) != 0) { if (hf != hr) { if (allPass || h < T) keep = true; } }
-        const uint64_t m = mm_ballot(keep);
-        int base = 0;
-        if (m && mm_lane() == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(&sTotal, (int)__popcll(m));
-        if (m) base = __shfl(base, (int)__builtin_ctzll(m));
-        if (keep) { LEnt x; x.h = h; x.m = ((uint32_t)(strip * 16 + j) << 1) | (hf < hr ? 1u : 0u); x.pad = 0; e[base + (int)mm_popc_below(m)] = x; }
+        mm_sk_append(e, &sTotal, keep, h, ((uint32_t)(strip * 16 + j) << 1) | (hf < hr ? 1u : 0u));
       };
       if constexpr (MMWideK<K>::value) {
         uint32_t ww[MMWideK<K>::NW];
@@ -102,7 +83,7 @@ k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of
     const int nSurv = sTotal;
     // ---- 2. padded to a power of two (N2 <= slice: the slice is one, and nSurv <= slice) and sorted ascending by (hash, position) ----
     const int64_t N2 = mm_skl_n2(nSurv);
-    for (int64_t p = nSurv + tid; p < N2; p += nthr) e[p] = l_padding();
+    for (int64_t p = nSurv + tid; p < N2; p += nthr) e[p] = mm_sk_ent_padding();
     __threadfence_block();
     __syncthreads();
     const int TL = (int)(N2 < MM_SKL_TILE ? N2 : MM_SKL_TILE);               // entries of a tile: TL divides N2, so a tile never reaches past N2
@@ -110,8 +91,8 @@ k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of
       [&](int64_t k2, int64_t j) {                                            // one sweep through HBM; i < q = i + j < N2
         for (int64_t p = tid; p < (N2 >> 1); p += nthr) {
           const int64_t i = mm_skl_pair_low(p, j), q = mm_skl_partner(i, j);
-          const LEnt a = e[i], b = e[q];
-          if (mm_skl_swaps(l_less(b, a), i, k2)) { e[i] = b; e[q] = a; }
+          const SkEnt a = e[i], b = e[q];
+          if (mm_skl_swaps(mm_sk_ent_less(b, a), i, k2)) { e[i] = b; e[q] = a; }
         }
         __threadfence_block();
         __syncthreads();
@@ -124,8 +105,8 @@ k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of
           mm_skl_tile_steps(k2lo, k2hi, MM_SKL_TILE, [&](int64_t k2, int64_t j) {
             for (int p = tid; p < (TL >> 1); p += nthr) {
               const int i = (int)mm_skl_pair_low(p, j), q = (int)mm_skl_partner(i, j);   // q = i + j < TL: j < TL
-              const LEnt a = tileE[i], b = tileE[q];
-              if (mm_skl_swaps(l_less(b, a), t0 + i, k2)) { tileE[i] = b; tileE[q] = a; }
+              const SkEnt a = tileE[i], b = tileE[q];
+              if (mm_skl_swaps(mm_sk_ent_less(b, a), t0 + i, k2)) { tileE[i] = b; tileE[q] = a; }
             }
             __syncthreads();
           });
@@ -134,30 +115,11 @@ k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of
         __threadfence_block();
         __syncthreads();
       });
-    // ---- 3. distinct hashes in order: every thread owns a contiguous chunk; a run belongs to the chunk its first entry lies in ----
-    const int64_t chunk = (N2 + nthr - 1) / nthr;
-    const int64_t c0 = (int64_t)tid * chunk < N2 ? (int64_t)tid * chunk : N2, c1 = c0 + chunk < N2 ? c0 + chunk : N2;
-    int mine = 0;
-    for (int64_t i = c0; i < c1; i++) { const uint64_t h = e[i].h; if (h != MM_HASH_MAX && (i == 0 || e[i - 1].h != h)) mine++; }
-    sCount[tid] = mine;
-    __syncthreads();
-    if (tid == 0) { int acc = 0; for (int t = 0; t < nthr; t++) { const int v = sCount[t]; sCount[t] = acc; acc += v; } sTotal = acc; }
-    __syncthreads();
-    if (sTotal < s && T != MM_HASH_MAX) { T = MM_HASH_MAX; __syncthreads(); continue; }     // fewer than s distinct hashes below the cut: once more without one
-    int rank = sCount[tid];
-    for (int64_t i = c0; i < c1 && rank < s; i++) {
-      const uint64_t h = e[i].h;
-      if (h == MM_HASH_MAX || (i != 0 && e[i - 1].h == h)) continue;
-      int first = (int)(e[i].m >> 1), last = first, sum = 0;
-      for (int64_t r = i; r < N2 && e[r].h == h; r++) { last = (int)(e[r].m >> 1); sum += (e[r].m & 1u) ? 1 : -1; }
-      const size_t o = (size_t)f * s + rank;
-      skHash[o] = h; skPos[o] = make_int2(first, last);
-      const int16_t acc = (int16_t)sum;                                    // the reference accumulates the strand in an int16 (base_types.hpp:24)
-      skStrand[o] = acc > 0 ? 1 : (acc == 0 ? 0 : -1);
-      rank++;
+    // ---- 3. one entry per distinct hash in order, the s smallest: mm_sk_emit_sorted ----
+    if (mm_sk_emit_sorted(e, N2, s, T != MM_HASH_MAX, f, sCount, &sTotal, skHash, skPos, skStrand, skCount)) {
+      T = MM_HASH_MAX; __syncthreads(); continue;     // fewer than s distinct hashes below the cut: once more without one
     }
     if (tid == 0) {
-      skCount[f] = (uint32_t)(sTotal < s ? sTotal : s);
       atomicAdd(&sketchWords[MM_SKW_LARGE_FRAGS], 1ull);
       if (T == MM_HASH_MAX) atomicAdd(&sketchWords[MM_SKW_LARGE_UNCUT], 1ull);
     }
@@ -170,22 +132,22 @@ k_sketch_large(int nF, int s, int64_t slice /* entries per workgroup, a power of
 template <int K>
 int launch_sketch_large_k(mm_ctx* c) {
   const int nF = (int)c->nFrags, s = c->P.sketchSize;
-  int64_t slice = 2; while (slice < c->maxFragLen) slice <<= 1;
-  const size_t lds = (size_t)MM_SKL_TABLE_BYTES + (size_t)MM_SKL_TILE * sizeof(LEnt);
+  const int64_t slice = sketch_scratch_slice(c->maxFragLen);
+  const size_t lds = (size_t)MM_SKL_TABLE_BYTES + (size_t)MM_SKL_TILE * sizeof(SkEnt);
   auto kern = k_sketch_large<K>;
   MM_HIP(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // as many workgroups as ~8 GiB of scratch allow, and no more than the device holds at once at this kernel's residency
+  // as many workgroups as the scratch cap allows, and no more than the device holds at once at this kernel's residency
   if (!c->chainCUs) { int cus = 0; MM_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device)); c->chainCUs = cus > 0 ? cus : 1; }
   int perCU = 0;
   MM_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void*)kern, 1024, lds));
   if (perCU < 1) perCU = 1;
-  const int grid = (int)std::min<int64_t>(std::min<int64_t>(nF, (int64_t)c->chainCUs * perCU), std::max<int64_t>(1, ((int64_t)8 << 30) / (slice * (int64_t)sizeof(LEnt))));
-  MM_HIP(c, c->dSketchSpill.ensure((size_t)grid * (size_t)slice * sizeof(LEnt) + 64));
+  const int grid = (int)std::min<int64_t>(std::min<int64_t>(nF, (int64_t)c->chainCUs * perCU), sketch_scratch_grid_cap(slice, sizeof(SkEnt)));
+  MM_HIP(c, c->dSketchSpill.ensure((size_t)grid * (size_t)slice * sizeof(SkEnt) + 64));
   unsigned long long* words = c->dCounters.as<unsigned long long>() + MM_CW_SKETCH;     // reset by mm_launch_sketch
   {
     KernelTimer t(c, MM_K_SKETCH_HARD);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, c->stream, nF, s, slice, c->dBases2.as<uint32_t>(), c->dNmask.as<uint32_t>(), c->dFrags.as<DFrag>(),
-                       c->dReadHasN.as<uint32_t>(), c->dSketchSpill.as<LEnt>(), c->dSkHash.as<uint64_t>(), c->dSkPos.as<int2>(), c->dSkStrand.as<int8_t>(),
+                       c->dReadHasN.as<uint32_t>(), c->dSketchSpill.as<SkEnt>(), c->dSkHash.as<uint64_t>(), c->dSkPos.as<int2>(), c->dSkStrand.as<int8_t>(),
                        c->dSkCount.as<uint32_t>(), words);
     MM_HIP(c, hipGetLastError());
   }
@@ -207,10 +169,7 @@ int mm_launch_sketch_large(mm_ctx* c) {
   if (!c->skLargeDone) MM_HIP(c, hipEventCreateWithFlags(&c->skLargeDone, hipEventDisableTiming));
   switch (c->P.kmerSize) {
 #define MM_CASE(KK) case KK: return launch_sketch_large_k<KK>(c);
-    MM_CASE(1) MM_CASE(2) MM_CASE(3) MM_CASE(4) MM_CASE(5) MM_CASE(6) MM_CASE(7) MM_CASE(8) MM_CASE(9) MM_CASE(10) MM_CASE(11) MM_CASE(12) MM_CASE(13) MM_CASE(14) MM_CASE(15) MM_CASE(16)
-    MM_CASE(17) MM_CASE(18) MM_CASE(19) MM_CASE(20) MM_CASE(21) MM_CASE(22) MM_CASE(23) MM_CASE(24) MM_CASE(25) MM_CASE(26) MM_CASE(27) MM_CASE(28) MM_CASE(29) MM_CASE(30) MM_CASE(31) MM_CASE(32)
-    MM_CASE(33) MM_CASE(34) MM_CASE(35) MM_CASE(36) MM_CASE(37) MM_CASE(38) MM_CASE(39) MM_CASE(40) MM_CASE(41) MM_CASE(42) MM_CASE(43) MM_CASE(44) MM_CASE(45) MM_CASE(46) MM_CASE(47) MM_CASE(48)
-    MM_CASE(49) MM_CASE(50) MM_CASE(51) MM_CASE(52) MM_CASE(53) MM_CASE(54) MM_CASE(55) MM_CASE(56) MM_CASE(57) MM_CASE(58) MM_CASE(59) MM_CASE(60) MM_CASE(61) MM_CASE(62) MM_CASE(63) MM_CASE(64)
+    MM_FOR_EACH_K(MM_CASE)
 #undef MM_CASE
     default: c->err = "kmerSize outside 1..64"; return MM_ERR_ARG;
   }

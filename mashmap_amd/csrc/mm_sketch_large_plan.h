@@ -7,6 +7,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "mm_sketch_plan.h"
 
 #ifdef __HIPCC__
 #define MM_SKL_HD __host__ __device__
@@ -14,16 +15,12 @@
 #define MM_SKL_HD
 #endif
 
-#define MM_SKL_HASH_MAX 0xFFFFFFFFFFFFFFFFULL   // MM_HASH_MAX of mm_device.h: "no cut", and the hash of a padding entry
+#define MM_SKL_HASH_MAX MM_SK_HASH_MAX          // MM_HASH_MAX of mm_device.h: "no cut", and the hash of a padding entry
 
 // ---- the cut ------------------------------------------------------------------------------------------------------------------------
 // Only hashes below T go into the sort, T placed where s + 5 sqrt(s) + 64 of the ~2n uniform strand hashes of a fragment of n k-mer
-// positions are expected; MM_SKL_HASH_MAX = no cut, when that many are all there are.  The expression of k_sketch_global, term by term.
-MM_SKL_HD inline double mm_sketch_want(int s) { return (double)s + 5.0 * sqrt((double)s) + 64.0; }
-MM_SKL_HD inline uint64_t mm_sketch_cut(int s, int n) {
-  const double want = mm_sketch_want(s);
-  return want >= (double)n ? MM_SKL_HASH_MAX : (uint64_t)(want / (2.0 * (double)n) * 18446744073709551616.0);
-}
+// positions are expected; MM_SKL_HASH_MAX = no cut, when that many are all there are: mm_sketch_want / mm_sketch_cut of
+// mm_sketch_plan.h, which k_sketch_global calls too.
 
 // ---- tile and sort geometry -------------------------------------------------------------------------------------------------------------
 #define MM_SKL_TILE 4096                        // entries of the sort one tile holds in LDS (a power of two)

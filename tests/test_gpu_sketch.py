@@ -91,6 +91,35 @@ def test_sketch_parameter_grid(oracle, k, s, L):
     _check(oracle, reads, k, s, L)
 
 
+@pytest.mark.parametrize("k,L", [(19, 5000), (16, 1000), (21, 5000), (19, 19)])
+def test_hash_only_runs_at_the_fast_kernels_geometry(oracle, k, L):
+    """mm_bench_hash_only, the yardstick bench.py divides the sketch kernel by: k_hash_only takes its threads and positions per thread from
+    sketch_fast_geom and its LDS from the front of the fast kernel's layout (strips of 20 at (19, 5000) and (21, 5000), of 16 at the others;
+    (19, 19): a single k-mer position per fragment).  It writes nothing: the sketch of the same context is the oracle's afterwards."""
+    from mashmap_amd import capi
+    s = 130
+    reads = [U.random_dna(300 + i, L) for i in range(8)] + [U.random_dna(299, k - 1)]      # the last one is no fragment
+    ctx = capi.Context(k=k, segLength=L, sketchSize=s)
+    nF = ctx.reads_upload(reads)
+    ms = ctx.bench_hash_only(1)
+    assert np.isfinite(ms) and ms > 0
+    got, cnt = ctx.sketch()
+    exp = _expect(oracle, reads, k, s, L)
+    assert nF == len(exp) == 8
+    for f in range(nF):
+        assert [(int(x["hash"]), int(x["wpos"]), int(x["wpos_end"]), int(x["seqId"]), int(x["strand"])) for x in got[f, :cnt[f]]] == exp[f]
+    ctx.close()
+
+
+def test_hash_only_is_refused_at_other_kmer_sizes():
+    from mashmap_amd import capi
+    ctx = capi.Context(k=20, segLength=1000, sketchSize=60)
+    ctx.reads_upload([U.random_dna(1, 1000)])
+    with pytest.raises(capi.MashmapError, match="mm_bench_hash_only: built for k = 16, 19, 21"):
+        ctx.bench_hash_only(1)
+    ctx.close()
+
+
 def test_sketch_many_hard_fragments(oracle):
     """a batch in which a large share of the fragments leaves the fast kernel (satellites: 171 distinct k-mers; N runs; tandem repeats):
     the device-resident hard list holds tens of thousands of fragments, every one of them must still come out exact"""

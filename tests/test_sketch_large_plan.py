@@ -46,7 +46,13 @@ def test_the_round_count_is_the_one_design_md_states(report):
 
 def test_the_cut_is_the_global_kernels(report):
     assert any(l.startswith("ok cut ") for l in report), report[-5:]
-    # ... whose expression still stands in k_sketch_global, which the header restates
+    # ... and k_sketch_global calls the function the sweep ran, instead of spelling the expression beside it
     src = open(os.path.join(ROOT, "mashmap_amd", "csrc", "mm_sketch_global.hip")).read()
-    assert "const double want = (double)s + 5.0 * sqrt((double)s) + 64.0;" in src
-    assert "want >= (double)n ? MM_HASH_MAX : (uint64_t)(want / (2.0 * (double)n) * 18446744073709551616.0)" in src
+    assert "uint64_t T = mm_sketch_cut(s, n);" in src
+    assert "sqrt((double)" not in src and "18446744073709551616" not in src and "5.0 *" not in src
+    large = open(os.path.join(ROOT, "mashmap_amd", "csrc", "mm_sketch_large.hip")).read()
+    assert "uint64_t T = mm_sketch_cut(s, n);" in large and "sqrt((double)" not in large and "18446744073709551616" not in large
+    # one definition of it in the sources
+    csrc = os.path.join(ROOT, "mashmap_amd", "csrc")
+    defs = [f for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip")) and "uint64_t mm_sketch_cut(int s, int n) {" in open(os.path.join(csrc, f)).read()]
+    assert defs == ["mm_sketch_plan.h"]
