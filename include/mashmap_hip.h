@@ -380,7 +380,7 @@ int mm_mappings_device(const mm_ctx* ctx, const mm_mapping** dMappings, size_t* 
  * sketchSize + 1, the stride of the replay tables; mm_stat_identity_table fills it with the host's own expression).
  * mm_chain_reads runs the stage on the context's stream and waits once, at its end, for the four counts.  MM_ERR_STATE, with the reason
  * in mm_last_error: nothing mapped or no replay tables; mm_set_chain_tables not called; MM_FLAG_SKIP_PREFIX (its filter runs group by
- * group); MM_FLAG_NO_SPLIT; sketchSize above MM_CHAIN_MAX_SKETCH (the identity table would pass 16 MB); a record that names a sketch
+ * group) and MM_FLAG_NO_SPLIT, unless MM_OPT_CHAIN_MODES is set; sketchSize above MM_CHAIN_MAX_SKETCH (the identity table would pass 16 MB); a record that names a sketch
  * size or shared count outside the identity table ("corrupt record": an error, never a hand-over -- the 16-record limit is the single
  * hand-over cause).  An empty batch, or one
  * without records, is MM_OK with zero counts.
@@ -389,6 +389,16 @@ int mm_mappings_device(const mm_ctx* ctx, const mm_mapping** dMappings, size_t* 
  * the handed-over reads', read-major, in their original order.  The device addresses are valid until the next mm_chain_reads or map call.
  * mm_chain_long_counts: *offered = reads of the batch with more than MM_CHAIN_MAX_RECORDS records, *finished = those of them
  * k_chain_reads_long wrote rows for (0 without MM_OPT_CHAIN_LONG); MM_ERR_STATE under the conditions of mm_chain_counts.
+ * With MM_OPT_CHAIN_MODES (below) the two refusals by flag fall away: under MM_FLAG_SKIP_PREFIX filterByGroup runs reference group by
+ * reference group, under MM_FLAG_NO_SPLIT no read is split.  mm_chain_group_counts: *runs = the group runs the filter stage swept or
+ * passed through, over all finished reads; *reads = the finished reads with more than one run.  A RUN is a maximal stretch of
+ * consecutive mappings of a read, in the order filterByGroup's first sort leaves them (by refSeqId, refStartPos), whose contigs have
+ * equal refGroup[refSeqId] -- what the reference's std::find_if_not delimits (computeMap.hpp:524); each run is sorted by the query key
+ * and swept on its own, a run of one mapping is passed through.  A group whose contigs are not consecutive in refGroup forms a run
+ * per stretch.  In a context without MM_FLAG_SKIP_PREFIX the mappings that reach the filter are one run; a read of which no mapping
+ * reaches the filter (the complexity gate or filterWeakMappings dropped them all) counts none, and with MM_CHAIN_FILTER_NONE no read
+ * counts any.  The two values come back with the words the stage already reads at its one host wait; MM_ERR_STATE under the
+ * conditions of mm_chain_counts.
  * Purely additive: MM_ABI_VERSION stays 2.
  */
 #define MM_CHAIN_MAX_RECORDS 16          /* what k_chain_reads (one thread per read, std::sort == __insertion_sort) takes */
@@ -416,6 +426,7 @@ int mm_set_chain_tables(mm_ctx* ctx, const mm_chain_params* params, const float*
 int mm_chain_reads(mm_ctx* ctx);
 int mm_chain_counts(const mm_ctx* ctx, size_t* offered, size_t* finished, size_t* rows, size_t* leftover);
 int mm_chain_long_counts(const mm_ctx* ctx, uint64_t* offered, uint64_t* finished);
+int mm_chain_group_counts(const mm_ctx* ctx, uint64_t* reads, uint64_t* runs);
 int mm_chain_download(mm_ctx* ctx, mm_chain_row* out, size_t cap, size_t* n);
 int mm_chain_leftover_download(mm_ctx* ctx, mm_mapping* out, size_t cap, size_t* n);
 int mm_chain_device(const mm_ctx* ctx, const mm_chain_row** dRows, size_t* nRows, const mm_mapping** dLeftover, size_t* nLeftover);
@@ -470,8 +481,16 @@ int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
  * sketch kernels, the survivors of the same cut sorted in LDS tiles of 4096 entries with sweeps through HBM only between tiles, the same
  * emission.  Same sketch bytes; mm_sketch_large_counts reports what the kernel took.  At sketchSize <= 8190 the option does nothing.
  * Purely additive: MM_ABI_VERSION stays 2.
+ * MM_OPT_CHAIN_MODES (default 0): with 1, mm_chain_reads takes a context created with MM_FLAG_SKIP_PREFIX, MM_FLAG_NO_SPLIT or both.
+ * Under MM_FLAG_SKIP_PREFIX the stage reads the index's refGroup array (an index that came through mm_index_replicate included) and
+ * filters every read run by run (mm_chain_group_counts above says what a run is), as the host's filterByGroup does under -Y; a record
+ * whose refSeqId is outside the index's contigs is a "corrupt record" (MM_ERR_STATE), never read past.  Under MM_FLAG_NO_SPLIT a read
+ * longer than segLength is one fragment: its row keeps the fragment's coordinates, queryLen is the read's length and n_merged is 0.
+ * Every other refusal keeps its place and its
+ * text -- sketchSize above 2048, no chain tables, nothing mapped, no replay tables --, and with the option off the two refusals by
+ * flag are those of before.  In a context with neither flag the option does nothing.  Purely additive: MM_ABI_VERSION stays 2.
  */
-enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6, MM_OPT_L2_LARGE_WAVE = 7, MM_OPT_CHAIN_LONG = 8, MM_OPT_SKETCH_LARGE = 9 };
+enum { MM_OPT_KEEP_POINTS = 1, MM_OPT_KEEP_FULL_INDEX = 2, MM_OPT_RESERVE_FRAGMENTS = 3, MM_OPT_L1_GROUP_STREAM = 4, MM_OPT_L2_WINDOW_WAVE = 5, MM_OPT_L1_GROUP_FUSED = 6, MM_OPT_L2_LARGE_WAVE = 7, MM_OPT_CHAIN_LONG = 8, MM_OPT_SKETCH_LARGE = 9, MM_OPT_CHAIN_MODES = 10 };
 int mm_set_option(mm_ctx* ctx, int option, int value);
 /* sorted interval points of fragment f after the seqId filters of computeMap.hpp:891-896 (needs MM_OPT_KEEP_POINTS; (seqId,pos,side) only, hash = 0).
  * Under MM_FLAG_SKIP_PREFIX the points are in HBM without that option too -- unless MM_OPT_L1_GROUP_FUSED is set: then MM_ERR_STATE. */

@@ -18,6 +18,7 @@ MM_OPT_L1_GROUP_FUSED = 6
 MM_OPT_L2_LARGE_WAVE = 7
 MM_OPT_CHAIN_LONG = 8
 MM_OPT_SKETCH_LARGE = 9
+MM_OPT_CHAIN_MODES = 10
 # bits of Context.pass_redo_cause() (include/mashmap_hip.h: MM_REDO_*)
 (MM_REDO_POINTS, MM_REDO_L1, MM_REDO_L2_LOCI, MM_REDO_L2_SLOTS, MM_REDO_L2_STREAM, MM_REDO_L2_OPS, MM_REDO_L2_LIST, MM_REDO_L2_CANDS,
  MM_REDO_MAPPINGS, MM_REDO_NO_STREAM_BUFFER) = (1 << i for i in range(10))
@@ -167,6 +168,7 @@ def load():
         "mm_chain_reads": (C.c_int, [vp]),
         "mm_chain_counts": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
         "mm_chain_long_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_chain_group_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_chain_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_leftover_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
@@ -200,7 +202,7 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
            "mm_stat_identity_table", "mm_set_chain_tables", "mm_chain_reads", "mm_chain_counts", "mm_chain_download",
            "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts", "mm_device_bytes",
-           "mm_sketch_large_counts"]
+           "mm_sketch_large_counts", "mm_chain_group_counts"]
 
 
 def device_bytes():
@@ -629,6 +631,18 @@ class Context:
         a, b = C.c_uint64(), C.c_uint64()
         self._ck(self.lib.mm_chain_long_counts(self.h, C.byref(a), C.byref(b)), "mm_chain_long_counts")
         return dict(offered=int(a.value), finished=int(b.value))
+
+    def chain_modes(self, on=True):
+        """MM_OPT_CHAIN_MODES: chain_reads() takes a context created with MM_FLAG_SKIP_PREFIX (filterByGroup then runs reference group by
+        reference group, from the index's refGroup array) and / or MM_FLAG_NO_SPLIT (no read is split); off, both are refused as before"""
+        self._ck(self.lib.mm_set_option(self.h, MM_OPT_CHAIN_MODES, 1 if on else 0), "mm_set_option")
+
+    def chain_group_counts(self):
+        """dict(reads, runs) of the last chain_reads(): the runs of one reference group filterByGroup swept or passed through over all
+        finished reads (one per read without MM_FLAG_SKIP_PREFIX, none with MM_CHAIN_FILTER_NONE), and the finished reads with more than one"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.mm_chain_group_counts(self.h, C.byref(a), C.byref(b)), "mm_chain_group_counts")
+        return dict(reads=int(a.value), runs=int(b.value))
 
     def chain_rows(self):
         n = self.chain_counts()["rows"]

@@ -101,6 +101,7 @@ int mm_set_option(mm_ctx* c, int option, int value) {
   if (option == MM_OPT_L2_LARGE_WAVE) { o.l2LargeWave = value & 3; return MM_OK; }
   if (option == MM_OPT_CHAIN_LONG) { o.chainLong = value != 0; return MM_OK; }
   if (option == MM_OPT_SKETCH_LARGE) { o.sketchLarge = value != 0; return MM_OK; }
+  if (option == MM_OPT_CHAIN_MODES) { o.chainModes = value != 0; return MM_OK; }
   c->err = "mm_set_option: unknown option"; return MM_ERR_ARG;
 }
 

@@ -22,12 +22,19 @@
 // kernel runs ONCE -- not once to count and once to write --: it leaves a read's rows at the read's record offset in a staging array (a
 // read leaves at most as many rows as it has records) and the count in cntRows[r] before the scan; k_chain_copy_long moves the rows to
 // their compact place behind the scan.  The stage keeps its single host wait.
+//
+// MM_OPT_CHAIN_MODES.  A context created with MM_FLAG_SKIP_PREFIX (-Y) or MM_FLAG_NO_SPLIT is then taken: the environment carries the
+// index's refGroup array and the noSplit flag, and filterByGroup walks the runs of one reference group (mm_chain_core.h, "runs").  Both
+// kernels get that from the core function; in k_chain_reads_long the runs are lane 0's, one after the other, like the rest of the
+// filter phase (a run per lane was built and measured: profiles/NOTES.md, "Chaining -Y and --noSplit reads").  Two more words of
+// dChainTotals count the runs (mm_chain_group_counts) and come back with the others.
 #include "mm_internal.h"
 #include "mm_chain_core.h"
 #include "../host/mm_stats.hpp"
 
 enum : int { MM_CT_ROWS = 0, MM_CT_LEFT = 1, MM_CT_OFFERED = 2, MM_CT_FINISHED = 3, MM_CT_BAD = 4,
-             MM_CT_LONG_OFFERED = 5, MM_CT_LONG_FINISHED = 6, MM_CT_LONG_LIST = 7, MM_CT_LONG_TICKET = 8, MM_CT_WORDS = 9 };   // dChainTotals
+             MM_CT_LONG_OFFERED = 5, MM_CT_LONG_FINISHED = 6, MM_CT_LONG_LIST = 7, MM_CT_LONG_TICKET = 8,
+             MM_CT_GROUP_READS = 9, MM_CT_GROUP_RUNS = 10, MM_CT_WORDS = 11 };   // dChainTotals
 #define MM_CHAIN_LONG_WG_PER_CU 4
 
 // the records are read-major: a read's are one run of equal querySeqId
@@ -53,7 +60,7 @@ k_chain_reads(mm_chain_env E, int nReads, const mm_mapping* __restrict__ recs, c
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   int n = 0, b = 0;
   if (r < nReads) { b = begin[r]; n = end[r] - b; if (n < 0) n = 0; }
-  int nRows = 0, nLeft = 0;
+  int nRows = 0, nLeft = 0, nRuns = 0;
   const bool isLong = longOn && n > MM_CHAIN_MAX_RECORDS && n <= MM_CHAIN_LONG_MAX_RECORDS;
   if (isLong) {
     if (!WRITE) longList[atomicAdd(&totals[MM_CT_LONG_LIST], 1ull)] = r;             // fewer entries than reads
@@ -61,17 +68,28 @@ k_chain_reads(mm_chain_env E, int nReads, const mm_mapping* __restrict__ recs, c
     nLeft = n;
     if (WRITE) { mm_mapping* dst = left + offLeft[r]; for (int i = 0; i < n; i++) dst[i] = recs[b + i]; }
   } else if (n > 0) {
-    nRows = mm_chain_read(E, recs + b, n, readLen[r], WRITE ? rows + offRows[r] : (mm_chain_row*)nullptr);
+    nRows = mm_chain_read(E, recs + b, n, readLen[r], WRITE ? rows + offRows[r] : (mm_chain_row*)nullptr, WRITE ? (int*)nullptr : &nRuns);
     if (nRows < 0) { nRows = 0; if (!WRITE) atomicAdd(&totals[MM_CT_BAD], 1ull); }     // MM_CHAIN_BAD_RECORD: the launcher reports it, nothing of the read is written
   }
   if (!WRITE) {
     if (r < nReads) { cntRows[r] = nRows; cntLeft[r] = nLeft; }
     const int offered = __syncthreads_count(n > 0), finished = __syncthreads_count(n > 0 && nLeft == 0);
     const int longOffered = __syncthreads_count(n > MM_CHAIN_MAX_RECORDS);
+    // the runs of the block's reads (at most 16 each): reads with more than t runs, summed over t
+    const int groupReads = __syncthreads_count(nRuns > 1);
+    int groupRuns = 0;
+    const int mostRuns = E.refGroup ? MM_CHAIN_MAX_RECORDS : 1;
+    for (int t = 0; t < mostRuns; t++) {
+      const int above = __syncthreads_count(nRuns > t);
+      if (!above) break;
+      groupRuns += above;
+    }
     if (threadIdx.x == 0) {
       if (offered) atomicAdd(&totals[MM_CT_OFFERED], (unsigned long long)offered);
       if (finished) atomicAdd(&totals[MM_CT_FINISHED], (unsigned long long)finished);
       if (longOffered) atomicAdd(&totals[MM_CT_LONG_OFFERED], (unsigned long long)longOffered);
+      if (groupReads) atomicAdd(&totals[MM_CT_GROUP_READS], (unsigned long long)groupReads);
+      if (groupRuns) atomicAdd(&totals[MM_CT_GROUP_RUNS], (unsigned long long)groupRuns);
     }
   }
 }
@@ -111,7 +129,7 @@ k_chain_reads_long(mm_chain_env E, const mm_mapping* __restrict__ recs, const in
     const int b = begin[r], n = end[r] - b;
     if (n <= MM_CHAIN_MAX_RECORDS || n > MM_CHAIN_LONG_MAX_RECORDS) continue;          // (the count pass lists no such read)
     const int32_t len = readLen[r];
-    const bool split = len > E.segLength;
+    const bool split = !E.noSplit && len > E.segLength;
     const int32_t querySeqId = recs[b].querySeqId;
     const int32_t queryLen = split ? len : recs[b].fragLen;
 
@@ -185,12 +203,17 @@ k_chain_reads_long(mm_chain_env E, const mm_mapping* __restrict__ recs, const in
       __syncthreads();
     }
 
-    // ---- filterByGroup: its sorts and the sweep
-    if (lane == 0) sM = mm_chain_filter(E, W, m, len);
+    // ---- filterByGroup: its sorts and the sweep of every run (nRuns: lane 0's alone)
+    int nRuns = 0;
+    if (lane == 0) sM = mm_chain_filter(E, W, m, len, &nRuns);
     __syncthreads();
     m = sM;
     for (int i = lane; i < m; i += 64) stage[(size_t)b + i] = mm_chain_emit(W, W.v[i], querySeqId, queryLen);
-    if (lane == 0) { cntRows[r] = m; atomicAdd(&totals[MM_CT_LONG_FINISHED], 1ull); }
+    if (lane == 0) {
+      cntRows[r] = m; atomicAdd(&totals[MM_CT_LONG_FINISHED], 1ull);
+      if (nRuns) atomicAdd(&totals[MM_CT_GROUP_RUNS], (unsigned long long)nRuns);
+      if (nRuns > 1) atomicAdd(&totals[MM_CT_GROUP_READS], 1ull);
+    }
   }
 }
 
@@ -236,14 +259,17 @@ int mm_set_chain_tables(mm_ctx* c, const mm_chain_params* params, const float* i
 int mm_chain_reads(mm_ctx* c) {
   c->chainPass = 0;
   // what the context was created with first, then what the caller has done with it
-  if (c->P.flags & MM_FLAG_SKIP_PREFIX) { c->err = "mm_chain_reads: MM_FLAG_SKIP_PREFIX is set (filterByGroup then runs reference group by reference group)"; return MM_ERR_STATE; }
-  if (c->P.flags & MM_FLAG_NO_SPLIT) { c->err = "mm_chain_reads: MM_FLAG_NO_SPLIT is set"; return MM_ERR_STATE; }
+  // (both taken with MM_OPT_CHAIN_MODES)
+  const bool grouped = (c->P.flags & MM_FLAG_SKIP_PREFIX) != 0, noSplit = (c->P.flags & MM_FLAG_NO_SPLIT) != 0;
+  if (grouped && !c->opt.chainModes) { c->err = "mm_chain_reads: MM_FLAG_SKIP_PREFIX is set (filterByGroup then runs reference group by reference group)"; return MM_ERR_STATE; }
+  if (noSplit && !c->opt.chainModes) { c->err = "mm_chain_reads: MM_FLAG_NO_SPLIT is set"; return MM_ERR_STATE; }
   if (c->P.sketchSize > MM_CHAIN_MAX_SKETCH) { c->err = "mm_chain_reads: sketchSize above 2048 (the identity table would be larger than 16 MB)"; return MM_ERR_STATE; }
   if (!c->haveChainTables) { c->err = "mm_chain_reads: mm_set_chain_tables was not called"; return MM_ERR_STATE; }
   if (!c->mapped || !c->haveReplayTables) { c->err = "mm_chain_reads: nothing mapped, or mm_set_replay_tables / mm_set_tables_default was not called"; return MM_ERR_STATE; }
-  c->chOffered = c->chFinished = c->chRows = c->chLeft = 0; c->chLongOffered = c->chLongFinished = 0;
+  c->chOffered = c->chFinished = c->chRows = c->chLeft = 0; c->chLongOffered = c->chLongFinished = 0; c->chGroupReads = c->chGroupRuns = 0;
   const size_t nR = c->nReads, nM = c->rep.nMappings;
   if (nM > (size_t)0x7fffffff || nR > (size_t)0x7fffffff) { c->err = "mm_chain_reads: more than 2^31 - 1 records in one batch"; return MM_ERR_CAPACITY; }
+  if (grouped && nR && nM && (!c->idx.ready || !c->idx.nContigs || c->idx.refGroup.bytes < c->idx.nContigs * 4)) { c->err = "mm_chain_reads: internal error: records without an index's reference groups"; return MM_ERR_STATE; }
   if (nR && nM) {
     MM_HIP(c, hipSetDevice(c->device));
     MM_HIP(c, c->dChainBegin.ensure(nR * 4 + 64)); MM_HIP(c, c->dChainEnd.ensure(nR * 4 + 64));
@@ -263,6 +289,7 @@ int mm_chain_reads(mm_ctx* c) {
                        c->dChainBegin.as<int32_t>(), c->dChainEnd.as<int32_t>());
     mm_chain_env E;
     E.p = c->chainP; E.kmerSize = c->P.kmerSize; E.segLength = c->P.segLength; E.stride = c->P.sketchSize + 1; E.identity = c->dChainIdent.as<float>();
+    E.refGroup = grouped ? c->idx.refGroup.as<int32_t>() : nullptr; E.nContigs = (int32_t)c->idx.nContigs; E.noSplit = noSplit ? 1 : 0;
     unsigned long long* totals = c->dChainTotals.as<unsigned long long>();
     const dim3 grid((unsigned)((nR + 127) / 128)), block(128);
     hipLaunchKernelGGL((k_chain_reads<false>), grid, block, 0, c->stream, E, (int)nR, recs, c->dChainBegin.as<int32_t>(), c->dChainEnd.as<int32_t>(),
@@ -294,7 +321,12 @@ int mm_chain_reads(mm_ctx* c) {
     MM_HIP(c, hipStreamSynchronize(c->stream));                    // the stage's one host wait
     c->chRows = (size_t)h[MM_CT_ROWS]; c->chLeft = (size_t)h[MM_CT_LEFT]; c->chOffered = (size_t)h[MM_CT_OFFERED]; c->chFinished = (size_t)h[MM_CT_FINISHED];
     c->chLongOffered = h[MM_CT_LONG_OFFERED]; c->chLongFinished = h[MM_CT_LONG_FINISHED];
-    if (h[MM_CT_BAD]) { c->err = "mm_chain_reads: corrupt record: a candidate mapping names a sketch size or shared count outside the identity table"; return MM_ERR_STATE; }
+    c->chGroupReads = h[MM_CT_GROUP_READS]; c->chGroupRuns = h[MM_CT_GROUP_RUNS];
+    if (h[MM_CT_BAD]) {
+      c->err = grouped ? "mm_chain_reads: corrupt record: a candidate mapping names a sketch size or shared count outside the identity table, or a contig outside the index"
+                       : "mm_chain_reads: corrupt record: a candidate mapping names a sketch size or shared count outside the identity table";
+      return MM_ERR_STATE;
+    }
     if (c->chRows > nM || c->chLeft > nM) { c->err = "mm_chain_reads: internal error: more rows or left-over records than records"; return MM_ERR_CAPACITY; }
   }
   c->chainPass = c->tot.nPasses;
@@ -316,6 +348,13 @@ int mm_chain_long_counts(const mm_ctx* c, uint64_t* offered, uint64_t* finished)
   if (!chain_valid(c)) { const_cast<mm_ctx*>(c)->err = "mm_chain_long_counts: mm_chain_reads has not run on the mapped batch"; return MM_ERR_STATE; }
   if (offered) *offered = c->chLongOffered;
   if (finished) *finished = c->chLongFinished;
+  return MM_OK;
+}
+
+int mm_chain_group_counts(const mm_ctx* c, uint64_t* reads, uint64_t* runs) {
+  if (!chain_valid(c)) { const_cast<mm_ctx*>(c)->err = "mm_chain_group_counts: mm_chain_reads has not run on the mapped batch"; return MM_ERR_STATE; }
+  if (reads) *reads = c->chGroupReads;
+  if (runs) *runs = c->chGroupRuns;
   return MM_OK;
 }
 

@@ -4,7 +4,8 @@
 //   Map::mapModule             coordinates of a split read                              :632-636
 //   Map::mergeMappingsInRange  sort, pair loop, union-find, extents, the two averages   :1580-1702   (src/common/dset64.hpp:93-125)
 //   Map::filterWeakMappings                                                             :423-432
-//   Map::filterByGroup         both sorts, the query-axis plane sweep                   :504-561, src/map/include/filter.hpp:36-160
+//   Map::filterByGroup         both sorts, the runs of one reference group under -Y,    :504-561, src/map/include/filter.hpp:36-160
+//                              the query-axis plane sweep of every run
 //
 // i.e. MapPost::finishRead (mashmap_amd/host/skch_map_post.hpp) up to and including filterByGroup, on the integers of mm_mapping.
 // Shared by the kernels (k_chain_reads, k_chain_reads_long, mm_chain.hip) and by the CPU checks (tests/hostlogic/chain_check.cpp,
@@ -15,7 +16,8 @@
 // MM_CHAIN_MAX_RECORDS (16) records with its working set on the stack and 8-bit ids; mm_chain_read_long takes one of at most
 // MM_CHAIN_LONG_MAX_RECORDS (512) with a working set the caller provides (the kernel's is in LDS) and 16-bit ids.  The body is made of the
 // steps the wave-per-read kernel calls one by one: mm_chain_prepare (one record), mm_chain_partner (the best partner of member i),
-// mm_chain_unite, mm_chain_finish_chain, mm_chain_keep, mm_chain_filter with mm_chain_sweep, mm_chain_emit (one row).
+// mm_chain_unite, mm_chain_finish_chain, mm_chain_keep, mm_chain_filter -- itself the sort by the reference key, mm_chain_run_end and
+// mm_chain_filter_run (with mm_chain_sweep) for every run, mm_chain_filter_compact --, mm_chain_emit (one row).
 //
 // Why the result is the host's, bit for bit:
 //   sorts     All five order-sensitive sorts of the tail -- per fragment, before the pair loop, by splitMappingId, the two of
@@ -47,6 +49,21 @@
 //             whose LARGEST hash lies below 2^40 -- s hashes out of 2^64 all that small -- which no sequence a sketch is taken of yields.
 //             tests/hostlogic/chain_check.cpp draws maxHash over the whole assumed range (2^40 .. 2^64).
 //   kmerComplexity  (double)((long double)maxHash / UINT64_MAX) without an 80-bit type: mm_chain_hash01.
+//   runs      Under -Y (mm_chain_env::refGroup set) filterByGroup filters reference group by reference group.  Behind its sort by
+//             (refSeqId, refStartPos) it walks RUNS: a run is a maximal stretch of consecutive members of that sorted order with equal
+//             refGroup[refSeqId] -- std::find_if_not from the run's first member (:524) --, so a group whose contigs are not consecutive
+//             in a refGroup array that is not non-decreasing (the C ABI takes one) forms two runs, here as there.  The host copies a
+//             run into a vector of its own, sorts the copy by the query key and sweeps it; here the run v[b, e) is sorted in place: the
+//             same elements in the same input order under the same comparator, so mm_std_sort makes the same moves.  The sweep's ids
+//             are absolute positions in v (b .. e - 1, below 512: the event word's 10 bits) where the host's count from 0 inside the
+//             copy: a constant offset, the same order of events and of the status set.  A run's events are ev[2b, 2e), its status set
+//             status[b, e), and it writes `discard` of its own members only: two runs touch disjoint scratch and disjoint members, in
+//             whatever order they are swept.  A run of one member is kept untouched
+//             (filterQueryAxis returns at size <= 1).  The survivors are appended run by run, i.e. compacted in order, and the final
+//             sort by the query key sees them in the order the host's `filtered` vector has.  secondaryToKeep is the same for every
+//             run.  Without refGroup the single run is [0, m): the code of before.
+//   noSplit   mm_chain_env::noSplit (MM_FLAG_NO_SPLIT): split_mapping is false for every read (:587), so a read longer than a segment
+//             keeps its fragment's coordinates (0 .. fragLen), is not merged, and queryLen is its one fragment's length.
 #pragma once
 #include <math.h>
 #include "mm_heap.h"
@@ -58,6 +75,9 @@ struct mm_chain_env {
   mm_chain_params p;
   int32_t kmerSize, segLength, stride;       // stride of `identity` (sketchSize + 1)
   const float* identity;                     // identity[Qs * stride + shared]
+  const int32_t* refGroup = nullptr;         // -Y (param.skip_prefix): refIdGroup[refSeqId], nContigs entries; nullptr: no groups, one run
+  int32_t nContigs = 0;
+  int32_t noSplit = 0;                       // --noSplit (!param.split): no read is split
 };
 
 // secondaryShort / secondarySegment are numMappingsFor... - 1 of an unsigned count: -1 (a count of 0) is what the reference and MapPost
@@ -67,7 +87,7 @@ MM_HD bool mm_chain_params_ok(const mm_chain_params& p) {
   return p.chainGap >= 0 && p.chainGap <= MM_CHAIN_MAX_GAP && (p.filter == MM_CHAIN_FILTER_NONE || p.filter == MM_CHAIN_FILTER_QUERY) &&
          p.secondaryShort >= -1 && p.secondarySegment >= -1 && p.minMerged >= 0;
 }
-#define MM_CHAIN_BAD_RECORD (-2)             // mm_chain_read: a record outside the identity table (an error, not a hand-over)
+#define MM_CHAIN_BAD_RECORD (-2)             // mm_chain_read: a record outside the identity table or, with refGroup, the contigs (an error, not a hand-over)
 
 // (double)((long double)maxHash / UINT64_MAX), getSeedHits' max_hash_01 (:830), in integers.  With D = 2^64 - 1 and m' = maxHash << clz
 // in [2^63, 2^64): m' * 2^64 = m' * D + m', so the quotient's 64-bit mantissa is m' with remainder m' -- more than D / 2, never a tie (D
@@ -144,15 +164,17 @@ MM_HD void mm_chain_sort(W& w, int b, int e, Less less) {
 template <class W> MM_HD void mm_chain_sort_ref(W& w, int b, int e) { mm_chain_sort(w, b, e, [&w](int x, int y) { return mm_chain_less_ref(w, x, y); }); }
 template <class W> MM_HD void mm_chain_sort_merge(W& w, int m) { mm_chain_sort(w, 0, m, [&w](int x, int y) { return mm_chain_less_merge(w, x, y); }); }
 template <class W> MM_HD void mm_chain_sort_smid(W& w, int m) { mm_chain_sort(w, 0, m, [&w](int x, int y) { return w.smid[x] < w.smid[y]; }); }
-template <class W> MM_HD void mm_chain_sort_query(W& w, int m) { mm_chain_sort(w, 0, m, [&w](int x, int y) { return mm_chain_less_query(w, x, y); }); }
+template <class W> MM_HD void mm_chain_sort_query(W& w, int b, int e) { mm_chain_sort(w, b, e, [&w](int x, int y) { return mm_chain_less_query(w, x, y); }); }
 
 // ---- prepare one record: record r of a fragment of length Qlen and complexity kc that passed the gate becomes member x (v[x] = x).
 // qs / qe are the read's coordinates at once (:632-636 sets them behind the fragment's sort, to the same values for every record of the
-// fragment).  false: the record names an entry outside the identity table -- not a hand-over cause but an error (k_l2_select writes
-// shared <= Qs <= sketchSize): nothing is read outside the table, and the caller reports it (mm_chain_reads: MM_ERR_STATE, "corrupt record")
+// fragment).  false: the record names an entry outside the identity table or, with refGroup set, a contig outside [0, nContigs) -- not a
+// hand-over cause but an error (k_l2_select writes shared <= Qs <= sketchSize and the index's own contig ids): nothing is read outside
+// either array, and the caller reports it (mm_chain_reads: MM_ERR_STATE, "corrupt record")
 template <class W>
 MM_HD bool mm_chain_prepare(const mm_chain_env& E, W& w, int x, const mm_mapping& r, bool split, float kc) {
   if ((uint32_t)r.sketchSize >= (uint32_t)E.stride || (uint32_t)r.conservedSketches >= (uint32_t)E.stride) return false;
+  if (E.refGroup && (uint32_t)r.refSeqId >= (uint32_t)E.nContigs) return false;
   const int32_t Qlen = r.fragLen;
   w.v[x] = (typename W::ID)x;
   w.ident[x] = E.identity[(size_t)r.sketchSize * (size_t)E.stride + (size_t)r.conservedSketches];
@@ -235,15 +257,18 @@ MM_HD void mm_chain_finish_chain(W& w, int it, int end) {
   w.kc[rep] = sumK / (double)w.nm[rep];
 }
 
-// ---- the sweep: filterQueryAxis over v[0, m) (m > 1), sorted by (queryStartPos, refSeqId, refStartPos); ids of the sweep are positions
-// in v.  An event is (pos, BEGIN = 1 / END = 2, id) in one word; marks the survivors with discard == 0.
+// ---- the sweep: filterQueryAxis over the run v[b, e) (e - b > 1), sorted by (queryStartPos, refSeqId, refStartPos); ids of the sweep are
+// positions in v (absolute: b .. e - 1).  An event is (pos, BEGIN = 1 / END = 2, id) in one word; marks the survivors with discard == 0.
+// Scratch: ev[2b, 2e) and status[b, e) -- two runs share nothing.
 template <class W>
-MM_HD void mm_chain_sweep(W& w, int m, int secondaryToKeep) {
-  uint64_t* ev = w.sw.ev;
+MM_HD void mm_chain_sweep(W& w, int b, int e, int secondaryToKeep) {
+  uint64_t* ev = w.sw.ev + 2 * b;
+  const int m = e - b;
   for (int i = 0; i < m; i++) {
-    w.discard[w.v[i]] = 1;
-    ev[2 * i] = ((uint64_t)((uint32_t)w.qs[w.v[i]] ^ 0x80000000u) << 12) | (1u << 10) | (uint64_t)i;
-    ev[2 * i + 1] = ((uint64_t)((uint32_t)w.qe[w.v[i]] ^ 0x80000000u) << 12) | (2u << 10) | (uint64_t)i;
+    const int x = w.v[b + i];
+    w.discard[x] = 1;
+    ev[2 * i] = ((uint64_t)((uint32_t)w.qs[x] ^ 0x80000000u) << 12) | (1u << 10) | (uint64_t)(b + i);
+    ev[2 * i + 1] = ((uint64_t)((uint32_t)w.qe[x] ^ 0x80000000u) << 12) | (2u << 10) | (uint64_t)(b + i);
   }
   const int nE = 2 * m;
   mm_std_heap_sort(ev, 0, nE, [](uint64_t x, uint64_t y) { return x < y; });     // distinct words: any sort does
@@ -253,7 +278,7 @@ MM_HD void mm_chain_sweep(W& w, int m, int secondaryToKeep) {
     if (w.ident[a] != w.ident[b]) return w.ident[a] > w.ident[b];
     if (w.qs[a] != w.qs[b]) return w.qs[a] > w.qs[b];
     return w.sid[a] > w.sid[b]; };
-  typename W::ID* status = w.sw.status;
+  typename W::ID* status = w.sw.status + b;
   int nS = 0;
   for (int i = 0; i < nE;) {
     int j = i;
@@ -304,21 +329,50 @@ MM_HD int mm_chain_keep(const mm_chain_env& E, W& w, int m, int32_t queryLen, bo
   return k;
 }
 
-// ---- filterByGroup, query axis, over v[0, m); -> new m
+// ---- filterByGroup, query axis, over v[0, m), step by step
+// secondaryToKeep of a read (:675-677 and the cast of :544)
+MM_HD int mm_chain_secondary(const mm_chain_env& E, int32_t readLen) { return (int)(uint16_t)(readLen < E.segLength ? E.p.secondaryShort : E.p.secondarySegment); }
+// the end of the run that starts at b < m: std::find_if_not over the members of the first one's group (:523-526); without groups, m
 template <class W>
-MM_HD int mm_chain_filter(const mm_chain_env& E, W& w, int m, int32_t readLen) {
+MM_HD int mm_chain_run_end(const mm_chain_env& E, const W& w, int m, int b) {
+  if (!E.refGroup) return m;
+  const int32_t g = E.refGroup[w.sid[w.v[b]]];
+  int e = b + 1;
+  while (e < m && E.refGroup[w.sid[w.v[e]]] == g) e++;
+  return e;
+}
+// one run: the sort by the query key, the sweep of more than one member; its survivors have discard == 0
+template <class W>
+MM_HD void mm_chain_filter_run(const mm_chain_env& E, W& w, int b, int e, int secondaryToKeep) {
+  (void)E;
+  mm_chain_sort_query(w, b, e);
+  if (e - b > 1) mm_chain_sweep(w, b, e, secondaryToKeep);
+  else w.discard[w.v[b]] = 0;
+}
+// behind the runs: the survivors in order, then the final sort; -> new m
+template <class W>
+MM_HD int mm_chain_filter_compact(W& w, int m) {
+  int k = 0;
+  for (int i = 0; i < m; i++) if (w.discard[w.v[i]] == 0) w.v[k++] = w.v[i];
+  mm_chain_sort_query(w, 0, k);
+  return k;
+}
+// all of it on one thread; -> new m.  *runs (when non-null) receives the number of runs swept or passed through
+template <class W>
+MM_HD int mm_chain_filter(const mm_chain_env& E, W& w, int m, int32_t readLen, int* runs = nullptr) {
+  if (runs) *runs = 0;
   if (E.p.filter != MM_CHAIN_FILTER_QUERY) return m;
-  const int secondaryToKeep = (int)(uint16_t)(readLen < E.segLength ? E.p.secondaryShort : E.p.secondarySegment);
+  const int secondaryToKeep = mm_chain_secondary(E, readLen);
   mm_chain_sort_ref(w, 0, m);
-  mm_chain_sort_query(w, m);
-  if (m > 1) {
-    mm_chain_sweep(w, m, secondaryToKeep);
-    int k = 0;
-    for (int i = 0; i < m; i++) if (w.discard[w.v[i]] == 0) w.v[k++] = w.v[i];
-    m = k;
+  int nRuns = 0;
+  for (int b = 0; b < m;) {
+    const int e = mm_chain_run_end(E, w, m, b);
+    mm_chain_filter_run(E, w, b, e, secondaryToKeep);
+    nRuns++;
+    b = e;
   }
-  mm_chain_sort_query(w, m);
-  return m;
+  if (runs) *runs = nRuns;
+  return mm_chain_filter_compact(w, m);
 }
 
 // ---- emit one row: member x
@@ -335,9 +389,10 @@ MM_HD mm_chain_row mm_chain_emit(const W& w, int x, int32_t querySeqId, int32_t 
 
 // the whole tail on one thread, 1 <= n <= W::CAP
 template <class W>
-MM_HD int mm_chain_read_t(const mm_chain_env& E, W& w, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out) {
+MM_HD int mm_chain_read_t(const mm_chain_env& E, W& w, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out, int* runs = nullptr) {
   int m = 0;
-  const bool split = readLen > E.segLength;                       // :583 (MM_FLAG_NO_SPLIT is refused by the caller)
+  if (runs) *runs = 0;
+  const bool split = !E.noSplit && readLen > E.segLength;         // :587
   const int32_t querySeqId = recs[0].querySeqId;
 
   // ---- per fragment: mapSingleQueryFrag's gate and sort, then the read's coordinates
@@ -375,7 +430,7 @@ MM_HD int mm_chain_read_t(const mm_chain_env& E, W& w, const mm_mapping* recs, i
     m = mm_chain_keep(E, w, m, queryLen, m >= 2);
   }
 
-  m = mm_chain_filter(E, w, m, readLen);
+  m = mm_chain_filter(E, w, m, readLen, runs);
 
   if (out) for (int i = 0; i < m; i++) out[i] = mm_chain_emit(w, w.v[i], querySeqId, queryLen);
   return m;
@@ -384,17 +439,25 @@ MM_HD int mm_chain_read_t(const mm_chain_env& E, W& w, const mm_mapping* recs, i
 // Finishes the read of length readLen whose records are recs[0, n), in mm_mappings_download's order.  Writes the surviving mappings to
 // out (when non-null; up to n of them), in the order filterByGroup leaves them, and returns their number; -1 for n above
 // MM_CHAIN_MAX_RECORDS (the read is not taken), MM_CHAIN_BAD_RECORD for a record outside the identity table.
-MM_HD int mm_chain_read(const mm_chain_env& E, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out) {
+// *runs (when non-null): the runs filterByGroup walked for this read -- 0 with MM_CHAIN_FILTER_NONE or when nothing reached the filter,
+// 1 without refGroup, the read's stretches of equal reference group with it; 0 for a read that is not taken or in error.
+MM_HD int mm_chain_read(const mm_chain_env& E, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out, int* runs = nullptr) {
+  if (runs) *runs = 0;
   if (n > MM_CHAIN_MAX_RECORDS) return -1;
   if (n <= 0) return 0;
   mm_chain_work W;
-  return mm_chain_read_t(E, W, recs, n, readLen, out);
+  const int rows = mm_chain_read_t(E, W, recs, n, readLen, out, runs);
+  if (rows < 0 && runs) *runs = 0;
+  return rows;
 }
 
 // The same for a read of up to MM_CHAIN_LONG_MAX_RECORDS (512) records in the working set W the caller provides (39 KB: not for a
 // device stack); -1 above that.  For n <= 16 the rows are mm_chain_read's.
-MM_HD int mm_chain_read_long(const mm_chain_env& E, mm_chain_work_long& W, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out) {
+MM_HD int mm_chain_read_long(const mm_chain_env& E, mm_chain_work_long& W, const mm_mapping* recs, int n, int32_t readLen, mm_chain_row* out, int* runs = nullptr) {
+  if (runs) *runs = 0;
   if (n > MM_CHAIN_LONG_MAX_RECORDS) return -1;
   if (n <= 0) return 0;
-  return mm_chain_read_t(E, W, recs, n, readLen, out);
+  const int rows = mm_chain_read_t(E, W, recs, n, readLen, out, runs);
+  if (rows < 0 && runs) *runs = 0;
+  return rows;
 }

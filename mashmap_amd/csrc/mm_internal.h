@@ -277,6 +277,7 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   // read's record offset, and the two counts of mm_chain_long_counts
   DevBuf dChainLongList, dChainStage;
   uint64_t chLongOffered = 0, chLongFinished = 0;
+  uint64_t chGroupReads = 0, chGroupRuns = 0;           // mm_chain_group_counts: finished reads with more than one run of filterByGroup, and the runs of all of them
   int chainCUs = 0;                                     // compute units of the device (k_chain_reads_long's grid), asked for once
   // multi-GPU exchange (mm_comm.hip)
   void* comm = nullptr; int commRank = 0, commWorld = 0; bool commCopy = false;   // commCopy: local group whose contexts share a device

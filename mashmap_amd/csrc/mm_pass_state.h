@@ -18,6 +18,7 @@ struct Options {                            // written by mm_set_option alone
   int l2LargeWave = 0;                      // MM_OPT_L2_LARGE_WAVE: bit 0: split batches on the literal L2 route go to k_l2_large_wave first; bit 1: they take that route at any sketch size
   bool sketchLarge = false;                 // MM_OPT_SKETCH_LARGE: sketches beyond MM_LDS_MAX_SKETCH on k_sketch_large instead of k_sketch_global
   bool chainLong = false;                   // MM_OPT_CHAIN_LONG: reads of 17 .. 512 records are chained on the device as well
+  bool chainModes = false;                  // MM_OPT_CHAIN_MODES: mm_chain_reads takes a context created with MM_FLAG_SKIP_PREFIX and / or MM_FLAG_NO_SPLIT
 };
 
 // the last mm_map_fragments, and nothing older: PassReport{} at the top of mm_launch_map (mm_pass_stats, mm_pass_redo_cause, mm_result_counts)

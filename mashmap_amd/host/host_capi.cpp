@@ -66,17 +66,19 @@ int64_t mmh_post_batch(int k, int segLength, int sketchSize, float pi, int filte
 // records, or neither.  Rows go through MapPost::finishRows, records through mapModuleFromRecords, and the reported mappings come out
 // in input order.  With no rows at all this is mmh_post_batch with chain_gap, block_length and the two mapping counts given
 // explicitly.  nMerged / approxMatches (may be null) receive those two fields of every reported mapping beside `rows`.
-int64_t mmh_post_chained(int k, int segLength, int sketchSize, float pi, int filterMode, int hgFilter, int numMappingsShort, int numMappingsSegment,
-                         int chainGap, int blockLength, int nContigs, const int32_t* contigLens, const mm_chain_row* chainRows, size_t nChainRows,
-                         const mm_mapping* recs, size_t nRecs, const int32_t* readLens, size_t nReads, int32_t firstSeqCounter, int threads,
-                         double* seconds, mmh_row* rows, int32_t* nMerged, int32_t* approxMatches, size_t cap) {
+static int64_t post_chained(int k, int segLength, int sketchSize, float pi, int filterMode, int hgFilter, int numMappingsShort, int numMappingsSegment,
+                            int chainGap, int blockLength, int nContigs, const int32_t* contigLens, const mm_chain_row* chainRows, size_t nChainRows,
+                            const mm_mapping* recs, size_t nRecs, const int32_t* readLens, size_t nReads, int32_t firstSeqCounter, int threads,
+                            double* seconds, mmh_row* rows, int32_t* nMerged, int32_t* approxMatches, size_t cap, const int32_t* refGroup, int split) {
   skch::Parameters p;
   p.kmerSize = k; p.segLength = segLength; p.block_length = blockLength; p.chain_gap = chainGap; p.sketchSize = sketchSize;
   p.percentageIdentity = pi; p.filterMode = filterMode; p.stage1_topANI_filter = hgFilter != 0;
   p.numMappingsForSegment = (uint32_t)numMappingsSegment; p.numMappingsForShortSequence = (uint32_t)numMappingsShort;
+  p.skip_prefix = refGroup != nullptr; p.split = split != 0;
   std::vector<skch::ContigInfo> meta((size_t)nContigs);
   for (int i = 0; i < nContigs; i++) meta[i] = skch::ContigInfo{"c" + std::to_string(i), contigLens[i]};
   std::vector<int> grp((size_t)nContigs, 0);
+  if (refGroup) grp.assign(refGroup, refGroup + nContigs);
   skch::MapPost post(p, meta, grp);
   const auto t0 = std::chrono::high_resolution_clock::now();
   std::vector<size_t> recBegin(nReads + 1, nRecs), rowBegin(nReads + 1, nChainRows);
@@ -112,19 +114,38 @@ int64_t mmh_post_chained(int k, int segLength, int sketchSize, float pi, int fil
   return n;
 }
 
+int64_t mmh_post_chained(int k, int segLength, int sketchSize, float pi, int filterMode, int hgFilter, int numMappingsShort, int numMappingsSegment,
+                         int chainGap, int blockLength, int nContigs, const int32_t* contigLens, const mm_chain_row* chainRows, size_t nChainRows,
+                         const mm_mapping* recs, size_t nRecs, const int32_t* readLens, size_t nReads, int32_t firstSeqCounter, int threads,
+                         double* seconds, mmh_row* rows, int32_t* nMerged, int32_t* approxMatches, size_t cap) {
+  return post_chained(k, segLength, sketchSize, pi, filterMode, hgFilter, numMappingsShort, numMappingsSegment, chainGap, blockLength, nContigs, contigLens, chainRows,
+                      nChainRows, recs, nRecs, readLens, nReads, firstSeqCounter, threads, seconds, rows, nMerged, approxMatches, cap, nullptr, 1);
+}
+// ... under -Y (refGroup, nContigs entries: skip_prefix and MapPost's refIdGroup; nullptr: none) and --noSplit (split == 0): the stage
+// behind mm_chain_reads with MM_OPT_CHAIN_MODES, and with no rows at all the host stage of such a run as it was (scripts/chain_probe.py --groups)
+int64_t mmh_post_chained_modes(int k, int segLength, int sketchSize, float pi, int filterMode, int hgFilter, int numMappingsShort, int numMappingsSegment,
+                               int chainGap, int blockLength, int nContigs, const int32_t* contigLens, const mm_chain_row* chainRows, size_t nChainRows,
+                               const mm_mapping* recs, size_t nRecs, const int32_t* readLens, size_t nReads, int32_t firstSeqCounter, int threads,
+                               double* seconds, mmh_row* rows, int32_t* nMerged, int32_t* approxMatches, size_t cap, const int32_t* refGroup, int split) {
+  return post_chained(k, segLength, sketchSize, pi, filterMode, hgFilter, numMappingsShort, numMappingsSegment, chainGap, blockLength, nContigs, contigLens, chainRows,
+                      nChainRows, recs, nRecs, readLens, nReads, firstSeqCounter, threads, seconds, rows, nMerged, approxMatches, cap, refGroup, split);
+}
+
 // What mm_chain_reads must leave, from the host's own code: for every read with 1 .. maxRecords records, MapPost::chainedFromRecords
 // (mapModuleFromRecords stopped behind filterByGroup) as mm_chain_row, in read order.  Returns the number of rows (out receives the
-// first `cap`).  The checker of the device rows in tests/test_gpu_chain.py; one thread.
-int64_t mmh_chain_rows(int k, int segLength, int sketchSize, float pi, int filterMode, int numMappingsShort, int numMappingsSegment, int chainGap,
-                       int blockLength, int nContigs, const int32_t* contigLens, const mm_mapping* recs, size_t nRecs, const int32_t* readLens,
-                       size_t nReads, int32_t firstSeqCounter, int maxRecords, mm_chain_row* out, size_t cap) {
+// first `cap`).  refGroup (nContigs entries; nullptr: no -Y) sets skip_prefix and MapPost's refIdGroup, split == 0 is --noSplit.  One thread.
+static int64_t chain_rows(int k, int segLength, int sketchSize, float pi, int filterMode, int numMappingsShort, int numMappingsSegment, int chainGap,
+                          int blockLength, int nContigs, const int32_t* contigLens, const mm_mapping* recs, size_t nRecs, const int32_t* readLens,
+                          size_t nReads, int32_t firstSeqCounter, int maxRecords, mm_chain_row* out, size_t cap, const int32_t* refGroup, int split) {
   skch::Parameters p;
   p.kmerSize = k; p.segLength = segLength; p.block_length = blockLength; p.chain_gap = chainGap; p.sketchSize = sketchSize;
   p.percentageIdentity = pi; p.filterMode = filterMode;
   p.numMappingsForSegment = (uint32_t)numMappingsSegment; p.numMappingsForShortSequence = (uint32_t)numMappingsShort;
+  p.skip_prefix = refGroup != nullptr; p.split = split != 0;
   std::vector<skch::ContigInfo> meta((size_t)nContigs);
   for (int i = 0; i < nContigs; i++) meta[i] = skch::ContigInfo{"c" + std::to_string(i), contigLens[i]};
   std::vector<int> grp((size_t)nContigs, 0);
+  if (refGroup) grp.assign(refGroup, refGroup + nContigs);
   skch::MapPost post(p, meta, grp);
   int64_t n = 0;
   skch::MappingResultsVector_t v;
@@ -149,6 +170,20 @@ int64_t mmh_chain_rows(int k, int segLength, int sketchSize, float pi, int filte
     i = j;
   }
   return n;
+}
+// the checker of the device rows in tests/test_gpu_chain.py
+int64_t mmh_chain_rows(int k, int segLength, int sketchSize, float pi, int filterMode, int numMappingsShort, int numMappingsSegment, int chainGap,
+                       int blockLength, int nContigs, const int32_t* contigLens, const mm_mapping* recs, size_t nRecs, const int32_t* readLens,
+                       size_t nReads, int32_t firstSeqCounter, int maxRecords, mm_chain_row* out, size_t cap) {
+  return chain_rows(k, segLength, sketchSize, pi, filterMode, numMappingsShort, numMappingsSegment, chainGap, blockLength, nContigs, contigLens, recs, nRecs, readLens,
+                    nReads, firstSeqCounter, maxRecords, out, cap, nullptr, 1);
+}
+// ... and for the modes MM_OPT_CHAIN_MODES adds, in tests/test_gpu_chain_modes.py
+int64_t mmh_chain_rows_modes(int k, int segLength, int sketchSize, float pi, int filterMode, int numMappingsShort, int numMappingsSegment, int chainGap,
+                             int blockLength, int nContigs, const int32_t* contigLens, const mm_mapping* recs, size_t nRecs, const int32_t* readLens,
+                             size_t nReads, int32_t firstSeqCounter, int maxRecords, mm_chain_row* out, size_t cap, const int32_t* refGroup, int split) {
+  return chain_rows(k, segLength, sketchSize, pi, filterMode, numMappingsShort, numMappingsSegment, chainGap, blockLength, nContigs, contigLens, recs, nRecs, readLens,
+                    nReads, firstSeqCounter, maxRecords, out, cap, refGroup, split);
 }
 
 // slots of the all-gatherv of candidate mappings (mm_exchange_plan.h, what mm_comm.hip places its RCCL broadcasts by): disp[world + 1]

@@ -89,8 +89,10 @@ class Map {
   // finished plus the records of the reads it handed over, instead of every record; the post stage finishes both kinds.  Only in a run
   // with one context, split reads, no reference groups (-Y), filter mode map or one-to-one, sketchSize <= MM_CHAIN_MAX_SKETCH and a
   // chain gap the stage takes; anywhere else the switch does nothing.  With the value `long` the context additionally gets
-  // MM_OPT_CHAIN_LONG: reads of 17 .. 512 records are chained on the device too, and only reads above 512 are handed over
-  bool deviceChain = false, deviceChainLong = false;
+  // MM_OPT_CHAIN_LONG: reads of 17 .. 512 records are chained on the device too, and only reads above 512 are handed over.  With the
+  // value `all` it gets MM_OPT_CHAIN_LONG and MM_OPT_CHAIN_MODES, and the condition "split reads, no reference groups" falls away: the
+  // stage then runs under -Y and --noSplit as well (the reference-axis filter of one-to-one stays on the host)
+  bool deviceChain = false, deviceChainLong = false, deviceChainModes = false;
   bool exchangeFellBack = false;                 // a default RCCL all-gatherv failed once: per-context downloads for the rest of the run
   skch::Time::time_point tStart = skch::Time::now();   // MASHMAP_HIP_TIMING lines carry the time since the Map was constructed
   // one write per diagnostic line: three stages log at once, and `std::cerr << a << b` from two threads interleaves inside a line
@@ -138,7 +140,9 @@ class Map {
       if (mm_set_tables(c, minHits.data(), minHits.size(), cut32.data(), cut32.size()) != MM_OK) die("mm_set_tables", c);
       if (mm_set_replay_tables(c, accept.data(), minIsz.data(), (size_t)p.sketchSize + 1) != MM_OK) die("mm_set_replay_tables", c);
     }
-    if (getenv("MASHMAP_HIP_DEVICE_CHAIN") && ctxs.size() == 1 && p.split && !p.skip_prefix && (p.filterMode == filter::MAP || p.filterMode == filter::ONETOONE) &&
+    const char* chainEnv = getenv("MASHMAP_HIP_DEVICE_CHAIN");
+    const bool chainAll = chainEnv && std::strcmp(chainEnv, "all") == 0;
+    if (chainEnv && ctxs.size() == 1 && (chainAll || (p.split && !p.skip_prefix)) && (p.filterMode == filter::MAP || p.filterMode == filter::ONETOONE) &&
         p.sketchSize <= MM_CHAIN_MAX_SKETCH && p.chain_gap >= 0 && p.chain_gap <= MM_CHAIN_MAX_GAP) {
       const size_t stride = (size_t)p.sketchSize + 1;
       std::vector<float> identity(stride * stride);
@@ -146,9 +150,13 @@ class Map {
       const mm_chain_params cp = post.chainParams();
       if (mm_set_chain_tables(ctx, &cp, identity.data(), stride) != MM_OK) die("mm_set_chain_tables");
       deviceChain = true;
-      if (std::strcmp(getenv("MASHMAP_HIP_DEVICE_CHAIN"), "long") == 0) {
+      if (std::strcmp(chainEnv, "long") == 0 || chainAll) {
         if (mm_set_option(ctx, MM_OPT_CHAIN_LONG, 1) != MM_OK) die("mm_set_option(MM_OPT_CHAIN_LONG)");
         deviceChainLong = true;
+      }
+      if (chainAll) {
+        if (mm_set_option(ctx, MM_OPT_CHAIN_MODES, 1) != MM_OK) die("mm_set_option(MM_OPT_CHAIN_MODES)");
+        deviceChainModes = true;
       }
     }
     if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] integer tables ready" << (deviceChain ? " (chaining on the device)" : "") << at();
@@ -430,13 +438,14 @@ class Map {
       releaseBuffers();
     }
     size_t n = 0;
-    uint64_t longOffered = 0, longFinished = 0;
+    uint64_t longOffered = 0, longFinished = 0, groupReads = 0, groupRuns = 0;
     const auto p2 = skch::Time::now();
     if (nCtx == 1 && deviceChain) {
       // rows of the reads the device finished + records of the reads it handed over, instead of every record
       if (mm_chain_reads(ctx) != MM_OK) die("mm_chain_reads");
       if (mm_chain_counts(ctx, nullptr, nullptr, &nRows, &n) != MM_OK) die("mm_chain_counts");
       if (deviceChainLong && mm_chain_long_counts(ctx, &longOffered, &longFinished) != MM_OK) die("mm_chain_long_counts");
+      if (deviceChainModes && mm_chain_group_counts(ctx, &groupReads, &groupRuns) != MM_OK) die("mm_chain_group_counts");
       allRows->resize(nRows); all->resize(n);
       if (nRows && mm_chain_download(ctx, allRows->data(), nRows, &nRows) != MM_OK) die("mm_chain_download");
       if (n && mm_chain_leftover_download(ctx, all->data(), n, &n) != MM_OK) die("mm_chain_leftover_download");
@@ -486,7 +495,8 @@ class Map {
                           << (deviceChain ? " left-over candidate mappings and " + std::to_string(nRows) + " chained rows): " : std::string(" candidate mappings): "))
                           << std::chrono::duration<double>(skch::Time::now() - t0).count() << " s (upload " << phase[0] << ", kernels " << phase[1]
                           << ", download " << std::chrono::duration<double>(skch::Time::now() - p2).count() << ") [bases " << passBases << "] [batches " << nB << "]"
-                          << (deviceChainLong ? " [" + std::to_string(longFinished) + " of " + std::to_string(longOffered) + " reads of more than 16 records chained on the device]" : std::string()) << at();
+                          << (deviceChainLong ? " [" + std::to_string(longFinished) + " of " + std::to_string(longOffered) + " reads of more than 16 records chained on the device]" : std::string())
+                          << (deviceChainModes ? " [" + std::to_string(groupRuns) + " group runs filtered on the device, " + std::to_string(groupReads) + " reads with more than one]" : std::string()) << at();
   }
 
   // post stage: per read, chaining + filters + PAF text on param.threads threads; then output in input order

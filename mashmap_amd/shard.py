@@ -36,6 +36,10 @@ def host_lib():
         lib.mmh_chain_rows.restype = C.c_int64
         lib.mmh_chain_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_int, C.c_void_p, C.c_size_t]
+        lib.mmh_chain_rows_modes.restype = C.c_int64                 # ... under -Y (refGroup) and --noSplit (split = 0)
+        lib.mmh_chain_rows_modes.argtypes = lib.mmh_chain_rows.argtypes + [C.c_void_p, C.c_int]
+        lib.mmh_post_chained_modes.restype = C.c_int64
+        lib.mmh_post_chained_modes.argtypes = lib.mmh_post_chained.argtypes + [C.c_void_p, C.c_int]
         _host = lib
     return _host
 

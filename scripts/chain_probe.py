@@ -20,6 +20,18 @@ alternating, with the stage lines of MASHMAP_HIP_TIMING ('time spent mapping the
 Every run has a time limit (--run-timeout); behind a run that fails or does not end in time nothing more is started: the probe writes
 what it has and exits with a non-zero status.
 
+--groups NAME is a workload of its own, one per invocation (the caller gives every invocation a time limit of its own and starts nothing
+behind one that failed): MM_OPT_CHAIN_MODES on a reference of 8 groups -- S0#1#chr .. S7#1#chr, copies of one 12 Mbp sequence with
+0 .. 3.5 % substitutions -- at segLength 5000:
+  y10k      200 000 reads of 10 kbp under -Y '#' (MM_FLAG_SKIP_PREFIX): a record per fragment and group, about 14 a read
+  y50k      40 000 reads of 50 kbp under -Y '#': about 70 a read, the wave-per-read kernel's
+  nosplit   100 000 reads of 12 kbp under --noSplit (MM_FLAG_NO_SPLIT)
+Three alternations on the same resident records of
+  A  the stage as it was: download all records, the host stage (mmh_post_chained_modes without rows) on 16 threads
+  C  MM_OPT_CHAIN_LONG and MM_OPT_CHAIN_MODES set: mm_chain_reads, download rows and left-over records, the host stage on both
+The reported mappings of the two forms must be byte-identical: the probe stops before it prints a time when they are not.  --scale
+shrinks the read counts; --device-only measures form C's device milliseconds alone (the A/B of two builds of the library).
+
 Prints one JSON document (and writes it to --out).  Every figure is read against form A / the run without the switch of the SAME run."""
 import argparse
 import ctypes as C
@@ -210,6 +222,90 @@ def part2(torch, dev, W, nreads, ref_np, contigs, out, run_timeout):
         shutil.rmtree(td, ignore_errors=True)
 
 
+GROUP_WORKLOADS = {"y10k": dict(reads=200_000, read_len=10_000, nosplit=False), "y50k": dict(reads=40_000, read_len=50_000, nosplit=False),
+                   "nosplit": dict(reads=100_000, read_len=12_000, nosplit=True)}
+
+
+def groups_part(torch, dev, name, out, scale=1.0, device_only=False):
+    from mashmap_amd import capi, shard
+    host = shard.host_lib()
+    W, G = WORKLOADS["configs1"], GROUP_WORKLOADS[name]
+    K, SEG, S, PI, L = W["k"], W["seg"], W["sketch"], W["pi"], G["read_len"]
+    nreads = max(1000, int(G["reads"] * scale))
+    base = make_reference(torch, dev, 1, 12_000_000, seed=7)[0]
+    gen = torch.Generator(device=dev); gen.manual_seed(77)
+    lut = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device=dev)
+    contigs = []
+    for g in range(8):                                              # group g: i.i.d. substitutions at 0.5 % x g
+        c = base.clone()
+        if g:
+            hit = torch.rand(len(c), generator=gen, device=dev) < 0.005 * g
+            c[hit] = lut[torch.randint(0, 4, (int(hit.sum()),), generator=gen, device=dev)]
+        contigs.append(c)
+    ref_np = contiguous_views(torch, contigs)
+    grouped = not G["nosplit"]
+    ref_group = np.arange(8, dtype=np.int32) if grouped else None   # S0#1#chr .. S7#1#chr: a group a contig
+    ctx = capi.Context(k=K, segLength=SEG, sketchSize=S, flags=capi.MM_FLAG_HG_FILTER | (capi.MM_FLAG_SKIP_PREFIX if grouped else capi.MM_FLAG_NO_SPLIT))
+    ctx.index_build(ref_np, ref_group, 0.001)
+    ctx.set_tables_default(PI)
+    ctx.set_chain_tables(SEG, 1, 0, 0, True, capi.MM_CHAIN_FILTER_QUERY, 0.0)
+    reads_t = make_reads(torch, dev, contigs, nreads, L, W["err"], seed=4343, chunk=max(64, 8192 * 10000 // L))
+    torch.cuda.synchronize()
+    offs = np.arange(nreads + 1, dtype=np.int64) * L
+    ctx.reads_upload_device(reads_t.data_ptr(), reads_t.numel(), offs, np.full(nreads, -1, dtype=np.int32), np.full(nreads, -1, dtype=np.int32))
+    del reads_t
+    ctx.map(); ctx.synchronize()
+    clens = np.array([len(a) for a in ref_np], dtype=np.int32); rl = np.full(nreads, L, dtype=np.int32)
+    rg_ptr = ref_group.ctypes.data if grouped else None
+    split = 0 if G["nosplit"] else 1
+    ev = StreamEvents(ctx.lib.mm_stream(ctx.h))
+    ctx.chain_long(True); ctx.chain_modes(True)
+    row_dt = np.dtype([("i", "<i4", 10), ("f", "<f4", 2)])
+
+    def host_stage(rows, recs, cap):
+        res = np.zeros(cap, dtype=row_dt)
+        c0 = cpu_seconds(); t0 = time.perf_counter()
+        n = host.mmh_post_chained_modes(K, SEG, S, PI, 1, 1, 1, 1, SEG, SEG, len(clens), clens.ctypes.data, rows.ctypes.data if rows is not None and len(rows) else None,
+                                        0 if rows is None else len(rows), recs.ctypes.data if len(recs) else None, len(recs), rl.ctypes.data, nreads, 0, THREADS, None,
+                                        res.ctypes.data, None, None, cap, rg_ptr, split)
+        return res[:n], round((time.perf_counter() - t0) * 1e3, 3), round(cpu_seconds() - c0, 4)
+
+    forms = {"C": []} if device_only else {"A": [], "C": []}
+    recs = None
+    for rep in range(3):
+        if not device_only:
+            t0 = time.perf_counter()
+            recs = ctx.mappings()
+            dl = time.perf_counter() - t0
+            rep_a, host_ms, cpu_s = host_stage(None, recs, len(recs) + 1)
+            a = dict(device_ms=0.0, download_ms=round(dl * 1e3, 3), download_bytes=int(recs.nbytes), host_ms=host_ms, host_cpu_s=cpu_s, reported=int(len(rep_a)), records=int(len(recs)))
+        ev.start(); t0 = time.perf_counter()
+        ctx.chain_reads()
+        wall_stage = time.perf_counter() - t0
+        dev_ms = ev.elapsed()
+        cnt, lcnt, gcnt = ctx.chain_counts(), ctx.chain_long_counts(), ctx.chain_group_counts()
+        c = dict(device_ms=dev_ms, stage_wall_ms=round(wall_stage * 1e3, 3), offered=cnt["offered"], finished=cnt["finished"], rows=cnt["rows"], leftover_records=cnt["leftover"],
+                 long_offered=lcnt["offered"], long_finished=lcnt["finished"], group_reads=gcnt["reads"], group_runs=gcnt["runs"])
+        if not device_only:
+            t0 = time.perf_counter()
+            rows = ctx.chain_rows(); left = ctx.chain_leftover()
+            dl = time.perf_counter() - t0
+            rep_c, host_ms, cpu_s = host_stage(rows, left, len(recs) + 1)
+            if rep_a.tobytes() != rep_c.tobytes():                  # before any time is printed
+                raise SystemExit("chain_probe.py --groups %s: the reported mappings of form C differ from form A's (%d against %d)" % (name, len(rep_c), len(rep_a)))
+            c.update(download_ms=round(dl * 1e3, 3), download_bytes=int(rows.nbytes + left.nbytes), host_ms=host_ms, host_cpu_s=cpu_s, reported=int(len(rep_c)), same_as_A=True)
+            forms["A"].append(a)
+            log("[chain_probe] %s, alternation %d: A %r" % (name, rep, a))
+        forms["C"].append(c)
+        log("[chain_probe] %s, alternation %d: C %r" % (name, rep, c))
+    res = dict(reads=nreads, read_len=L, flags="-Y '#'" if grouped else "--noSplit", host_threads=THREADS, forms=forms)
+    if recs is not None:
+        nrec = np.bincount(recs["querySeqId"], minlength=nreads)
+        res["records_per_read"] = {"mean": round(float(nrec.mean()), 3), "max": int(nrec.max()), "reads_above_16": int((nrec > 16).sum()), "reads_above_512": int((nrec > 512).sum())}
+    out["groups_" + name] = res
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=WORKLOADS["configs1"]["reads"])
@@ -219,6 +315,9 @@ def main():
     ap.add_argument("--chain-long", action="store_true", help="form C (MM_OPT_CHAIN_LONG) in part 1, and part 1 again on the long-read workload")
     ap.add_argument("--long-reads", type=int, default=20000, help="reads of the long-read workload (20 000 x 100 kbp: about 400 000 records)")
     ap.add_argument("--long-read-len", type=int, default=100000)
+    ap.add_argument("--groups", choices=sorted(GROUP_WORKLOADS), default=None, help="the MM_OPT_CHAIN_MODES workload of that name alone (8 reference groups)")
+    ap.add_argument("--scale", type=float, default=1.0, help="--groups: share of the workload's reads")
+    ap.add_argument("--device-only", action="store_true", help="--groups: form C's device milliseconds alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -228,6 +327,15 @@ def main():
     torch.zeros(1, device=dev).cpu()
     W = WORKLOADS["configs1"]
     out = {"workload": W["label"]}
+    if a.groups:
+        groups_part(torch, dev, a.groups, out, a.scale, a.device_only)
+        text = json.dumps(out, indent=1)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
     ref_np, contigs = part1(torch, dev, W, a.reads, out, chain_long=a.chain_long)
     if a.chain_long:
         part1(torch, dev, W, a.long_reads, out, chain_long=True, L=a.long_read_len, key="long_reads", ref=(ref_np, contigs))
