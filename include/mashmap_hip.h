@@ -582,6 +582,41 @@ const char* mm_kernel_name(int which);
 /* integer-roofline yardstick: a kernel that does nothing but the 2 x MurmurHash3_x64_128 per position of
  * every resident fragment (both strands, same tables and staging as the sketch kernel); *msAvg = average of `reps` launches */
 int mm_bench_hash_only(mm_ctx* ctx, int reps, double* msAvg);
+/*
+ * BGZF blocks inflated on the device (k_inflate_blocks, mashmap_amd/csrc/mm_inflate.hip; the decoder is mashmap_amd/csrc/mm_inflate_core.h,
+ * which tests/hostlogic/inflate_check.cpp runs against zlib on the host).  A BGZF block (SAM specification, section 4.1) is an independent
+ * raw-deflate stream of at most 64 KiB, compressed and inflated, followed by the CRC-32 and the length of its payload: one
+ * mm_inflate_block names the stream (comp + cOff, cLen bytes), where its payload goes (dst + uOff, uLen bytes) and the CRC-32 the payload
+ * must have.  mm_inflate_blocks copies the compressed bytes the descriptors span to the device, inflates every block on a wave of its
+ * own (any number of stored, fixed and dynamic deflate blocks up to BFINAL), checks length and CRC-32, copies every payload to its place
+ * in dst and writes every descriptor's status: MM_INFLATE_OK, or why the block was refused -- BAD_STREAM (block type 3, a stored length
+ * that is not its complement's, more than 286 literal/length or 30 distance codes, a repeat code with nothing to repeat or past the end,
+ * an over-subscribed or -- other than zlib allows -- incomplete code, no end-of-block code, a code that is not assigned, symbols 286 / 287
+ * / 30 / 31), TRUNCATED (the cLen bytes end inside the stream), OVERRUN (more than uLen bytes), SHORT (BFINAL's block ends before uLen),
+ * BAD_DISTANCE (a match that starts before the block's first byte), BAD_CRC.  The bytes of a refused block's own range in dst are
+ * unspecified; nothing outside the descriptors' ranges is written.  A block with uLen == 0 is decoded and checked like any other (the
+ * BGZF end-of-file block is one).  *nBad (may be NULL) receives the number of refused blocks.
+ * comp and dst are host pointers; page-locked memory (mm_host_alloc) makes both copies DMA transfers at PCIe rate, any host pointer
+ * works.  The call needs a context only -- no index, no reads --, touches neither the resident batch nor its results, and runs on a
+ * stream of its own: it joins the exception mm_reads_prefetch makes to "a ctx is thread-compatible" -- a reader thread may call it while
+ * the context's own thread is inside any other call; against itself it is serialised inside the library.  It returns when dst is filled.
+ * The text of a failed call is kept per calling thread: mm_last_error gives it when called next on that thread for that context.
+ * MM_ERR_ARG, before anything is launched: a descriptor whose ranges leave nComp or nDst, uLen or cLen above MM_INFLATE_MAX_BLOCK, output
+ * ranges that overlap.  MM_OK whenever the kernel ran (and for nBlocks == 0, which launches nothing): the status fields say the rest.
+ * The staging buffers belong to the context: they count in mm_device_bytes and go with mm_destroy.
+ * mm_inflate_counts: the context's calls that returned MM_OK so far, the blocks they named and the payload
+ * bytes of the blocks that were MM_INFLATE_OK -- the last two are kept by the kernel on the device, beside its count of refused blocks.
+ * mm_inflate_kernel_ms: device time of the last call's kernel alone (hipEvents on the inflate stream), 0 before the first call.
+ * Purely additive: MM_ABI_VERSION stays 2.
+ */
+#define MM_INFLATE_MAX_BLOCK 65536           /* BGZF's bound, both ways */
+enum { MM_INFLATE_OK = 0, MM_INFLATE_BAD_STREAM, MM_INFLATE_TRUNCATED, MM_INFLATE_OVERRUN,
+       MM_INFLATE_SHORT, MM_INFLATE_BAD_DISTANCE, MM_INFLATE_BAD_CRC };
+typedef struct { uint64_t cOff; uint32_t cLen, uLen; uint64_t uOff; uint32_t crc32, status; } mm_inflate_block;  /* 32 bytes */
+int mm_inflate_blocks(mm_ctx* ctx, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks,
+                      void* dst, size_t nDst, size_t* nBad);
+int mm_inflate_counts(const mm_ctx* ctx, uint64_t* calls, uint64_t* blocks, uint64_t* bytesOut);
+int mm_inflate_kernel_ms(const mm_ctx* ctx, double* ms);
 /* diagnostic: bytes of device memory the library holds at this moment, over every context of the process (their indexes, batches of
  * reads -- the parked ones included --, staging buffers) and the scratch of a call in progress.  Counted where the library allocates and
  * frees, not asked of the device: memory other libraries or processes hold is not in it.  After the last mm_destroy it is 0.  May be

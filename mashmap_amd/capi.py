@@ -65,6 +65,11 @@ MAPPING_DT = np.dtype([("querySeqId", "<i4"), ("fragStart", "<i4"), ("fragLen", 
                        ("conservedSketches", "<i4"), ("sketchSize", "<i4"), ("strand", "<i4"), ("rawSketchSize", "<i4"), ("pad", "<i4"),
                        ("maxHash", "<u8")])
 COMM_ID_BYTES = 128
+# mm_inflate_block (32 bytes) and the MM_INFLATE_* status values
+INFLATE_BLOCK_DT = np.dtype([("cOff", "<u8"), ("cLen", "<u4"), ("uLen", "<u4"), ("uOff", "<u8"), ("crc32", "<u4"), ("status", "<u4")])
+MM_INFLATE_MAX_BLOCK = 65536
+MM_INFLATE_OK, MM_INFLATE_BAD_STREAM, MM_INFLATE_TRUNCATED, MM_INFLATE_OVERRUN, MM_INFLATE_SHORT, MM_INFLATE_BAD_DISTANCE, MM_INFLATE_BAD_CRC = range(7)
+INFLATE_STATUS = ["OK", "BAD_STREAM", "TRUNCATED", "OVERRUN", "SHORT", "BAD_DISTANCE", "BAD_CRC"]
 L2_DT = np.dtype([("frag", "<i4"), ("cand", "<i4"), ("seqId", "<i4"), ("meanOptimalPos", "<i4"),
                   ("optimalStart", "<i4"), ("optimalEnd", "<i4"), ("sharedSketchSize", "<i4"), ("strand", "<i4")])
 assert MAPPING_DT.itemsize == 48 and MINMER_DT.itemsize == 24 and POINT_DT.itemsize == 24 and STATS_DT.itemsize == 24 and L2_DT.itemsize == 32
@@ -173,6 +178,9 @@ def load():
         "mm_chain_leftover_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
         "mm_device_bytes": (sz, []),
+        "mm_inflate_blocks": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, C.POINTER(sz)]),
+        "mm_inflate_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_inflate_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "mm_synchronize": (C.c_int, [vp]),
         "mm_stream": (vp, [vp]),
     }
@@ -202,7 +210,7 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
            "mm_stat_identity_table", "mm_set_chain_tables", "mm_chain_reads", "mm_chain_counts", "mm_chain_download",
            "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts", "mm_device_bytes",
-           "mm_sketch_large_counts", "mm_chain_group_counts"]
+           "mm_sketch_large_counts", "mm_chain_group_counts", "mm_inflate_blocks", "mm_inflate_counts", "mm_inflate_kernel_ms"]
 
 
 def device_bytes():
@@ -696,6 +704,62 @@ class Context:
         ms = C.c_double()
         self._ck(self.lib.mm_bench_hash_only(self.h, reps, C.byref(ms)), "mm_bench_hash_only")
         return ms.value
+
+    # ---- BGZF blocks inflated on the device (mm_inflate_blocks)
+    def inflate_blocks(self, comp, blocks, dst=None):
+        """comp: the compressed bytes; blocks: INFLATE_BLOCK_DT records (cOff, cLen, uLen, uOff, crc32; their status fields are
+        written).  dst: a writable uint8 array the payloads go into (bytes outside the blocks' ranges are left alone); None: one
+        of the size the blocks need.  Returns (dst, statuses); MashmapError for what the library refuses before launching."""
+        comp = np.frombuffer(comp, dtype=np.uint8) if not isinstance(comp, np.ndarray) else np.ascontiguousarray(comp, dtype=np.uint8)
+        blocks = np.ascontiguousarray(blocks, dtype=INFLATE_BLOCK_DT)
+        if dst is None:
+            dst = np.zeros(int((blocks["uOff"] + blocks["uLen"]).max()) if len(blocks) else 0, dtype=np.uint8)
+        if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.c_contiguous and dst.flags.writeable):
+            raise MashmapError("inflate_blocks: dst must be a writable contiguous uint8 array")
+        bad = C.c_size_t(0)
+        self._ck(self.lib.mm_inflate_blocks(self.h, _ptr(comp) if len(comp) else None, len(comp), _ptr(blocks) if len(blocks) else None, len(blocks),
+                                            _ptr(dst) if len(dst) else None, len(dst), C.byref(bad)), "mm_inflate_blocks")
+        self.inflate_bad = int(bad.value)
+        return dst, blocks["status"].copy()
+
+    def inflate_bgzf(self, data):
+        """the payload of a BGZF file held in `data` (bytes): the framing (gzip members with a 'BC' extra subfield, SAM specification 4.1)
+        is read here, the blocks are inflated and checked on the device.  MashmapError names the first bad block."""
+        data = bytes(data)
+        recs, at, uoff = [], 0, 0
+        while at < len(data):
+            if len(data) - at < 18 or data[at] != 31 or data[at + 1] != 139 or data[at + 2] != 8 or not data[at + 3] & 4:
+                raise MashmapError("inflate_bgzf: block %d (at byte %d) has no BGZF header" % (len(recs), at))
+            xlen = data[at + 10] | data[at + 11] << 8
+            bsize, x, xe = None, at + 12, at + 12 + xlen
+            while x + 4 <= min(xe, len(data)):
+                slen = data[x + 2] | data[x + 3] << 8
+                if data[x] == 66 and data[x + 1] == 67 and slen == 2 and x + 6 <= len(data):
+                    bsize = (data[x + 4] | data[x + 5] << 8) + 1
+                x += 4 + slen
+            if bsize is None or bsize < 12 + xlen + 8 or at + bsize > len(data):
+                raise MashmapError("inflate_bgzf: block %d (at byte %d) is malformed or truncated" % (len(recs), at))
+            crc = int.from_bytes(data[at + bsize - 8:at + bsize - 4], "little"); isize = int.from_bytes(data[at + bsize - 4:at + bsize], "little")
+            if isize > MM_INFLATE_MAX_BLOCK:
+                raise MashmapError("inflate_bgzf: block %d (at byte %d) claims %d bytes" % (len(recs), at, isize))
+            recs.append((at + 12 + xlen, bsize - 12 - xlen - 8, isize, uoff, crc, 0, at))
+            uoff += isize; at += bsize
+        blocks = np.array([r[:6] for r in recs], dtype=INFLATE_BLOCK_DT)
+        out, status = self.inflate_blocks(data, blocks, np.zeros(uoff, dtype=np.uint8))
+        for i in np.flatnonzero(status):
+            raise MashmapError("inflate_bgzf: block %d (at byte %d) is corrupt: %s" % (i, recs[i][6], INFLATE_STATUS[int(status[i])] if status[i] < 7 else int(status[i])))
+        return out.tobytes()
+
+    def inflate_counts(self):
+        """(calls, blocks, payload bytes of the blocks that were fine) of this context's mm_inflate_blocks so far"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.mm_inflate_counts(self.h, C.byref(a), C.byref(b), C.byref(c)), "mm_inflate_counts")
+        return int(a.value), int(b.value), int(c.value)
+
+    def inflate_kernel_ms(self):
+        v = C.c_double(0)
+        self._ck(self.lib.mm_inflate_kernel_ms(self.h, C.byref(v)), "mm_inflate_kernel_ms")
+        return float(v.value)
 
     def synchronize(self):
         self._ck(self.lib.mm_synchronize(self.h), "mm_synchronize")

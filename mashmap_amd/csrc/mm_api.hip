@@ -35,7 +35,10 @@ int mm_abi_version(void) { return MM_ABI_VERSION; }
 size_t mm_device_bytes(void) { return g_mmDeviceBytes.load(); }
 const char* mm_kernel_name(int which) { return (which >= 0 && which < MM_K_COUNT) ? kKernelNames[which] : "?"; }
 
-const char* mm_last_error(const mm_ctx* ctx) { return ctx ? ctx->err.c_str() : g_createErr.c_str(); }
+const char* mm_last_error(const mm_ctx* ctx) {
+  if (const char* t = mm_inflate_take_error(ctx)) return t;     // this thread's mm_inflate_blocks failed last on ctx: its own text, kept per thread
+  return ctx ? ctx->err.c_str() : g_createErr.c_str();
+}
 
 int mm_create(mm_ctx** out, int device, const mm_params* p) {
   if (!out || !p) { g_createErr = "mm_create: null argument"; return MM_ERR_ARG; }
@@ -77,6 +80,9 @@ void mm_destroy(mm_ctx* c) {
   if (c->commStream) (void)hipStreamDestroy(c->commStream);
   if (c->copyStream) { (void)hipStreamSynchronize(c->copyStream); (void)hipStreamDestroy(c->copyStream); }
   if (c->copyDone) (void)hipEventDestroy(c->copyDone);
+  if (c->inflateStream) { (void)hipStreamSynchronize(c->inflateStream); (void)hipStreamDestroy(c->inflateStream); }
+  if (c->infEvA) (void)hipEventDestroy(c->infEvA);
+  if (c->infEvB) (void)hipEventDestroy(c->infEvB);
   if (c->hPass) (void)hipHostFree(c->hPass);
   if (c->hSkLarge) (void)hipHostFree(c->hSkLarge);
   if (c->skLargeDone) (void)hipEventDestroy(c->skLargeDone);

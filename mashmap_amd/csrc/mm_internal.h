@@ -243,6 +243,12 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   struct StagedPart { const void* b2; const void* nm; size_t nPacked; size_t off; };   // packed parts sent ahead (mm_reads_prefetch_packed[_append]): [codes | mask] at dAsciiNext + off
   std::vector<StagedPart> staged; size_t stagedBytes = 0;
   std::mutex prefetchMu;                                // mm_reads_prefetch* may come from another thread than the uploads (a reader thread): the staging state is shared
+  // mm_inflate_blocks (mm_inflate.hip): a stream, a lock and staging of its own -- a reader thread calls it beside the context's own thread
+  DevBuf dInfComp, dInfOut, dInfDesc, dInfStatus, dInfStats;   // compressed span, payloads packed end to end, descriptors, one status word per block, [next block | blocks, bytes out, bad blocks]
+  hipStream_t inflateStream = nullptr; hipEvent_t infEvA = nullptr, infEvB = nullptr;
+  mutable std::mutex inflateMu;
+  std::vector<mm_inflate_block> infDesc; std::vector<uint32_t> infOrder, infStatus;
+  uint64_t infCalls = 0, infBlocks = 0, infBytes = 0, infBad = 0; double infKernelMs = 0; int infGrid = 0;
   ReadBatch parked[MM_BATCH_SLOTS];                     // batches parked beside the resident one (mm_reads_exchange)
 
   // sketches: raw (a4) and after frequent-seed removal (a8)
@@ -301,6 +307,7 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   std::vector<std::pair<int, size_t>> evPending;                              // (kernel, pool index)
 };
 
+const char* mm_inflate_take_error(const mm_ctx* c);     // mm_inflate.hip: the text of this thread's failed mm_inflate_blocks on c, once; else null
 // the resident batch changed (an upload, an exchange): nothing sketched, mapped or gathered belongs to it
 inline void mm_batch_changed(mm_ctx* c) { c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false; }
 

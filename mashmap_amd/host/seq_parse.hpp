@@ -12,7 +12,7 @@
 // lengths, a prefix sum places them, and the threads copy the sequence bytes -- without the line breaks -- straight into the batch
 // buffer (pinned host memory when the caller provides an allocator, so that the upload to the GPU is one DMA).  Plain files are
 // mmap'ed; BGZF files (bgzip: independent <= 64 KiB deflate blocks, htslib's format -- the reference's data directory ships .gzi
-// indexes of such files) are inflated block-parallel; any other gzip stream is inflated by one thread ahead of the parsers.
+// indexes of such files) are inflated block-parallel -- by zlib on the pool, or by a block inflater the caller sets (BatchReader::setBlockInflater) --; any other gzip stream is inflated by one thread ahead of the parsers.
 #pragma once
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -90,7 +90,53 @@ struct ParsedBatch {
   uint32_t* nmask() const { return (uint32_t*)(bases + maskBase / 4); }
 };
 
+// One BGZF block for an optional block inflater: the compressed stream comp + cOff (cLen bytes), where its payload goes (dst + uOff,
+// uLen bytes), the CRC-32 the payload must have, and the inflater's verdict (0: fine).  Field for field the C ABI's mm_inflate_block,
+// restated here so that this header stays free of that ABI (skch_sketch.hpp, which binds the two, asserts that the layouts agree).
+struct InflateBlock { uint64_t cOff; uint32_t cLen, uLen; uint64_t uOff; uint32_t crc32, status; };
+// inflates and checks blocks[0 .. n), writing every status; false: the inflater itself failed (it has said why)
+typedef std::function<bool(const void* comp, size_t nComp, InflateBlock* blocks, size_t n, void* dst, size_t nDst)> BlockInflater;
+
 namespace detail {
+
+// the bytes of a GzSource: a std::vector, as ever -- or, once pin() has been called (a BGZF file whose blocks go to a block inflater that
+// copies them to and from a device), a buffer from the reader's page-locked allocator pair that grows by doubling and does not
+// zero-fill.  Without pin() nothing differs from the vector it wraps.
+class ByteBuf {
+ public:
+  ByteBuf() = default;
+  ~ByteBuf() { if (p_) free_(p_); }
+  ByteBuf(const ByteBuf&) = delete;
+  ByteBuf& operator=(const ByteBuf&) = delete;
+  void pin(std::function<char*(size_t)> a, std::function<void(char*)> f) { alloc_ = std::move(a); free_ = std::move(f); pinned_ = true; }   // before the first byte
+  char* data() { return pinned_ ? p_ : v_.data(); }
+  size_t size() const { return pinned_ ? n_ : v_.size(); }
+  bool empty() const { return size() == 0; }
+  void clear() { if (pinned_) n_ = 0; else v_.clear(); }
+  void resize(size_t n) {
+    if (!pinned_) { v_.resize(n); return; }
+    if (n > cap_) {
+      const size_t nc = std::max(n + 4096, cap_ * 2);
+      char* q = alloc_(nc);
+      if (!q) { std::cerr << "[mashmap_hip] out of page-locked host memory for " << nc << " bytes of BGZF input" << std::endl; exit(1); }
+      if (n_) std::memcpy(q, p_, n_);
+      if (p_) free_(p_);
+      p_ = q; cap_ = nc;
+    }
+    n_ = n;
+  }
+  void erase_front(size_t k) {
+    if (!pinned_) { v_.erase(v_.begin(), v_.begin() + (std::ptrdiff_t)std::min(k, v_.size())); return; }
+    if (k >= n_) { n_ = 0; return; }
+    std::memmove(p_, p_ + k, n_ - k); n_ -= k;
+  }
+
+ private:
+  std::vector<char> v_;
+  bool pinned_ = false;
+  std::function<char*(size_t)> alloc_; std::function<void(char*)> free_;
+  char* p_ = nullptr; size_t n_ = 0, cap_ = 0;
+};
 
 }  // namespace detail
 
@@ -330,8 +376,10 @@ class MmapSource : public RawSource {
 class GzSource : public RawSource {
   std::string path_; size_t window_; unsigned threads_; WorkerPool* pool_;
   FILE* raw_ = nullptr; bool bgzf_ = false; gzFile gz_ = nullptr;
-  std::vector<char> buf_; size_t carry_ = 0; bool eof_ = false;
-  std::vector<unsigned char> comp_;
+  BlockInflater inflater_;                        // set: BGZF blocks go to it (and the two buffers are the reader's page-locked memory) instead of zlib on the pool
+  ByteBuf buf_; size_t carry_ = 0; bool eof_ = false;
+  ByteBuf comp_;
+  const bool timing_ = getenv("MASHMAP_HIP_TIMING") != nullptr;
 
   bool fill_stream(size_t want) {
     while (buf_.size() < want && !eof_) {
@@ -351,40 +399,50 @@ class GzSource : public RawSource {
   }
   // BGZF (SAM spec 4.1): gzip member with extra subfield 'B','C' holding BSIZE = block size - 1; payload = raw deflate; trailer CRC32 + ISIZE
   bool fill_bgzf(size_t want) {
-    struct Blk { size_t cOff, cLen, uOff, uLen; uint32_t crc; };
     while (buf_.size() < want && !eof_) {
-      std::vector<Blk> blks; comp_.clear();
+      const auto t0 = std::chrono::steady_clock::now();
+      std::vector<InflateBlock> blks; comp_.clear();
       size_t uTot = 0;
-      while (uTot < (64u << 20)) {
+      // blocks per round: 64 MB for the pool's threads; a block inflater takes what the window still lacks in one call (1 GB at the most)
+      const size_t round = inflater_ ? std::min<size_t>((size_t)1 << 30, std::max<size_t>(64u << 20, want - buf_.size())) : (64u << 20);
+      while (uTot < round) {
         unsigned char h[18];
         if (fread(h, 1, 18, raw_) != 18) { eof_ = true; break; }
         if (h[0] != 31 || h[1] != 139 || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') { std::cerr << "[mashmap_hip] malformed BGZF block in " << path_ << std::endl; exit(1); }
         const size_t bsize = (size_t)h[16] + ((size_t)h[17] << 8) + 1;
         const size_t at = comp_.size(); comp_.resize(at + bsize - 18);
         if (fread(comp_.data() + at, 1, bsize - 18, raw_) != bsize - 18) { std::cerr << "[mashmap_hip] truncated BGZF file " << path_ << std::endl; exit(1); }
-        const unsigned char* t = comp_.data() + at + bsize - 18 - 4;
+        const unsigned char* t = (const unsigned char*)comp_.data() + at + bsize - 18 - 4;
         const size_t isize = (size_t)t[0] | ((size_t)t[1] << 8) | ((size_t)t[2] << 16) | ((size_t)t[3] << 24);
         const uint32_t crc = (uint32_t)t[-4] | ((uint32_t)t[-3] << 8) | ((uint32_t)t[-2] << 16) | ((uint32_t)t[-1] << 24);
-        blks.push_back(Blk{at, bsize - 18 - 8, uTot, isize, crc});
+        blks.push_back(InflateBlock{at, (uint32_t)(bsize - 18 - 8), (uint32_t)isize, uTot, crc, 0});
         uTot += isize;
       }
       const size_t base = buf_.size(); buf_.resize(base + uTot);
       std::atomic<size_t> nextB(0); std::atomic<int> bad(0);
+      if (inflater_) {
+        for (auto& k : blks) k.uOff += base;
+        if (!blks.empty() && !inflater_(comp_.data(), comp_.size(), blks.data(), blks.size(), buf_.data(), buf_.size())) bad = 1;
+        for (const auto& k : blks) if (k.status) bad = 1;
+      } else
       run_parallel(*pool_, std::max(1u, std::min<unsigned>(threads_, (unsigned)blks.size())), [&](unsigned) {
         z_stream zs;
         for (size_t i = nextB.fetch_add(1); i < blks.size(); i = nextB.fetch_add(1)) {
           if (!blks[i].uLen) continue;
           std::memset(&zs, 0, sizeof zs);
           if (inflateInit2(&zs, -15) != Z_OK) { bad = 1; return; }
-          zs.next_in = comp_.data() + blks[i].cOff; zs.avail_in = (uInt)blks[i].cLen;
+          zs.next_in = (Bytef*)comp_.data() + blks[i].cOff; zs.avail_in = (uInt)blks[i].cLen;
           zs.next_out = (Bytef*)(buf_.data() + base + blks[i].uOff); zs.avail_out = (uInt)blks[i].uLen;
           const int rc = inflate(&zs, Z_FINISH);
           inflateEnd(&zs);
           if (rc != Z_STREAM_END || zs.total_out != blks[i].uLen) bad = 1;
-          else if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)(buf_.data() + base + blks[i].uOff), (uInt)blks[i].uLen) != blks[i].crc) bad = 1;   // trailer: CRC32 of the payload
+          else if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)(buf_.data() + base + blks[i].uOff), (uInt)blks[i].uLen) != blks[i].crc32) bad = 1;   // trailer: CRC32 of the payload
         }
       });
       if (bad) { std::cerr << "[mashmap_hip] corrupt BGZF block in " << path_ << std::endl; exit(1); }
+      if (timing_ && !blks.empty())
+        fprintf(stderr, "[mashmap_hip::timing] reader: BGZF %s inflater: %zu blocks, %zu bytes of %s in %.4f s\n", inflater_ ? "device" : "host", blks.size(), uTot, path_.c_str(),
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     }
     return !buf_.empty();
   }
@@ -393,21 +451,27 @@ class GzSource : public RawSource {
   // streamOnly: the path is not a regular file (FIFO, /dev/stdin, process substitution): it can be opened and read exactly once, so
   // there is no sniffing with a handle of its own -- gzopen reads plain data transparently and gzip (BGZF included: concatenated
   // members) by inflating it, which is what the reference's igzstream does with such inputs (src/common/gzstream.h:50)
-  GzSource(const std::string& path, size_t window, unsigned threads, WorkerPool* pool, bool streamOnly = false) : path_(path), window_(window), threads_(threads), pool_(pool) {
+  GzSource(const std::string& path, size_t window, unsigned threads, WorkerPool* pool, bool streamOnly = false, BlockInflater inflater = nullptr,
+           std::function<char*(size_t)> pinAlloc = nullptr, std::function<void(char*)> pinFree = nullptr)
+      : path_(path), window_(window), threads_(threads), pool_(pool) {
     if (streamOnly) { gz_ = gzopen(path.c_str(), "rb"); if (gz_) gzbuffer(gz_, 1u << 20); return; }
     raw_ = fopen(path.c_str(), "rb");
     if (!raw_) return;
     unsigned char h[18] = {0};
     const size_t got = fread(h, 1, 18, raw_);
     bgzf_ = got == 18 && h[0] == 31 && h[1] == 139 && (h[3] & 4) && h[10] == 6 && h[11] == 0 && h[12] == 'B' && h[13] == 'C';
-    if (bgzf_) fseek(raw_, 0, SEEK_SET);
+    if (bgzf_) {
+      fseek(raw_, 0, SEEK_SET);
+      // only a BGZF file has blocks for the hook: then, and only then, the two buffers are the reader's page-locked memory
+      if (inflater && pinAlloc && pinFree) { inflater_ = std::move(inflater); buf_.pin(pinAlloc, pinFree); comp_.pin(pinAlloc, pinFree); }
+    }
     else { fclose(raw_); raw_ = nullptr; gz_ = gzopen(path.c_str(), "rb"); if (gz_) gzbuffer(gz_, 1u << 20); }
   }
   ~GzSource() override { if (raw_) fclose(raw_); if (gz_) gzclose(gz_); }
   bool ok() const { return raw_ || gz_; }
-  char first_byte() override { if (buf_.empty()) { if (bgzf_) fill_bgzf(1); else fill_stream(1); } return buf_.empty() ? 0 : buf_[0]; }
+  char first_byte() override { if (buf_.empty()) { if (bgzf_) fill_bgzf(1); else fill_stream(1); } return buf_.empty() ? 0 : buf_.data()[0]; }
   bool next(const char*& p, size_t& n, bool fasta, bool) override {
-    if (carry_) { buf_.erase(buf_.begin(), buf_.begin() + (std::ptrdiff_t)carry_); carry_ = 0; }
+    if (carry_) { buf_.erase_front(carry_); carry_ = 0; }
     size_t want = window_;
     while (true) {
       if (bgzf_) fill_bgzf(want); else fill_stream(want);
@@ -448,6 +512,9 @@ class BatchReader {
   bool fileDone() const { return fileDone_; }
   size_t splitWindows() const { return splitWindows_; }   // windows that went through parseWindowPackedSplit (records cut across threads)
   void release(ParsedBatch& b) { if (b.bases) free_(b.bases); b.bases = nullptr; b.cap = 0; }
+  // optional: BGZF files opened from here on hand their blocks to `f` instead of inflating them with zlib on the reader's threads, and
+  // keep their compressed and inflated bytes in memory from the reader's allocator pair (page-locked when the caller's is)
+  void setBlockInflater(BlockInflater f) { inflater_ = std::move(f); }
 
   bool next(ParsedBatch& out) {
     out.names.clear(); out.offs.assign(1, 0);
@@ -471,6 +538,7 @@ class BatchReader {
   std::unordered_set<std::string> keepSeq_; std::string keepPrefix_;
   WorkerPool pool_;
   Alloc alloc_; Free free_;
+  BlockInflater inflater_;
   size_t splitWindows_ = 0;
   bool packOutput_ = false;          // batches carry 2-bit codes + N mask (what mm_reads_upload_packed takes) instead of ASCII
   detail::RawSource* src_ = nullptr; size_t nextFile_ = 0, curFile_ = 0; bool fasta_ = true, firstWindow_ = true, fileDone_ = false;
@@ -483,7 +551,7 @@ class BatchReader {
     if (regular) { FILE* f = fopen(path.c_str(), "rb"); if (f) { unsigned char m[2] = {0, 0}; if (fread(m, 1, 2, f) == 2) gz = m[0] == 31 && m[1] == 139; fclose(f); } }
     bool ok = false;
     if (!regular) { auto* s = new detail::GzSource(path, window_, threads_, &pool_, true); ok = s->ok(); src_ = s; }
-    else if (gz) { auto* s = new detail::GzSource(path, window_, threads_, &pool_); ok = s->ok(); src_ = s; }
+    else if (gz) { auto* s = new detail::GzSource(path, window_, threads_, &pool_, false, inflater_, alloc_, free_); ok = s->ok(); src_ = s; }
     else { auto* s = new detail::MmapSource(path, window_); ok = s->ok(); src_ = s; }
     const char c = ok ? src_->first_byte() : 0;
     if (!ok || (c != '>' && c != '@')) {

@@ -162,6 +162,11 @@ class Map {
     if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] integer tables ready" << (deviceChain ? " (chaining on the device)" : "") << at();
     this->mapQuery();
     if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] mapQuery done" << at();
+    if (getenv("MASHMAP_HIP_TIMING")) {
+      uint64_t calls = 0, blocks = 0, bytes = 0;                 // reference and query readers together; all zero unless MASHMAP_HIP_DEVICE_INFLATE=1 met BGZF input
+      if (mm_inflate_counts(ctxs[0], &calls, &blocks, &bytes) == MM_OK)
+        LogLine() << "[mashmap_hip::timing] device inflater: " << calls << " calls, " << blocks << " blocks, " << bytes << " bytes";
+    }
   }
 
   static void insertL2ResultsToVec(MappingResultsVector_t& v, const MappingResult& reportedL2Result) { v.push_back(reportedL2Result); }
@@ -223,6 +228,7 @@ class Map {
                                                                            << std::chrono::duration<double>(skch::Time::now() - t0).count() << " s";
                                return p;
                              }, [](char* p) { mm_host_free(p); }, packedUpload);
+      rd.setBlockInflater(deviceBlockInflater(ctxs[0]));          // MASHMAP_HIP_DEVICE_INFLATE=1: BGZF blocks of the query go to mm_inflate_blocks (its own stream: it runs beside the device stage)
       while (true) {
         Batch batch;
         { auto b = HostBufferPool::instance().take(0); batch.in.bases = b.first; batch.in.cap = b.second; }

@@ -10,6 +10,7 @@
 // request (materializeLookupIndex), because nothing in the device path reads it.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +31,23 @@
 #include "skch_types.hpp"
 
 namespace skch {
+
+// MASHMAP_HIP_DEVICE_INFLATE=1 (read once): the readers hand the blocks of BGZF input to mm_inflate_blocks of `ctx` -- the first context
+// of a run with several -- instead of inflating them with zlib on their own threads.  Unset, or any other value: no hook (an empty
+// function), and nothing of the readers changes.  This is where seq_parse.hpp's InflateBlock meets the C ABI's mm_inflate_block.
+inline mmhost::BlockInflater deviceBlockInflater(mm_ctx* ctx) {
+  static const bool on = [] { const char* e = getenv("MASHMAP_HIP_DEVICE_INFLATE"); return e && atoi(e) == 1; }();
+  if (!on || !ctx) return nullptr;
+  static_assert(sizeof(mmhost::InflateBlock) == sizeof(mm_inflate_block) && offsetof(mmhost::InflateBlock, cOff) == offsetof(mm_inflate_block, cOff) &&
+                offsetof(mmhost::InflateBlock, cLen) == offsetof(mm_inflate_block, cLen) && offsetof(mmhost::InflateBlock, uLen) == offsetof(mm_inflate_block, uLen) &&
+                offsetof(mmhost::InflateBlock, uOff) == offsetof(mm_inflate_block, uOff) && offsetof(mmhost::InflateBlock, crc32) == offsetof(mm_inflate_block, crc32) &&
+                offsetof(mmhost::InflateBlock, status) == offsetof(mm_inflate_block, status), "seq_parse.hpp restates mm_inflate_block");
+  return [ctx](const void* comp, size_t nComp, mmhost::InflateBlock* blocks, size_t n, void* dst, size_t nDst) {
+    const int rc = mm_inflate_blocks(ctx, comp, nComp, reinterpret_cast<mm_inflate_block*>(blocks), n, dst, nDst, nullptr);
+    if (rc != MM_OK) std::cerr << "[mashmap_hip] mm_inflate_blocks: " << mm_last_error(ctx) << std::endl;
+    return rc == MM_OK;
+  };
+}
 
 // The device path holds sequence positions as int32 in both builds: a reference or query record longer than this is refused with a
 // message, not truncated (the LARGE_CONTIG build has 64-bit offset_t on the host, and only there)
@@ -367,6 +385,7 @@ class Sketch {
     for (const auto& fileName : param.refSequences) {
       mmhost::BatchReader rd({fileName}, (size_t)-1 >> 1, (unsigned)std::min(16, std::max(1, param.threads)), allowed, param.target_prefix,   // see skch_map.hpp: more workers than this get in each other's way
                              [](size_t n) { return (char*)mm_host_alloc(n); }, [](char* p) { mm_host_free(p); });
+      rd.setBlockInflater(deviceBlockInflater(ctx_));             // -r ref.fa.gz, bgzipped: the blocks go to the device under MASHMAP_HIP_DEVICE_INFLATE=1
       mmhost::ParsedBatch b;
       while (rd.next(b)) {
         for (size_t r = 0; r < b.size(); r++) {
