@@ -617,6 +617,50 @@ int mm_inflate_blocks(mm_ctx* ctx, const void* comp, size_t nComp, mm_inflate_bl
                       void* dst, size_t nDst, size_t* nBad);
 int mm_inflate_counts(const mm_ctx* ctx, uint64_t* calls, uint64_t* blocks, uint64_t* bytesOut);
 int mm_inflate_kernel_ms(const mm_ctx* ctx, double* ms);
+/*
+ * FASTA / FASTQ text parsed on the device into the packed read batch (mashmap_amd/csrc/mm_text.hip; the record rules are
+ * mashmap_amd/csrc/mm_text_core.h, which tests/hostlogic/text_check.cpp runs against the host reader's serial functions).  A context owns
+ * one TEXT BUFFER on the device (at most 2^32 - 1 bytes; it counts in mm_device_bytes and goes with mm_destroy):
+ *   mm_text_reset            empties it (a new file).
+ *   mm_text_append           copies n bytes (a host pointer, or a device pointer with onDevice != 0) behind what it holds.
+ *   mm_text_append_inflated  is mm_inflate_blocks whose payloads stay on the device: the same checks of the descriptors, the same kernel,
+ *                            the same statuses.  uOff only orders the payloads: they are laid end to end, in ascending uOff, behind what
+ *                            the buffer holds.  If a block is refused nothing is appended; *nBad says how many were.
+ *   mm_text_scan             finds the records of the buffer.  final == 0: FASTA -- every record but the last header line's is complete and
+ *                            *consumed is that line's offset (one header line: 0 records, 0 bytes); FASTQ -- newlines / 4 records, and
+ *                            *consumed lies behind the last of their newlines.  final != 0: everything to the end belongs to records (a last
+ *                            FASTQ group of fewer than four lines is one) and *consumed is the buffer's length.  *nNameBytes: the names' total.
+ *   mm_text_records          the last scan's table: one mm_text_record per record (hdrOff: offset of its header line in the buffer; seqLen:
+ *                            its bases; hasN: one of them is not A C G T a c g t), and the names end to end, nameLen bytes each (the header
+ *                            line without its first byte, cut at the first ' ' only).  Either pointer may be NULL.
+ *   mm_text_pack             packs the bases of the records with keep[r] != 0 (keep == NULL: all) the way mm_reads_upload_packed lays a
+ *                            batch out -- record after record, each on a 32-base boundary, no gaps; a record that is not kept is a read of
+ *                            length 0 -- and hands the piece over as mm_reads_prefetch_packed_append would: if it fits the staging area (the
+ *                            same growth rule, the same reservePackedBases) the words are written THERE, as a staged piece with the key
+ *                            (bases2, nmask, *nPackedBases), the two host buffers are never touched and *staged = 1; otherwise they are
+ *                            copied to the two host buffers, which hold capPackedBases, and *staged = 0.  Either way the caller's
+ *                            mm_reads_upload_packed[_parts] with that key and the kept lengths carries the piece.  Then the consumed bytes
+ *                            leave the buffer and its tail becomes its front.  MM_ERR_ARG, with the buffer as it was: a kept record of 2^31
+ *                            bases or more, a total above capPackedBases.
+ *   mm_text_counts           scans that returned MM_OK, the records they found and the bytes they consumed, so far.
+ *   mm_text_kernel_ms        device time of the last scan's kernels and of the last pack's (hipEvents), 0 before the first.
+ * mm_text_records and mm_text_pack answer MM_ERR_STATE without a scan since the buffer last changed.  All of these join the thread exception
+ * of mm_reads_prefetch / mm_inflate_blocks: a reader thread may make them while the context's own thread is inside another call; they run
+ * on the inflate stream and are serialised among themselves and against mm_inflate_blocks inside the library; the text of a failed call
+ * is kept per calling thread like mm_inflate_blocks's.  Purely additive: MM_ABI_VERSION stays 2.
+ */
+#define MM_TEXT_TILE 4096                    /* bytes a wave summarises and resolves */
+enum { MM_TEXT_FASTA = 0, MM_TEXT_FASTQ = 1 };
+typedef struct { uint64_t hdrOff; int64_t seqLen; uint32_t nameLen, hasN; } mm_text_record;   /* 24 bytes */
+int mm_text_reset(mm_ctx* ctx);
+int mm_text_append(mm_ctx* ctx, const void* bytes, size_t n, int onDevice);
+int mm_text_append_inflated(mm_ctx* ctx, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks, size_t* nBad);
+int mm_text_scan(mm_ctx* ctx, int format, int final, size_t* nRecords, size_t* nNameBytes, size_t* consumed);
+int mm_text_records(mm_ctx* ctx, mm_text_record* recs, char* names);
+int mm_text_pack(mm_ctx* ctx, const uint8_t* keep, uint32_t* bases2, uint32_t* nmask, size_t capPackedBases,
+                 size_t reservePackedBases, size_t* nPackedBases, int* staged);
+int mm_text_counts(const mm_ctx* ctx, uint64_t* scans, uint64_t* records, uint64_t* bytes);
+int mm_text_kernel_ms(const mm_ctx* ctx, double* scanMs, double* packMs);
 /* diagnostic: bytes of device memory the library holds at this moment, over every context of the process (their indexes, batches of
  * reads -- the parked ones included --, staging buffers) and the scratch of a call in progress.  Counted where the library allocates and
  * frees, not asked of the device: memory other libraries or processes hold is not in it.  After the last mm_destroy it is 0.  May be

@@ -70,6 +70,10 @@ INFLATE_BLOCK_DT = np.dtype([("cOff", "<u8"), ("cLen", "<u4"), ("uLen", "<u4"), 
 MM_INFLATE_MAX_BLOCK = 65536
 MM_INFLATE_OK, MM_INFLATE_BAD_STREAM, MM_INFLATE_TRUNCATED, MM_INFLATE_OVERRUN, MM_INFLATE_SHORT, MM_INFLATE_BAD_DISTANCE, MM_INFLATE_BAD_CRC = range(7)
 INFLATE_STATUS = ["OK", "BAD_STREAM", "TRUNCATED", "OVERRUN", "SHORT", "BAD_DISTANCE", "BAD_CRC"]
+# mm_text_record (24 bytes), the MM_TEXT_* formats and the tile of the text kernels
+TEXT_RECORD_DT = np.dtype([("hdrOff", "<u8"), ("seqLen", "<i8"), ("nameLen", "<u4"), ("hasN", "<u4")])
+MM_TEXT_FASTA, MM_TEXT_FASTQ = 0, 1
+MM_TEXT_TILE = 4096
 L2_DT = np.dtype([("frag", "<i4"), ("cand", "<i4"), ("seqId", "<i4"), ("meanOptimalPos", "<i4"),
                   ("optimalStart", "<i4"), ("optimalEnd", "<i4"), ("sharedSketchSize", "<i4"), ("strand", "<i4")])
 assert MAPPING_DT.itemsize == 48 and MINMER_DT.itemsize == 24 and POINT_DT.itemsize == 24 and STATS_DT.itemsize == 24 and L2_DT.itemsize == 32
@@ -181,6 +185,14 @@ def load():
         "mm_inflate_blocks": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, C.POINTER(sz)]),
         "mm_inflate_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_inflate_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "mm_text_reset": (C.c_int, [vp]),
+        "mm_text_append": (C.c_int, [vp, vp, sz, C.c_int]),
+        "mm_text_append_inflated": (C.c_int, [vp, vp, sz, vp, sz, C.POINTER(sz)]),
+        "mm_text_scan": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+        "mm_text_records": (C.c_int, [vp, vp, vp]),
+        "mm_text_pack": (C.c_int, [vp, vp, vp, vp, sz, sz, C.POINTER(sz), C.POINTER(C.c_int)]),
+        "mm_text_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_text_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "mm_synchronize": (C.c_int, [vp]),
         "mm_stream": (vp, [vp]),
     }
@@ -210,7 +222,9 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
            "mm_stat_identity_table", "mm_set_chain_tables", "mm_chain_reads", "mm_chain_counts", "mm_chain_download",
            "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts", "mm_device_bytes",
-           "mm_sketch_large_counts", "mm_chain_group_counts", "mm_inflate_blocks", "mm_inflate_counts", "mm_inflate_kernel_ms"]
+           "mm_sketch_large_counts", "mm_chain_group_counts", "mm_inflate_blocks", "mm_inflate_counts", "mm_inflate_kernel_ms",
+           "mm_text_reset", "mm_text_append", "mm_text_append_inflated", "mm_text_scan", "mm_text_records", "mm_text_pack", "mm_text_counts",
+           "mm_text_kernel_ms"]
 
 
 def device_bytes():
@@ -760,6 +774,63 @@ class Context:
         v = C.c_double(0)
         self._ck(self.lib.mm_inflate_kernel_ms(self.h, C.byref(v)), "mm_inflate_kernel_ms")
         return float(v.value)
+
+    # ---- FASTA / FASTQ text parsed on the device (mm_text_*)
+    def text_reset(self):
+        self._ck(self.lib.mm_text_reset(self.h), "mm_text_reset")
+
+    def text_append(self, data, device_ptr=None):
+        """bytes (or a uint8 array) behind what the text buffer holds; device_ptr: `data` is a byte count and the bytes lie on the device"""
+        if device_ptr is not None:
+            self._ck(self.lib.mm_text_append(self.h, C.c_void_p(device_ptr), int(data), 1), "mm_text_append")
+            return
+        a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        self._ck(self.lib.mm_text_append(self.h, _ptr(a) if len(a) else None, len(a), 0), "mm_text_append")
+
+    def text_append_inflated(self, comp, blocks):
+        """mm_text_append_inflated: blocks are INFLATE_BLOCK_DT records whose status fields are written; returns (statuses, nBad)"""
+        comp = np.frombuffer(comp, dtype=np.uint8) if not isinstance(comp, np.ndarray) else np.ascontiguousarray(comp, dtype=np.uint8)
+        blocks = np.ascontiguousarray(blocks, dtype=INFLATE_BLOCK_DT)
+        bad = C.c_size_t(0)
+        self._ck(self.lib.mm_text_append_inflated(self.h, _ptr(comp) if len(comp) else None, len(comp), _ptr(blocks) if len(blocks) else None, len(blocks),
+                                                  C.byref(bad)), "mm_text_append_inflated")
+        return blocks["status"].copy(), int(bad.value)
+
+    def text_scan(self, fmt, final):
+        """(nRecords, nNameBytes, consumed)"""
+        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.lib.mm_text_scan(self.h, int(fmt), 1 if final else 0, C.byref(a), C.byref(b), C.byref(c)), "mm_text_scan")
+        self._text_scanned = (int(a.value), int(b.value))
+        return int(a.value), int(b.value), int(c.value)
+
+    def text_records(self):
+        """the last scan's table (TEXT_RECORD_DT) and the list of names (bytes)"""
+        n, nb = getattr(self, "_text_scanned", (0, 0))
+        recs = np.zeros(n, dtype=TEXT_RECORD_DT); names = np.zeros(max(1, nb), dtype=np.uint8)
+        self._ck(self.lib.mm_text_records(self.h, _ptr(recs) if n else None, _ptr(names)), "mm_text_records")
+        ends = np.cumsum(recs["nameLen"].astype(np.int64))
+        raw = names.tobytes()
+        return recs, [raw[int(e) - int(l):int(e)] for e, l in zip(ends, recs["nameLen"])]
+
+    def text_pack(self, b2, nm, keep=None, reserve=0):
+        """packs the last scan's records (keep: uint8 flags, None = all) into the staging area, keyed by the uint32 arrays b2 / nm, or
+        -- when it does not fit there -- into the arrays themselves; returns (nPackedBases, staged)"""
+        assert b2.dtype == np.uint32 and nm.dtype == np.uint32 and b2.flags.c_contiguous and nm.flags.c_contiguous
+        k = np.ascontiguousarray(keep, dtype=np.uint8) if keep is not None else None
+        n, st = C.c_size_t(0), C.c_int(0)
+        self._ck(self.lib.mm_text_pack(self.h, _ptr(k), _ptr(b2), _ptr(nm), min(b2.size * 16, nm.size * 32), int(reserve), C.byref(n), C.byref(st)), "mm_text_pack")
+        return int(n.value), int(st.value)
+
+    def text_counts(self):
+        """(scans, records, bytes consumed) of this context's mm_text_scan so far"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.mm_text_counts(self.h, C.byref(a), C.byref(b), C.byref(c)), "mm_text_counts")
+        return int(a.value), int(b.value), int(c.value)
+
+    def text_kernel_ms(self):
+        a, b = C.c_double(0), C.c_double(0)
+        self._ck(self.lib.mm_text_kernel_ms(self.h, C.byref(a), C.byref(b)), "mm_text_kernel_ms")
+        return float(a.value), float(b.value)
 
     def synchronize(self):
         self._ck(self.lib.mm_synchronize(self.h), "mm_synchronize")

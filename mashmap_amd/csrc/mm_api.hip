@@ -83,6 +83,9 @@ void mm_destroy(mm_ctx* c) {
   if (c->inflateStream) { (void)hipStreamSynchronize(c->inflateStream); (void)hipStreamDestroy(c->inflateStream); }
   if (c->infEvA) (void)hipEventDestroy(c->infEvA);
   if (c->infEvB) (void)hipEventDestroy(c->infEvB);
+  if (c->textEvA) (void)hipEventDestroy(c->textEvA);
+  if (c->textEvB) (void)hipEventDestroy(c->textEvB);
+  if (c->textDone) (void)hipEventDestroy(c->textDone);
   if (c->hPass) (void)hipHostFree(c->hPass);
   if (c->hSkLarge) (void)hipHostFree(c->hSkLarge);
   if (c->skLargeDone) (void)hipEventDestroy(c->skLargeDone);
@@ -426,9 +429,11 @@ int mm_reads_prefetch(mm_ctx* c, const char* bases, size_t nBytes) {
   return MM_OK;
 }
 
-// adds one packed piece to the staging area (prefetchMu held)
-static int stage_packed(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases, size_t reservePackedBases, int* stagedOut = nullptr) {
-  if (stagedOut) *stagedOut = 0;
+}  // extern "C"
+
+// where the next packed piece goes in the staging area (prefetchMu held): c->stagedBytes, if *fits
+int mm_stage_place(mm_ctx* c, size_t nPackedBases, size_t reservePackedBases, bool* fitsOut) {
+  *fitsOut = false;
   if (nPackedBases % 32) { c->err = "mm_reads_prefetch_packed: the packed length of a batch is a multiple of 32 bases"; return MM_ERR_ARG; }
   { const int rc = prefetch_streams(c); if (rc != MM_OK) return rc; }
   c->prefetchValid = false;                           // (packed pieces replace an ASCII batch sent ahead)
@@ -449,12 +454,26 @@ static int stage_packed(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask
     if (!fits(0)) return MM_OK;                       // no room under the pieces that are on their way: this one travels with its upload
     c->stagedBytes = 0;
   }
+  *fitsOut = true;
+  return MM_OK;
+}
+void mm_stage_commit(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases) {
+  c->staged.push_back(mm_ctx::StagedPart{bases2, nmask, nPackedBases, c->stagedBytes});
+  c->stagedBytes += nPackedBases / 4 + nPackedBases / 8;   // where the next piece goes
+}
+
+extern "C" {
+
+// adds one packed piece to the staging area (prefetchMu held)
+static int stage_packed(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases, size_t reservePackedBases, int* stagedOut = nullptr) {
+  if (stagedOut) *stagedOut = 0;
+  bool fits = false;
+  { const int rc = mm_stage_place(c, nPackedBases, reservePackedBases, &fits); if (rc != MM_OK || !fits) return rc; }
   char* dst = (char*)c->dAsciiNext.p + c->stagedBytes;
   MM_HIP(c, hipMemcpyAsync(dst, bases2, nPackedBases / 4, hipMemcpyHostToDevice, c->copyStream));
   MM_HIP(c, hipMemcpyAsync(dst + nPackedBases / 4, nmask, nPackedBases / 8, hipMemcpyHostToDevice, c->copyStream));
   MM_HIP(c, hipEventRecord(c->copyDone, c->copyStream));   // the event always marks the last piece: an upload that waits for it has them all
-  c->staged.push_back(mm_ctx::StagedPart{bases2, nmask, nPackedBases, c->stagedBytes});
-  c->stagedBytes += bytes;                            // where the next piece goes
+  mm_stage_commit(c, bases2, nmask, nPackedBases);
   if (stagedOut) *stagedOut = 1;
   return MM_OK;
 }

@@ -104,11 +104,14 @@ const char* mm_inflate_take_error(const mm_ctx* c) {
   t_inflateErrCtx = nullptr;
   return t_inflateErr.c_str();
 }
-struct InflateErr { std::string err; };           // what MM_HIP writes to on this path
+void mm_inflate_keep_error(const mm_ctx* c, InflateErr& e, int rc) {
+  if (rc != MM_OK) { t_inflateErr.swap(e.err); t_inflateErrCtx = c; } else if (t_inflateErrCtx == c) t_inflateErrCtx = nullptr;
+}
 
-static int inflate_blocks(mm_ctx* c, InflateErr* e, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks, void* dst, size_t nDst, size_t* nBad) {
-  std::lock_guard<std::mutex> lock(c->inflateMu);
-  if (nBlocks && (!blocks || !comp || (!dst && nDst))) { e->err = "mm_inflate_blocks: null argument"; return MM_ERR_ARG; }
+// mm_inflate_blocks (devOut == null: the payloads go to dInfOut and from there to dst) and mm_text_append_inflated (mm_text.hip: they are
+// laid end to end at devOut, which holds the sum of the uLen, and stay there; dst is null and nDst SIZE_MAX).  inflateMu is held.
+int mm_inflate_run(mm_ctx* c, InflateErr* e, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks, void* dst, size_t nDst, size_t* nBad, uint8_t* devOut) {
+  if (nBlocks && (!blocks || !comp || (!dst && nDst && !devOut))) { e->err = "mm_inflate_blocks: null argument"; return MM_ERR_ARG; }
   if (nBlocks > 0x7fffffffu) { e->err = "mm_inflate_blocks: too many blocks"; return MM_ERR_ARG; }
   // every range inside its buffer, no two output ranges overlapping; nothing is launched before this has passed
   uint64_t cLo = ~0ull, cHi = 0;
@@ -140,7 +143,7 @@ static int inflate_blocks(mm_ctx* c, InflateErr* e, const void* comp, size_t nCo
   for (uint32_t i : c->infOrder) { c->infDesc[i].uOff = at; at += blocks[i].uLen; }
   for (size_t i = 0; i < nBlocks; i++) { if (!blocks[i].uLen) c->infDesc[i].uOff = 0; c->infDesc[i].cOff = blocks[i].cLen ? blocks[i].cOff - cLo : 0; c->infDesc[i].status = 0; }
   MM_HIP(e, c->dInfComp.ensure((size_t)(cHi - cLo) + 64));
-  MM_HIP(e, c->dInfOut.ensure((size_t)at + 64));
+  if (!devOut) MM_HIP(e, c->dInfOut.ensure((size_t)at + 64));
   MM_HIP(e, c->dInfDesc.ensure(nBlocks * sizeof(mm_inflate_block)));
   MM_HIP(e, c->dInfStatus.ensure(nBlocks * sizeof(uint32_t)));
   if (!c->dInfStats.p) { MM_HIP(e, c->dInfStats.ensure(64)); MM_HIP(e, hipMemsetAsync(c->dInfStats.p, 0, 64, st)); }
@@ -157,11 +160,11 @@ static int inflate_blocks(mm_ctx* c, InflateErr* e, const void* comp, size_t nCo
   const unsigned grid = (unsigned)std::min<size_t>((size_t)c->infGrid, (nBlocks + MM_INF_WAVES - 1) / MM_INF_WAVES);
   MM_HIP(e, hipEventRecord(c->infEvA, st));
   hipLaunchKernelGGL(k_inflate_blocks, dim3(grid), dim3(64 * MM_INF_WAVES), 0, st, c->dInfComp.as<uint8_t>(), c->dInfDesc.as<mm_inflate_block>(), (uint32_t)nBlocks,
-                     c->dInfOut.as<uint8_t>(), c->dInfStatus.as<uint32_t>(), (unsigned int*)stats, stats + 1);
+                     devOut ? devOut : c->dInfOut.as<uint8_t>(), c->dInfStatus.as<uint32_t>(), (unsigned int*)stats, stats + 1);
   MM_HIP(e, hipGetLastError());
   MM_HIP(e, hipEventRecord(c->infEvB, st));
   // the payloads back, one copy per run of adjacent output ranges
-  for (size_t k = 0; k < c->infOrder.size();) {
+  for (size_t k = 0; !devOut && k < c->infOrder.size();) {
     size_t j = k + 1;
     while (j < c->infOrder.size() && blocks[c->infOrder[j - 1]].uOff + blocks[c->infOrder[j - 1]].uLen == blocks[c->infOrder[j]].uOff) j++;
     const mm_inflate_block& first = blocks[c->infOrder[k]]; const mm_inflate_block& last = blocks[c->infOrder[j - 1]];
@@ -189,8 +192,9 @@ int mm_inflate_blocks(mm_ctx* c, const void* comp, size_t nComp, mm_inflate_bloc
   if (nBad) *nBad = 0;
   if (!c) return MM_ERR_ARG;
   InflateErr e;
-  const int rc = inflate_blocks(c, &e, comp, nComp, blocks, nBlocks, dst, nDst, nBad);
-  if (rc != MM_OK) { t_inflateErr.swap(e.err); t_inflateErrCtx = c; } else if (t_inflateErrCtx == c) t_inflateErrCtx = nullptr;
+  std::lock_guard<std::mutex> lock(c->inflateMu);
+  const int rc = mm_inflate_run(c, &e, comp, nComp, blocks, nBlocks, dst, nDst, nBad, nullptr);
+  mm_inflate_keep_error(c, e, rc);
   return rc;
 }
 

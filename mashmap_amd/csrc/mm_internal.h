@@ -249,6 +249,14 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   mutable std::mutex inflateMu;
   std::vector<mm_inflate_block> infDesc; std::vector<uint32_t> infOrder, infStatus;
   uint64_t infCalls = 0, infBlocks = 0, infBytes = 0, infBad = 0; double infKernelMs = 0; int infGrid = 0;
+  // mm_text_* (mm_text.hip), under inflateMu and on the inflate stream: the text buffer (dText, textLen bytes; dTextAlt takes the tail when
+  // the consumed bytes leave), per tile its summary and carry-in, the record table with the sequence-byte index at every record start,
+  // keep flags, packed start of every record, the totals block, scratch for a piece that is not staged
+  DevBuf dText, dTextAlt, dTextSum, dTextCarry, dTextRecs, dTextSeqStart, dTextKeep, dTextPackOff, dTextTotals, dTextNames, dTextWords;
+  size_t textLen = 0; bool textScanned = false; int textFormat = 0, textFinal = 0;
+  size_t textRecords = 0, textNameBytes = 0, textConsumed = 0;
+  hipEvent_t textEvA = nullptr, textEvB = nullptr, textDone = nullptr;
+  uint64_t textScans = 0, textRecordsTotal = 0, textBytesTotal = 0; double textScanMs = 0, textPackMs = 0;
   ReadBatch parked[MM_BATCH_SLOTS];                     // batches parked beside the resident one (mm_reads_exchange)
 
   // sketches: raw (a4) and after frequent-seed removal (a8)
@@ -307,7 +315,14 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   std::vector<std::pair<int, size_t>> evPending;                              // (kernel, pool index)
 };
 
-const char* mm_inflate_take_error(const mm_ctx* c);     // mm_inflate.hip: the text of this thread's failed mm_inflate_blocks on c, once; else null
+const char* mm_inflate_take_error(const mm_ctx* c);     // mm_inflate.hip: the text of this thread's failed mm_inflate_blocks / mm_text_* on c, once; else null
+struct InflateErr { std::string err; };                 // what MM_HIP writes to on the reader thread's paths (never mm_ctx::err)
+void mm_inflate_keep_error(const mm_ctx* c, InflateErr& e, int rc);   // rc != MM_OK: e's text becomes this thread's for c; MM_OK: forgets it
+int mm_inflate_run(mm_ctx* c, InflateErr* e, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks, void* dst, size_t nDst, size_t* nBad, uint8_t* devOut);
+// the staging area of packed pieces (mm_api.hip; prefetchMu held): where a piece of nPackedBases goes -- *fits = false: no room under the
+// pieces on their way -- and its entry once its words are on their way there (copyDone recorded behind them)
+int mm_stage_place(mm_ctx* c, size_t nPackedBases, size_t reservePackedBases, bool* fits);
+void mm_stage_commit(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases);
 // the resident batch changed (an upload, an exchange): nothing sketched, mapped or gathered belongs to it
 inline void mm_batch_changed(mm_ctx* c) { c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false; }
 

@@ -13,6 +13,8 @@
 // buffer (pinned host memory when the caller provides an allocator, so that the upload to the GPU is one DMA).  Plain files are
 // mmap'ed; BGZF files (bgzip: independent <= 64 KiB deflate blocks, htslib's format -- the reference's data directory ships .gzi
 // indexes of such files) are inflated block-parallel -- by zlib on the pool, or by a block inflater the caller sets (BatchReader::setBlockInflater) --; any other gzip stream is inflated by one thread ahead of the parsers.
+// A caller that can inflate, parse and pack elsewhere sets a window parser (BatchReader::setWindowParser): regular BGZF files then reach
+// it as windows of compressed blocks and it fills the batches; nothing of the above runs for such a file.
 #pragma once
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -88,6 +90,9 @@ struct ParsedBatch {
   int64_t packEnd(size_t r0, size_t r1) const { return r1 > r0 ? packOffs[r1 - 1] + ((int64_t)lens[r1 - 1] + 31) / 32 * 32 : packOffs[r0]; }
   uint32_t* bases2() const { return (uint32_t*)bases; }
   uint32_t* nmask() const { return (uint32_t*)(bases + maskBase / 4); }
+  // a window parser (below) has left the packed words in the first context's staging area already: the buffer was not written, its two
+  // pointers and packedBases are the key the upload finds the piece by
+  bool staged = false;
 };
 
 // One BGZF block for an optional block inflater: the compressed stream comp + cOff (cLen bytes), where its payload goes (dst + uOff,
@@ -96,6 +101,20 @@ struct ParsedBatch {
 struct InflateBlock { uint64_t cOff; uint32_t cLen, uLen; uint64_t uOff; uint32_t crc32, status; };
 // inflates and checks blocks[0 .. n), writing every status; false: the inflater itself failed (it has said why)
 typedef std::function<bool(const void* comp, size_t nComp, InflateBlock* blocks, size_t n, void* dst, size_t nDst)> BlockInflater;
+
+// One window of a BGZF file for an optional window parser: the compressed bytes and descriptors of blocks whose payloads -- behind the
+// payloads of the file's windows before -- are the text to parse (uOff orders them), whether the text is FASTA, whether this is the
+// file's first window and whether it is its last (final: everything to the end belongs to records; otherwise only complete records are
+// returned and the parser keeps the tail for the next window).  keep(name): the reader's name filters.  grow(batch, bytes): makes the
+// batch's buffer hold that many bytes, from the reader's allocator pair.
+struct TextWindow {
+  const void* comp; size_t nComp; InflateBlock* blocks; size_t nBlocks; bool fasta, first, final;
+  std::function<bool(const std::string&)> keep;
+  std::function<void(ParsedBatch&, size_t)> grow;
+};
+// fills the batch (names, offs, lens, hasN, packOffs, packed, staged) with the window's complete records -- none when a record is longer
+// than what has arrived.  Returns 0, 1 for a corrupt block, 2 when the parser itself failed (it has said why)
+typedef std::function<int(const TextWindow& w, ParsedBatch& out)> WindowParser;
 
 namespace detail {
 
@@ -271,6 +290,9 @@ class RawSource {
   virtual bool next(const char*& p, size_t& n, bool fasta, bool first) = 0;   // false: exhausted
   virtual char first_byte() = 0;
   virtual bool fileMapped() const { return false; }                           // windows point into a file mapping (pages may not be mapped yet)
+  // a source that hands its windows to a window parser as compressed blocks instead of bytes; false: exhausted
+  virtual bool handsBlocks() const { return false; }
+  virtual bool nextBlocks(TextWindow&) { return false; }
 };
 
 }  // namespace detail
@@ -379,6 +401,7 @@ class GzSource : public RawSource {
   BlockInflater inflater_;                        // set: BGZF blocks go to it (and the two buffers are the reader's page-locked memory) instead of zlib on the pool
   ByteBuf buf_; size_t carry_ = 0; bool eof_ = false;
   ByteBuf comp_;
+  bool blocksOnly_ = false, finalSent_ = false; std::vector<InflateBlock> winBlks_;   // handBlocks()
   const bool timing_ = getenv("MASHMAP_HIP_TIMING") != nullptr;
 
   bool fill_stream(size_t want) {
@@ -398,6 +421,21 @@ class GzSource : public RawSource {
     return !buf_.empty();
   }
   // BGZF (SAM spec 4.1): gzip member with extra subfield 'B','C' holding BSIZE = block size - 1; payload = raw deflate; trailer CRC32 + ISIZE
+  // the next block of the file: its compressed bytes behind comp_'s, its descriptor (payload at uTot) behind blks; false at the file's end
+  bool read_block(std::vector<InflateBlock>& blks, size_t& uTot) {
+    unsigned char h[18];
+    if (fread(h, 1, 18, raw_) != 18) { eof_ = true; return false; }
+    if (h[0] != 31 || h[1] != 139 || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') { std::cerr << "[mashmap_hip] malformed BGZF block in " << path_ << std::endl; exit(1); }
+    const size_t bsize = (size_t)h[16] + ((size_t)h[17] << 8) + 1;
+    const size_t at = comp_.size(); comp_.resize(at + bsize - 18);
+    if (fread(comp_.data() + at, 1, bsize - 18, raw_) != bsize - 18) { std::cerr << "[mashmap_hip] truncated BGZF file " << path_ << std::endl; exit(1); }
+    const unsigned char* t = (const unsigned char*)comp_.data() + at + bsize - 18 - 4;
+    const size_t isize = (size_t)t[0] | ((size_t)t[1] << 8) | ((size_t)t[2] << 16) | ((size_t)t[3] << 24);
+    const uint32_t crc = (uint32_t)t[-4] | ((uint32_t)t[-3] << 8) | ((uint32_t)t[-2] << 16) | ((uint32_t)t[-1] << 24);
+    blks.push_back(InflateBlock{at, (uint32_t)(bsize - 18 - 8), (uint32_t)isize, uTot, crc, 0});
+    uTot += isize;
+    return true;
+  }
   bool fill_bgzf(size_t want) {
     while (buf_.size() < want && !eof_) {
       const auto t0 = std::chrono::steady_clock::now();
@@ -405,19 +443,7 @@ class GzSource : public RawSource {
       size_t uTot = 0;
       // blocks per round: 64 MB for the pool's threads; a block inflater takes what the window still lacks in one call (1 GB at the most)
       const size_t round = inflater_ ? std::min<size_t>((size_t)1 << 30, std::max<size_t>(64u << 20, want - buf_.size())) : (64u << 20);
-      while (uTot < round) {
-        unsigned char h[18];
-        if (fread(h, 1, 18, raw_) != 18) { eof_ = true; break; }
-        if (h[0] != 31 || h[1] != 139 || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') { std::cerr << "[mashmap_hip] malformed BGZF block in " << path_ << std::endl; exit(1); }
-        const size_t bsize = (size_t)h[16] + ((size_t)h[17] << 8) + 1;
-        const size_t at = comp_.size(); comp_.resize(at + bsize - 18);
-        if (fread(comp_.data() + at, 1, bsize - 18, raw_) != bsize - 18) { std::cerr << "[mashmap_hip] truncated BGZF file " << path_ << std::endl; exit(1); }
-        const unsigned char* t = (const unsigned char*)comp_.data() + at + bsize - 18 - 4;
-        const size_t isize = (size_t)t[0] | ((size_t)t[1] << 8) | ((size_t)t[2] << 16) | ((size_t)t[3] << 24);
-        const uint32_t crc = (uint32_t)t[-4] | ((uint32_t)t[-3] << 8) | ((uint32_t)t[-2] << 16) | ((uint32_t)t[-1] << 24);
-        blks.push_back(InflateBlock{at, (uint32_t)(bsize - 18 - 8), (uint32_t)isize, uTot, crc, 0});
-        uTot += isize;
-      }
+      while (uTot < round && read_block(blks, uTot)) {}
       const size_t base = buf_.size(); buf_.resize(base + uTot);
       std::atomic<size_t> nextB(0); std::atomic<int> bad(0);
       if (inflater_) {
@@ -469,7 +495,39 @@ class GzSource : public RawSource {
   }
   ~GzSource() override { if (raw_) fclose(raw_); if (gz_) gzclose(gz_); }
   bool ok() const { return raw_ || gz_; }
-  char first_byte() override { if (buf_.empty()) { if (bgzf_) fill_bgzf(1); else fill_stream(1); } return buf_.empty() ? 0 : buf_.data()[0]; }
+  // A BGZF file whose windows go to a window parser: nothing is inflated here any more.  nextBlocks reads blocks until their ISIZEs -- the
+  // trailers give the payload sizes without inflating -- sum to the window; the window that meets the file's end is the final one.
+  bool bgzf() const { return bgzf_; }
+  void handBlocks(std::function<char*(size_t)> pinAlloc, std::function<void(char*)> pinFree) { blocksOnly_ = true; if (pinAlloc && pinFree) comp_.pin(pinAlloc, pinFree); }
+  bool handsBlocks() const override { return blocksOnly_; }
+  bool nextBlocks(TextWindow& w) override {
+    if (finalSent_) return false;
+    winBlks_.clear(); comp_.clear();
+    size_t uTot = 0;
+    while (uTot < window_ && read_block(winBlks_, uTot)) {}
+    finalSent_ = eof_;
+    w.comp = comp_.data(); w.nComp = comp_.size(); w.blocks = winBlks_.data(); w.nBlocks = winBlks_.size(); w.final = eof_;
+    return true;
+  }
+  char first_byte() override {
+    if (blocksOnly_) {                             // the format sniff: the first payload byte, by zlib; the file is read from its start again
+      std::vector<InflateBlock> b; size_t u = 0; char c = 0;
+      comp_.clear();
+      while (!u && read_block(b, u)) {}
+      if (u) {
+        std::vector<char> tmp(b.back().uLen);
+        z_stream zs; std::memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, -15) == Z_OK) {
+          zs.next_in = (Bytef*)comp_.data() + b.back().cOff; zs.avail_in = (uInt)b.back().cLen; zs.next_out = (Bytef*)tmp.data(); zs.avail_out = (uInt)tmp.size();
+          (void)inflate(&zs, Z_FINISH);
+          if (zs.total_out) c = tmp[0];
+          inflateEnd(&zs);
+        }
+      }
+      fseek(raw_, 0, SEEK_SET); eof_ = false; comp_.clear();
+      return c;
+    }
+    if (buf_.empty()) { if (bgzf_) fill_bgzf(1); else fill_stream(1); } return buf_.empty() ? 0 : buf_.data()[0]; }
   bool next(const char*& p, size_t& n, bool fasta, bool) override {
     if (carry_) { buf_.erase_front(carry_); carry_ = 0; }
     size_t want = window_;
@@ -515,14 +573,18 @@ class BatchReader {
   // optional: BGZF files opened from here on hand their blocks to `f` instead of inflating them with zlib on the reader's threads, and
   // keep their compressed and inflated bytes in memory from the reader's allocator pair (page-locked when the caller's is)
   void setBlockInflater(BlockInflater f) { inflater_ = std::move(f); }
+  // optional, with packOutput: regular BGZF files opened from here on hand their windows, still compressed, to `f`, which inflates, parses
+  // and packs them elsewhere (on a device) and fills the batch; every other input is read and parsed here as ever
+  void setWindowParser(WindowParser f) { windowParser_ = std::move(f); }
 
   bool next(ParsedBatch& out) {
-    out.names.clear(); out.offs.assign(1, 0);
+    out.names.clear(); out.offs.assign(1, 0); out.staged = false;
     while (true) {
       if (!src_) {
         if (nextFile_ >= files_.size()) return false;
         openFile(files_[nextFile_]); curFile_ = nextFile_++; firstWindow_ = true;
       }
+      if (src_->handsBlocks()) { if (nextFromParser(out)) return true; continue; }
       const char* p = nullptr; size_t n = 0;
       if (!src_->next(p, n, fasta_, firstWindow_)) { delete src_; src_ = nullptr; continue; }
       firstWindow_ = false;
@@ -539,6 +601,7 @@ class BatchReader {
   WorkerPool pool_;
   Alloc alloc_; Free free_;
   BlockInflater inflater_;
+  WindowParser windowParser_;
   size_t splitWindows_ = 0;
   bool packOutput_ = false;          // batches carry 2-bit codes + N mask (what mm_reads_upload_packed takes) instead of ASCII
   detail::RawSource* src_ = nullptr; size_t nextFile_ = 0, curFile_ = 0; bool fasta_ = true, firstWindow_ = true, fileDone_ = false;
@@ -551,7 +614,10 @@ class BatchReader {
     if (regular) { FILE* f = fopen(path.c_str(), "rb"); if (f) { unsigned char m[2] = {0, 0}; if (fread(m, 1, 2, f) == 2) gz = m[0] == 31 && m[1] == 139; fclose(f); } }
     bool ok = false;
     if (!regular) { auto* s = new detail::GzSource(path, window_, threads_, &pool_, true); ok = s->ok(); src_ = s; }
-    else if (gz) { auto* s = new detail::GzSource(path, window_, threads_, &pool_, false, inflater_, alloc_, free_); ok = s->ok(); src_ = s; }
+    else if (gz) {
+      auto* s = new detail::GzSource(path, window_, threads_, &pool_, false, inflater_, alloc_, free_); ok = s->ok(); src_ = s;
+      if (ok && windowParser_ && packOutput_ && s->bgzf()) s->handBlocks(alloc_, free_);
+    }
     else { auto* s = new detail::MmapSource(path, window_); ok = s->ok(); src_ = s; }
     const char c = ok ? src_->first_byte() : 0;
     if (!ok || (c != '>' && c != '@')) {
@@ -559,6 +625,28 @@ class BatchReader {
       exit(1);
     }
     fasta_ = c == '>';
+  }
+
+  // windows of the current file through the window parser until one yields records; false: the file is exhausted (src_ is gone)
+  bool nextFromParser(ParsedBatch& out) {
+    TextWindow w;
+    w.keep = [this](const std::string& name) { return (keepPrefix_.empty() || name.compare(0, keepPrefix_.size(), keepPrefix_) == 0) && (keepSeq_.empty() || keepSeq_.count(name)); };
+    w.grow = [this](ParsedBatch& b, size_t need) {
+      if (need <= b.cap) return;
+      if (b.bases) free_(b.bases);
+      b.bases = alloc_(need + (need >> 4) + 4096);
+      if (!b.bases) { std::cerr << "[mashmap_hip] out of host memory for a batch of " << need << " packed bytes" << std::endl; exit(1); }
+      b.cap = need + (need >> 4) + 4096;
+    };
+    while (src_->nextBlocks(w)) {
+      w.fasta = fasta_; w.first = firstWindow_; firstWindow_ = false;
+      const int rc = windowParser_(w, out);
+      if (rc == 1) { std::cerr << "[mashmap_hip] corrupt BGZF block in " << files_[curFile_] << std::endl; exit(1); }
+      if (rc) exit(1);
+      if (out.size()) { fileDone_ = false; return true; }             // (no record yet: one longer than the window -- the parser keeps what came)
+    }
+    delete src_; src_ = nullptr;
+    return false;
   }
 
   // the sequence bytes of the window's records as 2-bit codes + N mask: the workers normalise and pack while they drop the line breaks

@@ -166,6 +166,9 @@ class Map {
       uint64_t calls = 0, blocks = 0, bytes = 0;                 // reference and query readers together; all zero unless MASHMAP_HIP_DEVICE_INFLATE=1 met BGZF input
       if (mm_inflate_counts(ctxs[0], &calls, &blocks, &bytes) == MM_OK)
         LogLine() << "[mashmap_hip::timing] device inflater: " << calls << " calls, " << blocks << " blocks, " << bytes << " bytes";
+      uint64_t scans = 0, records = 0, textBytes = 0;            // all zero unless MASHMAP_HIP_DEVICE_PARSE=1 met a BGZF query file
+      if (mm_text_counts(ctxs[0], &scans, &records, &textBytes) == MM_OK)
+        LogLine() << "[mashmap_hip::timing] device parser: " << scans << " scans, " << records << " records, " << textBytes << " bytes";
     }
   }
 
@@ -229,6 +232,8 @@ class Map {
                                return p;
                              }, [](char* p) { mm_host_free(p); }, packedUpload);
       rd.setBlockInflater(deviceBlockInflater(ctxs[0]));          // MASHMAP_HIP_DEVICE_INFLATE=1: BGZF blocks of the query go to mm_inflate_blocks (its own stream: it runs beside the device stage)
+      // MASHMAP_HIP_DEVICE_PARSE=1, one context, packed uploads: windows of BGZF query files are inflated, parsed and packed on the device
+      if (ctxs.size() == 1 && packedUpload) rd.setWindowParser(deviceWindowParser(ctxs[0], stageReserveBases));
       while (true) {
         Batch batch;
         { auto b = HostBufferPool::instance().take(0); batch.in.bases = b.first; batch.in.cap = b.second; }
@@ -263,6 +268,9 @@ class Map {
           // while holding it would never be served.
           parsed.waitSpace();
           std::lock_guard<std::mutex> lk(pfMu);
+          if (batch.in.staged) {                              // the device parser has put the words into context 0's staging area: on its way already
+            batch.prefetched.assign(ctxs.size(), 0); batch.prefetched[0] = 1; stagedBases[0] += batch.bases();
+          }
           if (packedUpload) {
             const std::vector<size_t> cut = blocksOf(batch);
             for (size_t i = 0; i < ctxs.size(); i++) issuePrefetch(batch, i, cut);

@@ -49,6 +49,56 @@ inline mmhost::BlockInflater deviceBlockInflater(mm_ctx* ctx) {
   };
 }
 
+// MASHMAP_HIP_DEVICE_PARSE=1 (read once): the query reader hands the windows of regular BGZF files, still compressed, to `ctx`, which
+// inflates them into its text buffer, finds the records, and packs the kept ones into the staging area its uploads take their pieces
+// from: mm_text_append_inflated -> mm_text_scan -> mm_text_records -> mm_text_pack.  The host keeps the names and the record table only.
+// Unset, or any other value: no hook, and nothing of the readers changes.  reservePackedBases: the staging area's size (issuePrefetch's).
+inline mmhost::WindowParser deviceWindowParser(mm_ctx* ctx, size_t reservePackedBases) {
+  static const bool on = [] { const char* e = getenv("MASHMAP_HIP_DEVICE_PARSE"); return e && atoi(e) == 1; }();
+  if (!on || !ctx) return nullptr;
+  return [ctx, reservePackedBases](const mmhost::TextWindow& w, mmhost::ParsedBatch& out) -> int {
+    const auto t0 = std::chrono::steady_clock::now();
+    auto fail = [&](const char* what) { std::cerr << "[mashmap_hip] " << what << ": " << mm_last_error(ctx) << std::endl; return 2; };
+    if (w.first && mm_text_reset(ctx) != MM_OK) return fail("mm_text_reset");
+    size_t nBad = 0, nRec = 0, nNameBytes = 0, consumed = 0;
+    if (mm_text_append_inflated(ctx, w.comp, w.nComp, reinterpret_cast<mm_inflate_block*>(w.blocks), w.nBlocks, &nBad) != MM_OK) return fail("mm_text_append_inflated");
+    if (nBad) return 1;
+    if (mm_text_scan(ctx, w.fasta ? MM_TEXT_FASTA : MM_TEXT_FASTQ, w.final ? 1 : 0, &nRec, &nNameBytes, &consumed) != MM_OK) return fail("mm_text_scan");
+    if (!nRec && !w.final) return 0;                          // one record longer than what has arrived: the buffer keeps it
+    std::vector<mm_text_record> recs(nRec);
+    std::vector<char> names(nNameBytes + 1);
+    if (mm_text_records(ctx, recs.data(), names.data()) != MM_OK) return fail("mm_text_records");
+    out.names.resize(nRec); out.offs.assign(nRec + 1, 0); out.packOffs.assign(nRec + 1, 0); out.lens.assign(nRec, 0); out.hasN.assign(nRec, 0);
+    std::vector<uint8_t> keep(nRec);
+    const int64_t maxLen = std::numeric_limits<int32_t>::max();   // kDeviceMaxLen, below
+    size_t nameAt = 0; int64_t at = 0, pk = 0; bool tooLong = false;
+    for (size_t r = 0; r < nRec; r++) {
+      out.names[r].assign(names.data() + nameAt, recs[r].nameLen); nameAt += recs[r].nameLen;
+      keep[r] = w.keep(out.names[r]) ? 1 : 0;
+      const int64_t len = keep[r] ? recs[r].seqLen : 0;       // a record that is not kept is a read of length 0
+      tooLong |= len > maxLen;
+      out.offs[r] = at; at += len;
+      out.packOffs[r] = pk; pk += (len + 31) / 32 * 32;
+      out.lens[r] = (int32_t)std::min<int64_t>(len, maxLen); out.hasN[r] = len ? (uint8_t)(recs[r].hasN != 0) : 0;
+    }
+    out.offs[nRec] = at; out.packOffs[nRec] = pk;
+    if (tooLong) { out.packed = false; return 0; }             // the reader reports it from the 64-bit lengths in offs, before anything is packed
+    out.packedBases = pk; out.maskBase = pk; out.packed = true;
+    w.grow(out, (size_t)pk / 4 + (size_t)pk / 8 + 64);
+    size_t nPacked = 0; int staged = 0;
+    if (mm_text_pack(ctx, keep.data(), out.bases2(), out.nmask(), (size_t)pk, reservePackedBases, &nPacked, &staged) != MM_OK) return fail("mm_text_pack");
+    if ((int64_t)nPacked != pk) { std::cerr << "[mashmap_hip] mm_text_pack: " << nPacked << " packed bases, the table says " << pk << std::endl; return 2; }
+    out.staged = staged != 0;
+    if (getenv("MASHMAP_HIP_TIMING")) {
+      double scanMs = 0, packMs = 0;
+      (void)mm_text_kernel_ms(ctx, &scanMs, &packMs);
+      fprintf(stderr, "[mashmap_hip::timing] reader: device parser: %zu blocks, %zu records, %zu bytes consumed, scan %.3f ms, pack %.3f ms, %s, in %.4f s\n", w.nBlocks, nRec,
+              consumed, scanMs, packMs, staged ? "staged" : "not staged", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    }
+    return 0;
+  };
+}
+
 // The device path holds sequence positions as int32 in both builds: a reference or query record longer than this is refused with a
 // message, not truncated (the LARGE_CONTIG build has 64-bit offset_t on the host, and only there)
 constexpr int64_t kDeviceMaxLen = std::numeric_limits<int32_t>::max();
