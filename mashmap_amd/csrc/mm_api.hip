@@ -63,8 +63,7 @@ int mm_create(mm_ctx** out, int device, const mm_params* p) {
   }
   mm_ctx* c = new mm_ctx();
   c->device = device; c->P = *p; c->env = mm_read_env();
-  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipEventCreate(&c->evA)) != hipSuccess || (e = hipEventCreate(&c->evB)) != hipSuccess) {
+  if ((e = c->stream.ensure()) != hipSuccess || (e = c->evA.ensure()) != hipSuccess || (e = c->evB.ensure()) != hipSuccess) {
     g_createErr = hipGetErrorString(e); delete c; return MM_ERR_DEVICE;
   }
   *out = c;
@@ -77,27 +76,15 @@ void mm_destroy(mm_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   if (c->gatherThread.joinable()) c->gatherThread.join();
   mm_comm_release(c);
-  if (c->commStream) (void)hipStreamDestroy(c->commStream);
-  if (c->copyStream) { (void)hipStreamSynchronize(c->copyStream); (void)hipStreamDestroy(c->copyStream); }
-  if (c->copyDone) (void)hipEventDestroy(c->copyDone);
-  if (c->inflateStream) { (void)hipStreamSynchronize(c->inflateStream); (void)hipStreamDestroy(c->inflateStream); }
-  if (c->infEvA) (void)hipEventDestroy(c->infEvA);
-  if (c->infEvB) (void)hipEventDestroy(c->infEvB);
-  if (c->textEvA) (void)hipEventDestroy(c->textEvA);
-  if (c->textEvB) (void)hipEventDestroy(c->textEvB);
-  if (c->textDone) (void)hipEventDestroy(c->textDone);
-  if (c->hPass) (void)hipHostFree(c->hPass);
-  if (c->hSkLarge) (void)hipHostFree(c->hSkLarge);
-  if (c->skLargeDone) (void)hipEventDestroy(c->skLargeDone);
-  for (auto& pr : c->evPool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  if (c->evA) (void)hipEventDestroy(c->evA);
-  if (c->evB) (void)hipEventDestroy(c->evB);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;   // frees every DevBuf of the context, the parked batches' included -- behind the streams' destruction: each was synchronised above (commStream by the joined gather thread)
+  if (c->stage.copyStream) (void)hipStreamSynchronize(c->stage.copyStream);
+  if (c->input.inflateStream) (void)hipStreamSynchronize(c->input.inflateStream);
+  // every stream is idle (commStream was drained by the joined gather thread), so the order in which the members -- buffers, streams,
+  // events, page-locked blocks, the parked batches' included -- give back what they own carries no meaning
+  delete c;
 }
 
 int mm_synchronize(mm_ctx* c) { MM_HIP(c, hipStreamSynchronize(c->stream)); return MM_OK; }
-void* mm_stream(const mm_ctx* c) { return (void*)c->stream; }
+void* mm_stream(const mm_ctx* c) { return (void*)c->stream.h; }
 
 int mm_set_option(mm_ctx* c, int option, int value) {
   Options& o = c->opt;
@@ -260,7 +247,8 @@ static int upload_reads_ascii(mm_ctx* c, const void* ascii, bool onDevice, const
   if (!readOffsets) { c->err = "mm_reads_upload: null argument"; return MM_ERR_ARG; }
   // the prefetch state (staging buffer, its copy event, what it holds) is matched and consumed below, and the copies out of the staging
   // buffer have completed when this function returns: a mm_reads_prefetch* from another thread waits for that
-  std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);
+  Staging& S = c->stage;
+  std::lock_guard<std::mutex> prefetchLock(S.prefetchMu);
   MM_HIP(c, hipSetDevice(c->device));
   std::vector<int64_t> srcOff(nReads + 1), packOff(nReads + 1);
   std::vector<int32_t> rlen(nReads);
@@ -284,10 +272,10 @@ static int upload_reads_ascii(mm_ctx* c, const void* ascii, bool onDevice, const
   if (nSrc && !ascii) { c->err = "mm_reads_upload: null argument"; return MM_ERR_ARG; }
   for (size_t r = 0; r <= nReads; r++) srcOff[r] -= (int64_t)srcBase;
   // bytes mm_reads_prefetch has already sent (same host range): take that buffer and wait for its copy on the device
-  const bool prefetched = c->prefetchValid && !onDevice && nSrc && c->prefetchPtr == (const void*)((const char*)ascii + srcBase) && c->prefetchBytes == nSrc;
-  c->prefetchValid = false;
-  c->staged.clear(); c->stagedBytes = 0;             // an ASCII upload drops whatever packed pieces were sent ahead (header contract): nothing stale can match later
-  if (prefetched) { std::swap(c->dAscii, c->dAsciiNext); MM_HIP(c, hipStreamWaitEvent(c->stream, c->copyDone, 0)); }
+  const bool prefetched = S.prefetchValid && !onDevice && nSrc && S.prefetchPtr == (const void*)((const char*)ascii + srcBase) && S.prefetchBytes == nSrc;
+  S.prefetchValid = false;
+  S.ring.clear();                                     // an ASCII upload drops whatever packed pieces were sent ahead (header contract): nothing stale can match later
+  if (prefetched) { std::swap(c->dAscii, S.dAsciiNext); MM_HIP(c, hipStreamWaitEvent(c->stream, S.copyDone, 0)); }
   else MM_HIP(c, c->dAscii.ensure(nSrc + 64));
   { const int rc = ensure_read_buffers(c, nReads, pk, dfr.size()); if (rc != MM_OK) return rc; }
   if (nSrc && !prefetched) MM_HIP(c, hipMemcpyAsync(c->dAscii.p, (const char*)ascii + srcBase, nSrc, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
@@ -300,7 +288,8 @@ static int upload_reads_ascii(mm_ctx* c, const void* ascii, bool onDevice, const
 // Packed pieces laid end to end: part p owns the packed bases [base_p, base_p + P_p) of the resident batch
 static int upload_packed_parts(mm_ctx* c, const mm_packed_part* parts, size_t nParts, int32_t seqCounterBase) {
   if (nParts && !parts) { c->err = "mm_reads_upload_packed: null argument"; return MM_ERR_ARG; }
-  std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);
+  Staging& S = c->stage;
+  std::lock_guard<std::mutex> prefetchLock(S.prefetchMu);
   MM_HIP(c, hipSetDevice(c->device));
   size_t nReads = 0;
   for (size_t p = 0; p < nParts; p++) {
@@ -349,23 +338,21 @@ static int upload_packed_parts(mm_ctx* c, const mm_packed_part* parts, size_t nP
   c->nReads = nReads; c->nFrags = dfr.size(); c->nPackedBases = (size_t)pk; c->seqCounterBase = seqCounterBase; c->maxFragLen = maxLen;
   mm_batch_changed(c);
   c->windowed = anyLong;
-  c->prefetchValid = false;                           // (an ASCII prefetch, if any, is not for this upload)
+  S.prefetchValid = false;                            // (an ASCII prefetch, if any, is not for this upload)
   { const int rc = ensure_read_buffers(c, nReads, pk, dfr.size()); if (rc != MM_OK) return rc; }
   // the words are the device layout already: straight into dBases2 / dNmask at the part's base -- from the staging area where the piece
   // travelled ahead (mm_reads_prefetch_packed[_append]: same two pointers, same packed length), from the host otherwise
   bool waited = false;
-  std::vector<char> used(c->staged.size(), 0);
+  std::vector<char> used(S.ring.pieces.size(), 0);
   for (size_t p = 0; p < nParts; p++) {
     const int64_t n = partBase[p + 1] - partBase[p];
     if (!n) continue;
     char* dB = (char*)c->dBases2.p + partBase[p] / 4; char* dM = (char*)c->dNmask.p + partBase[p] / 8;
-    size_t hit = c->staged.size();
-    for (size_t q = 0; q < c->staged.size(); q++)
-      if (!used[q] && c->staged[q].b2 == (const void*)parts[p].bases2 && c->staged[q].nm == (const void*)parts[p].nmask && c->staged[q].nPacked == (size_t)n) { hit = q; break; }
-    if (hit < c->staged.size()) {
-      if (!waited) { MM_HIP(c, hipStreamWaitEvent(c->stream, c->copyDone, 0)); waited = true; }
+    const size_t hit = S.ring.match(parts[p].bases2, parts[p].nmask, (size_t)n, used);
+    if (hit != StageRing::npos) {
+      if (!waited) { MM_HIP(c, hipStreamWaitEvent(c->stream, S.copyDone, 0)); waited = true; }
       used[hit] = 1;
-      const char* src = (const char*)c->dAsciiNext.p + c->staged[hit].off;
+      const char* src = S.dAsciiNext.as<char>() + S.ring.pieces[hit].off;
       MM_HIP(c, hipMemcpyAsync(dB, src, (size_t)n / 4, hipMemcpyDeviceToDevice, c->stream));
       MM_HIP(c, hipMemcpyAsync(dM, src + (size_t)n / 4, (size_t)n / 8, hipMemcpyDeviceToDevice, c->stream));
     } else {
@@ -374,10 +361,7 @@ static int upload_packed_parts(mm_ctx* c, const mm_packed_part* parts, size_t nP
     }
   }
   const int rc = finish_upload(c, nReads, pk, srcOff, packOff, rlen, grp, self, &hasN32, dfr, false);   // synchronises: the copies out of the staging area are done
-  // pieces this upload did not name stay staged; the area starts over once it is empty
-  std::vector<mm_ctx::StagedPart> left;
-  for (size_t q = 0; q < c->staged.size(); q++) if (!used[q]) left.push_back(c->staged[q]);
-  c->staged.swap(left);
+  S.ring.retire(used);                                // pieces this upload did not name stay staged; the area starts over once it is empty
   return rc;
 }
 
@@ -411,56 +395,39 @@ int mm_reads_packed_download(mm_ctx* c, uint32_t* bases2, uint32_t* nmask, uint3
 
 static int prefetch_streams(mm_ctx* c) {
   MM_HIP(c, hipSetDevice(c->device));
-  if (!c->copyStream) MM_HIP(c, hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
-  if (!c->copyDone) MM_HIP(c, hipEventCreateWithFlags(&c->copyDone, hipEventDisableTiming));
+  MM_HIP(c, c->stage.copyStream.ensure());
+  MM_HIP(c, c->stage.copyDone.ensure(hipEventDisableTiming));
   return MM_OK;
 }
 
 int mm_reads_prefetch(mm_ctx* c, const char* bases, size_t nBytes) {
-  std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);
-  c->prefetchValid = false;
+  Staging& S = c->stage;
+  std::lock_guard<std::mutex> prefetchLock(S.prefetchMu);
+  S.prefetchValid = false;
   if (!bases || !nBytes) return MM_OK;
   { const int rc = prefetch_streams(c); if (rc != MM_OK) return rc; }
-  c->staged.clear(); c->stagedBytes = 0;              // the staging area is one buffer: ASCII ahead replaces packed pieces ahead
-  MM_HIP(c, c->dAsciiNext.ensure(nBytes + 64));
-  MM_HIP(c, hipMemcpyAsync(c->dAsciiNext.p, bases, nBytes, hipMemcpyHostToDevice, c->copyStream));
-  MM_HIP(c, hipEventRecord(c->copyDone, c->copyStream));
-  c->prefetchPtr = bases; c->prefetchPtr2 = nullptr; c->prefetchBytes = nBytes; c->prefetchPacked = false; c->prefetchValid = true;
+  S.ring.clear();                                     // the staging area is one buffer: ASCII ahead replaces packed pieces ahead
+  MM_HIP(c, S.dAsciiNext.ensure(nBytes + 64));
+  MM_HIP(c, hipMemcpyAsync(S.dAsciiNext.p, bases, nBytes, hipMemcpyHostToDevice, S.copyStream));
+  MM_HIP(c, hipEventRecord(S.copyDone, S.copyStream));
+  S.prefetchPtr = bases; S.prefetchBytes = nBytes; S.prefetchValid = true;
   return MM_OK;
 }
 
 }  // extern "C"
 
-// where the next packed piece goes in the staging area (prefetchMu held): c->stagedBytes, if *fits
+// where the next packed piece goes in the staging area (prefetchMu held): stage.ring.next, if *fits
 int mm_stage_place(mm_ctx* c, size_t nPackedBases, size_t reservePackedBases, bool* fitsOut) {
+  Staging& S = c->stage;
   *fitsOut = false;
-  if (nPackedBases % 32) { c->err = "mm_reads_prefetch_packed: the packed length of a batch is a multiple of 32 bases"; return MM_ERR_ARG; }
+  if (const char* why = StageRing::refusal(nPackedBases)) { c->err = why; return MM_ERR_ARG; }
   { const int rc = prefetch_streams(c); if (rc != MM_OK) return rc; }
-  c->prefetchValid = false;                           // (packed pieces replace an ASCII batch sent ahead)
-  const size_t bytes = nPackedBases / 4 + nPackedBases / 8;
-  if (c->staged.empty()) {                            // nothing on its way: the area may grow, and starts over
-    const size_t want = std::max(bytes, reservePackedBases / 4 + reservePackedBases / 8) + 64;
-    MM_HIP(c, c->dAsciiNext.ensure(want));
-    c->stagedBytes = 0;
-  }
-  // the area is used as a ring: pieces leave in the order they came (an upload takes the pieces of the oldest batches), so the next
-  // piece goes behind the newest one, or to the front again once the oldest ones have left
-  auto fits = [&](size_t off) {
-    if (off + bytes + 64 > c->dAsciiNext.bytes) return false;
-    for (const auto& q : c->staged) { const size_t qb = q.nPacked / 4 + q.nPacked / 8; if (off < q.off + qb && q.off < off + bytes) return false; }
-    return true;
-  };
-  if (!fits(c->stagedBytes)) {
-    if (!fits(0)) return MM_OK;                       // no room under the pieces that are on their way: this one travels with its upload
-    c->stagedBytes = 0;
-  }
-  *fitsOut = true;
+  S.prefetchValid = false;                            // (packed pieces replace an ASCII batch sent ahead)
+  if (S.ring.empty()) MM_HIP(c, S.dAsciiNext.ensure(StageRing::want(nPackedBases, reservePackedBases)));   // nothing on its way: the area may grow
+  *fitsOut = S.ring.place(nPackedBases, S.dAsciiNext.bytes);   // false: this piece travels with its upload
   return MM_OK;
 }
-void mm_stage_commit(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases) {
-  c->staged.push_back(mm_ctx::StagedPart{bases2, nmask, nPackedBases, c->stagedBytes});
-  c->stagedBytes += nPackedBases / 4 + nPackedBases / 8;   // where the next piece goes
-}
+void mm_stage_commit(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases) { c->stage.ring.commit(bases2, nmask, nPackedBases); }
 
 extern "C" {
 
@@ -469,42 +436,43 @@ static int stage_packed(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask
   if (stagedOut) *stagedOut = 0;
   bool fits = false;
   { const int rc = mm_stage_place(c, nPackedBases, reservePackedBases, &fits); if (rc != MM_OK || !fits) return rc; }
-  char* dst = (char*)c->dAsciiNext.p + c->stagedBytes;
-  MM_HIP(c, hipMemcpyAsync(dst, bases2, nPackedBases / 4, hipMemcpyHostToDevice, c->copyStream));
-  MM_HIP(c, hipMemcpyAsync(dst + nPackedBases / 4, nmask, nPackedBases / 8, hipMemcpyHostToDevice, c->copyStream));
-  MM_HIP(c, hipEventRecord(c->copyDone, c->copyStream));   // the event always marks the last piece: an upload that waits for it has them all
+  Staging& S = c->stage;
+  char* dst = S.dAsciiNext.as<char>() + S.ring.next;
+  MM_HIP(c, hipMemcpyAsync(dst, bases2, nPackedBases / 4, hipMemcpyHostToDevice, S.copyStream));
+  MM_HIP(c, hipMemcpyAsync(dst + nPackedBases / 4, nmask, nPackedBases / 8, hipMemcpyHostToDevice, S.copyStream));
+  MM_HIP(c, hipEventRecord(S.copyDone, S.copyStream));   // the event always marks the last piece: an upload that waits for it has them all
   mm_stage_commit(c, bases2, nmask, nPackedBases);
   if (stagedOut) *stagedOut = 1;
   return MM_OK;
 }
 
 int mm_reads_prefetch_packed(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases) {
-  std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);
-  c->prefetchValid = false;
-  c->staged.clear(); c->stagedBytes = 0;
+  std::lock_guard<std::mutex> prefetchLock(c->stage.prefetchMu);
+  c->stage.prefetchValid = false;
+  c->stage.ring.clear();
   if (!bases2 || !nmask || !nPackedBases) return MM_OK;
   return stage_packed(c, bases2, nmask, nPackedBases, nPackedBases);
 }
 
 int mm_reads_prefetch_packed_append(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases, size_t reservePackedBases, int* staged) {
-  std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);
+  std::lock_guard<std::mutex> prefetchLock(c->stage.prefetchMu);
   if (staged) *staged = 0;
   if (!bases2 || !nmask || !nPackedBases) return MM_OK;
   return stage_packed(c, bases2, nmask, nPackedBases, reservePackedBases, staged);
 }
 
 int mm_reads_prefetch_reserve(mm_ctx* c, size_t reservePackedBases) {
-  std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);
-  if (!c->staged.empty() || c->prefetchValid) return MM_OK;
+  std::lock_guard<std::mutex> prefetchLock(c->stage.prefetchMu);
+  if (!c->stage.ring.empty() || c->stage.prefetchValid) return MM_OK;
   { const int rc = prefetch_streams(c); if (rc != MM_OK) return rc; }
-  MM_HIP(c, c->dAsciiNext.ensure(reservePackedBases / 4 + reservePackedBases / 8 + 64));
+  MM_HIP(c, c->stage.dAsciiNext.ensure(StageRing::want(0, reservePackedBases)));
   return MM_OK;
 }
 
 int mm_reads_prefetch_drop(mm_ctx* c) {
-  std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);
-  c->prefetchValid = false;
-  c->staged.clear(); c->stagedBytes = 0;
+  std::lock_guard<std::mutex> prefetchLock(c->stage.prefetchMu);
+  c->stage.prefetchValid = false;
+  c->stage.ring.clear();
   return MM_OK;
 }
 
@@ -517,7 +485,7 @@ void mm_host_free(void* p) { if (p) (void)hipHostFree(p); }
 
 int mm_reads_exchange(mm_ctx* c, int slot) {
   if (slot < 0 || slot >= MM_BATCH_SLOTS) { c->err = "mm_reads_exchange: slot out of range"; return MM_ERR_ARG; }
-  std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);   // an upload of the resident batch is not under way
+  std::lock_guard<std::mutex> prefetchLock(c->stage.prefetchMu);   // an upload of the resident batch is not under way
   MM_HIP(c, hipSetDevice(c->device));
   MM_HIP(c, hipStreamSynchronize(c->stream));                // nothing queued still reads the outgoing batch
   std::swap(static_cast<ReadBatch&>(*c), c->parked[slot]);

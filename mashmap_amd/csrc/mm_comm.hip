@@ -225,7 +225,7 @@ int mm_allgatherv_mappings_begin(mm_ctx* c) {
   Rccl* R = rccl_open(c->env, c->err);
   if (!R) return MM_ERR_DEVICE;
   MM_HIP(c, hipSetDevice(c->device));
-  if (!c->commStream) MM_HIP(c, hipStreamCreateWithFlags(&c->commStream, hipStreamNonBlocking));
+  MM_HIP(c, c->commStream.ensure());
   // snapshot: the next mm_map_fragments overwrites dMappings while the exchange is in flight
   const size_t n = c->rep.nMappings;
   MM_HIP(c, c->dGatherSrc.ensure(n * sizeof(mm_mapping) + 64));

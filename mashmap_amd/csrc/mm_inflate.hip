@@ -109,80 +109,80 @@ void mm_inflate_keep_error(const mm_ctx* c, InflateErr& e, int rc) {
 }
 
 // mm_inflate_blocks (devOut == null: the payloads go to dInfOut and from there to dst) and mm_text_append_inflated (mm_text.hip: they are
-// laid end to end at devOut, which holds the sum of the uLen, and stay there; dst is null and nDst SIZE_MAX).  inflateMu is held.
+// laid end to end at devOut, which holds the sum of the uLen, and stay there; dst is null and nDst SIZE_MAX).  DeviceInput::inflateMu is held.
 int mm_inflate_run(mm_ctx* c, InflateErr* e, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks, void* dst, size_t nDst, size_t* nBad, uint8_t* devOut) {
+  DeviceInput::Inflate& I = c->input.inf;
   if (nBlocks && (!blocks || !comp || (!dst && nDst && !devOut))) { e->err = "mm_inflate_blocks: null argument"; return MM_ERR_ARG; }
   if (nBlocks > 0x7fffffffu) { e->err = "mm_inflate_blocks: too many blocks"; return MM_ERR_ARG; }
   // every range inside its buffer, no two output ranges overlapping; nothing is launched before this has passed
   uint64_t cLo = ~0ull, cHi = 0;
-  c->infOrder.clear();
+  I.infOrder.clear();
   for (size_t i = 0; i < nBlocks; i++) {
     const mm_inflate_block& b = blocks[i];
     if (b.cLen > MM_INFLATE_MAX_BLOCK || b.uLen > MM_INFLATE_MAX_BLOCK) { e->err = "mm_inflate_blocks: a block above MM_INFLATE_MAX_BLOCK"; return MM_ERR_ARG; }
     if (b.cOff > nComp || nComp - b.cOff < b.cLen || b.uOff > nDst || nDst - b.uOff < b.uLen) { e->err = "mm_inflate_blocks: a descriptor's range leaves its buffer"; return MM_ERR_ARG; }
     if (b.cLen) { cLo = std::min<uint64_t>(cLo, b.cOff); cHi = std::max<uint64_t>(cHi, b.cOff + b.cLen); }
-    if (b.uLen) c->infOrder.push_back((uint32_t)i);
+    if (b.uLen) I.infOrder.push_back((uint32_t)i);
   }
-  std::sort(c->infOrder.begin(), c->infOrder.end(), [&](uint32_t a, uint32_t b) { return blocks[a].uOff < blocks[b].uOff; });
-  for (size_t k = 1; k < c->infOrder.size(); k++) {
-    const mm_inflate_block& p = blocks[c->infOrder[k - 1]];
-    if (p.uOff + p.uLen > blocks[c->infOrder[k]].uOff) { e->err = "mm_inflate_blocks: output ranges overlap"; return MM_ERR_ARG; }
+  std::sort(I.infOrder.begin(), I.infOrder.end(), [&](uint32_t a, uint32_t b) { return blocks[a].uOff < blocks[b].uOff; });
+  for (size_t k = 1; k < I.infOrder.size(); k++) {
+    const mm_inflate_block& p = blocks[I.infOrder[k - 1]];
+    if (p.uOff + p.uLen > blocks[I.infOrder[k]].uOff) { e->err = "mm_inflate_blocks: output ranges overlap"; return MM_ERR_ARG; }
   }
-  if (!nBlocks) { c->infCalls++; return MM_OK; }
+  if (!nBlocks) { I.infCalls++; return MM_OK; }
   if (cLo > cHi) cLo = cHi = 0;
 
-  MM_HIP(e, hipSetDevice(c->device));
-  if (!c->inflateStream) MM_HIP(e, hipStreamCreateWithFlags(&c->inflateStream, hipStreamNonBlocking));
-  if (!c->infEvA) MM_HIP(e, hipEventCreate(&c->infEvA));
-  if (!c->infEvB) MM_HIP(e, hipEventCreate(&c->infEvB));
-  hipStream_t st = c->inflateStream;
+  { const int rc = c->input.ready(c->device, e); if (rc != MM_OK) return rc; }
+  MM_HIP(e, I.infEvA.ensure());
+  MM_HIP(e, I.infEvB.ensure());
+  hipStream_t st = c->input.inflateStream;
   // device descriptors: cOff relative to the compressed span, payloads packed end to end in ascending uOff (what is adjacent in dst stays
   // adjacent on the device, so a run of adjacent ranges comes back as one copy)
-  c->infDesc.assign(blocks, blocks + nBlocks);
+  I.infDesc.assign(blocks, blocks + nBlocks);
   uint64_t at = 0;
-  for (uint32_t i : c->infOrder) { c->infDesc[i].uOff = at; at += blocks[i].uLen; }
-  for (size_t i = 0; i < nBlocks; i++) { if (!blocks[i].uLen) c->infDesc[i].uOff = 0; c->infDesc[i].cOff = blocks[i].cLen ? blocks[i].cOff - cLo : 0; c->infDesc[i].status = 0; }
-  MM_HIP(e, c->dInfComp.ensure((size_t)(cHi - cLo) + 64));
-  if (!devOut) MM_HIP(e, c->dInfOut.ensure((size_t)at + 64));
-  MM_HIP(e, c->dInfDesc.ensure(nBlocks * sizeof(mm_inflate_block)));
-  MM_HIP(e, c->dInfStatus.ensure(nBlocks * sizeof(uint32_t)));
-  if (!c->dInfStats.p) { MM_HIP(e, c->dInfStats.ensure(64)); MM_HIP(e, hipMemsetAsync(c->dInfStats.p, 0, 64, st)); }
-  if (!c->infGrid) {
+  for (uint32_t i : I.infOrder) { I.infDesc[i].uOff = at; at += blocks[i].uLen; }
+  for (size_t i = 0; i < nBlocks; i++) { if (!blocks[i].uLen) I.infDesc[i].uOff = 0; I.infDesc[i].cOff = blocks[i].cLen ? blocks[i].cOff - cLo : 0; I.infDesc[i].status = 0; }
+  MM_HIP(e, I.dInfComp.ensure((size_t)(cHi - cLo) + 64));
+  if (!devOut) MM_HIP(e, I.dInfOut.ensure((size_t)at + 64));
+  MM_HIP(e, I.dInfDesc.ensure(nBlocks * sizeof(mm_inflate_block)));
+  MM_HIP(e, I.dInfStatus.ensure(nBlocks * sizeof(uint32_t)));
+  if (!I.dInfStats.p) { MM_HIP(e, I.dInfStats.ensure(64)); MM_HIP(e, hipMemsetAsync(I.dInfStats.p, 0, 64, st)); }
+  if (!I.infGrid) {
     int cus = 0, perCu = 0;
     MM_HIP(e, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     MM_HIP(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_inflate_blocks, 64 * MM_INF_WAVES, 0));
-    c->infGrid = std::max(1, cus) * std::max(1, perCu);         // what the device holds at the kernel's residency
+    I.infGrid = std::max(1, cus) * std::max(1, perCu);         // what the device holds at the kernel's residency
   }
-  if (cHi > cLo) MM_HIP(e, hipMemcpyAsync(c->dInfComp.p, (const char*)comp + cLo, (size_t)(cHi - cLo), hipMemcpyHostToDevice, st));
-  MM_HIP(e, hipMemcpyAsync(c->dInfDesc.p, c->infDesc.data(), nBlocks * sizeof(mm_inflate_block), hipMemcpyHostToDevice, st));
-  MM_HIP(e, hipMemsetAsync(c->dInfStats.p, 0, 8, st));                       // the block counter starts over; the three counts behind it go on
-  unsigned long long* stats = c->dInfStats.as<unsigned long long>();
-  const unsigned grid = (unsigned)std::min<size_t>((size_t)c->infGrid, (nBlocks + MM_INF_WAVES - 1) / MM_INF_WAVES);
-  MM_HIP(e, hipEventRecord(c->infEvA, st));
-  hipLaunchKernelGGL(k_inflate_blocks, dim3(grid), dim3(64 * MM_INF_WAVES), 0, st, c->dInfComp.as<uint8_t>(), c->dInfDesc.as<mm_inflate_block>(), (uint32_t)nBlocks,
-                     devOut ? devOut : c->dInfOut.as<uint8_t>(), c->dInfStatus.as<uint32_t>(), (unsigned int*)stats, stats + 1);
+  if (cHi > cLo) MM_HIP(e, hipMemcpyAsync(I.dInfComp.p, (const char*)comp + cLo, (size_t)(cHi - cLo), hipMemcpyHostToDevice, st));
+  MM_HIP(e, hipMemcpyAsync(I.dInfDesc.p, I.infDesc.data(), nBlocks * sizeof(mm_inflate_block), hipMemcpyHostToDevice, st));
+  MM_HIP(e, hipMemsetAsync(I.dInfStats.p, 0, 8, st));                       // the block counter starts over; the three counts behind it go on
+  unsigned long long* stats = I.dInfStats.as<unsigned long long>();
+  const unsigned grid = (unsigned)std::min<size_t>((size_t)I.infGrid, (nBlocks + MM_INF_WAVES - 1) / MM_INF_WAVES);
+  MM_HIP(e, hipEventRecord(I.infEvA, st));
+  hipLaunchKernelGGL(k_inflate_blocks, dim3(grid), dim3(64 * MM_INF_WAVES), 0, st, I.dInfComp.as<uint8_t>(), I.dInfDesc.as<mm_inflate_block>(), (uint32_t)nBlocks,
+                     devOut ? devOut : I.dInfOut.as<uint8_t>(), I.dInfStatus.as<uint32_t>(), (unsigned int*)stats, stats + 1);
   MM_HIP(e, hipGetLastError());
-  MM_HIP(e, hipEventRecord(c->infEvB, st));
+  MM_HIP(e, hipEventRecord(I.infEvB, st));
   // the payloads back, one copy per run of adjacent output ranges
-  for (size_t k = 0; !devOut && k < c->infOrder.size();) {
+  for (size_t k = 0; !devOut && k < I.infOrder.size();) {
     size_t j = k + 1;
-    while (j < c->infOrder.size() && blocks[c->infOrder[j - 1]].uOff + blocks[c->infOrder[j - 1]].uLen == blocks[c->infOrder[j]].uOff) j++;
-    const mm_inflate_block& first = blocks[c->infOrder[k]]; const mm_inflate_block& last = blocks[c->infOrder[j - 1]];
-    MM_HIP(e, hipMemcpyAsync((char*)dst + first.uOff, c->dInfOut.as<char>() + c->infDesc[c->infOrder[k]].uOff, (size_t)(last.uOff + last.uLen - first.uOff), hipMemcpyDeviceToHost, st));
+    while (j < I.infOrder.size() && blocks[I.infOrder[j - 1]].uOff + blocks[I.infOrder[j - 1]].uLen == blocks[I.infOrder[j]].uOff) j++;
+    const mm_inflate_block& first = blocks[I.infOrder[k]]; const mm_inflate_block& last = blocks[I.infOrder[j - 1]];
+    MM_HIP(e, hipMemcpyAsync((char*)dst + first.uOff, I.dInfOut.as<char>() + I.infDesc[I.infOrder[k]].uOff, (size_t)(last.uOff + last.uLen - first.uOff), hipMemcpyDeviceToHost, st));
     k = j;
   }
-  c->infStatus.resize(nBlocks);
+  I.infStatus.resize(nBlocks);
   uint64_t hStats[4] = {0, 0, 0, 0};
-  MM_HIP(e, hipMemcpyAsync(c->infStatus.data(), c->dInfStatus.p, nBlocks * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  MM_HIP(e, hipMemcpyAsync(hStats, c->dInfStats.p, sizeof hStats, hipMemcpyDeviceToHost, st));
+  MM_HIP(e, hipMemcpyAsync(I.infStatus.data(), I.dInfStatus.p, nBlocks * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  MM_HIP(e, hipMemcpyAsync(hStats, I.dInfStats.p, sizeof hStats, hipMemcpyDeviceToHost, st));
   MM_HIP(e, hipStreamSynchronize(st));
-  c->infCalls++;                                                  // a call that ran: counted behind its one wait
+  I.infCalls++;                                                  // a call that ran: counted behind its one wait
   size_t bad = 0;
-  for (size_t i = 0; i < nBlocks; i++) { blocks[i].status = c->infStatus[i]; bad += c->infStatus[i] != MM_INFLATE_OK; }
+  for (size_t i = 0; i < nBlocks; i++) { blocks[i].status = I.infStatus[i]; bad += I.infStatus[i] != MM_INFLATE_OK; }
   if (nBad) *nBad = bad;
-  c->infBlocks = hStats[1]; c->infBytes = hStats[2]; c->infBad = hStats[3];
+  I.infBlocks = hStats[1]; I.infBytes = hStats[2]; I.infBad = hStats[3];
   float ms = 0;
-  if (hipEventElapsedTime(&ms, c->infEvA, c->infEvB) == hipSuccess) c->infKernelMs = ms; else (void)hipGetLastError();
+  if (hipEventElapsedTime(&ms, I.infEvA, I.infEvB) == hipSuccess) I.infKernelMs = ms; else (void)hipGetLastError();
   return MM_OK;
 }
 
@@ -190,27 +190,22 @@ extern "C" {
 
 int mm_inflate_blocks(mm_ctx* c, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks, void* dst, size_t nDst, size_t* nBad) {
   if (nBad) *nBad = 0;
-  if (!c) return MM_ERR_ARG;
-  InflateErr e;
-  std::lock_guard<std::mutex> lock(c->inflateMu);
-  const int rc = mm_inflate_run(c, &e, comp, nComp, blocks, nBlocks, dst, nDst, nBad, nullptr);
-  mm_inflate_keep_error(c, e, rc);
-  return rc;
+  return mm_input_call(c, [&](InflateErr* e) { return mm_inflate_run(c, e, comp, nComp, blocks, nBlocks, dst, nDst, nBad, nullptr); });
 }
 
 int mm_inflate_counts(const mm_ctx* c, uint64_t* calls, uint64_t* blocks, uint64_t* bytesOut) {
   if (!c) return MM_ERR_ARG;
-  std::lock_guard<std::mutex> lock(c->inflateMu);
-  if (calls) *calls = c->infCalls;
-  if (blocks) *blocks = c->infBlocks;
-  if (bytesOut) *bytesOut = c->infBytes;
+  std::lock_guard<std::mutex> lock(c->input.inflateMu);
+  if (calls) *calls = c->input.inf.infCalls;
+  if (blocks) *blocks = c->input.inf.infBlocks;
+  if (bytesOut) *bytesOut = c->input.inf.infBytes;
   return MM_OK;
 }
 
 int mm_inflate_kernel_ms(const mm_ctx* c, double* ms) {
   if (!c || !ms) return MM_ERR_ARG;
-  std::lock_guard<std::mutex> lock(c->inflateMu);
-  *ms = c->infKernelMs;
+  std::lock_guard<std::mutex> lock(c->input.inflateMu);
+  *ms = c->input.inf.infKernelMs;
   return MM_OK;
 }
 

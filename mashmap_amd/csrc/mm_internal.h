@@ -12,6 +12,7 @@
 #include "../../include/mashmap_hip.h"
 #include "mm_devbuf.h"
 #include "mm_pass_state.h"
+#include "mm_stage_plan.h"
 
 #define MM_WAVE 64
 
@@ -25,7 +26,7 @@
 // ---------------------------------------------------------------------------------------------
 // host-side helpers
 // ---------------------------------------------------------------------------------------------
-// (DevBuf, the owner of every device allocation: mm_devbuf.h)
+// (DevBuf, DevStream, DevEvent, PinnedBuf -- the owners of every device allocation, stream, event and page-locked block: mm_devbuf.h)
 
 // fragment descriptor on the device
 struct DFrag {
@@ -213,9 +214,50 @@ struct ReadBatch {
   std::vector<mm_fragment> hFrags;
 };
 
+// A reader thread, the context's own thread and the gather thread all touch mm_ctx.  Two locks guard what they share, and each sits in a
+// member of mm_ctx beside exactly the fields it guards: Staging::prefetchMu and DeviceInput::inflateMu.  Where both are taken, inflateMu
+// is taken first (mm_text_pack).  Everything else in mm_ctx belongs to the context's own thread, which lends the exchange's fields to the
+// gather thread from mm_allgatherv_mappings_begin until it joins it.
+//
+// What travels ahead of an upload, on a stream of its own while the current batch is mapped (mm_reads_prefetch*): the next batch's ASCII
+// bytes, or packed pieces in a ring (mm_stage_plan.h) -- one area, dAsciiNext, holds either.  copyDone always marks the last copy into it.
+// mm_reads_prefetch* and mm_text_pack may come from another thread than the uploads, which match and consume this state.
+struct Staging {
+  std::mutex prefetchMu;
+  DevBuf dAsciiNext; DevStream copyStream; DevEvent copyDone;
+  const void* prefetchPtr = nullptr; size_t prefetchBytes = 0; bool prefetchValid = false;   // the ASCII bytes sent ahead: their host range
+  StageRing ring;                                       // the packed pieces sent ahead: [codes | mask] at dAsciiNext + off
+};
+
+struct InflateErr { std::string err; };                 // what MM_HIP writes to on the reader thread's paths (never mm_ctx::err)
+
+// mm_inflate_blocks (mm_inflate.hip) and mm_text_* (mm_text.hip): a stream, a lock and buffers of their own -- a reader thread calls them
+// beside the context's own thread
+struct DeviceInput {
+  mutable std::mutex inflateMu;
+  DevStream inflateStream;
+  struct Inflate {
+    DevBuf dInfComp, dInfOut, dInfDesc, dInfStatus, dInfStats;   // compressed span, payloads packed end to end, descriptors, one status word per block, [next block | blocks, bytes out, bad blocks]
+    DevEvent infEvA, infEvB;
+    std::vector<mm_inflate_block> infDesc; std::vector<uint32_t> infOrder, infStatus;
+    uint64_t infCalls = 0, infBlocks = 0, infBytes = 0, infBad = 0; double infKernelMs = 0; int infGrid = 0;
+  } inf;
+  // the text buffer (dText, textLen bytes; dTextAlt takes the tail when the consumed bytes leave), per tile its summary and carry-in, the
+  // record table with the sequence-byte index at every record start, keep flags, packed start of every record, the totals block, scratch
+  // for a piece that is not staged
+  struct Text {
+    DevBuf dText, dTextAlt, dTextSum, dTextCarry, dTextRecs, dTextSeqStart, dTextKeep, dTextPackOff, dTextTotals, dTextNames, dTextWords;
+    size_t textLen = 0; bool textScanned = false; int textFormat = 0, textFinal = 0;
+    size_t textRecords = 0, textNameBytes = 0, textConsumed = 0;
+    DevEvent textEvA, textEvB, textDone;
+    uint64_t textScans = 0, textRecordsTotal = 0, textBytesTotal = 0; double textScanMs = 0, textPackMs = 0;
+  } text;
+  int ready(int device, InflateErr* e);                 // inflateMu held: the device is set and the stream exists
+};
+
 struct mm_ctx : ReadBatch {                             // the resident reads: the base
   int device = 0;
-  hipStream_t stream = nullptr;
+  DevStream stream;
   mm_params P{};
   mm_env env;
   std::string err;
@@ -237,26 +279,8 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   DevBuf dMinHits, dCutoffs; size_t nMinHits = 0, nCutoffs = 0;
 
   DevBuf dAscii;                                        // the resident batch's ASCII bytes as uploaded (an upload's scratch: not part of ReadBatch)
-  // mm_reads_prefetch: the next batch's ASCII bytes, copied on a stream of their own while the current batch is mapped
-  DevBuf dAsciiNext; hipStream_t copyStream = nullptr; hipEvent_t copyDone = nullptr;
-  const void* prefetchPtr = nullptr; const void* prefetchPtr2 = nullptr; size_t prefetchBytes = 0; bool prefetchValid = false, prefetchPacked = false;
-  struct StagedPart { const void* b2; const void* nm; size_t nPacked; size_t off; };   // packed parts sent ahead (mm_reads_prefetch_packed[_append]): [codes | mask] at dAsciiNext + off
-  std::vector<StagedPart> staged; size_t stagedBytes = 0;
-  std::mutex prefetchMu;                                // mm_reads_prefetch* may come from another thread than the uploads (a reader thread): the staging state is shared
-  // mm_inflate_blocks (mm_inflate.hip): a stream, a lock and staging of its own -- a reader thread calls it beside the context's own thread
-  DevBuf dInfComp, dInfOut, dInfDesc, dInfStatus, dInfStats;   // compressed span, payloads packed end to end, descriptors, one status word per block, [next block | blocks, bytes out, bad blocks]
-  hipStream_t inflateStream = nullptr; hipEvent_t infEvA = nullptr, infEvB = nullptr;
-  mutable std::mutex inflateMu;
-  std::vector<mm_inflate_block> infDesc; std::vector<uint32_t> infOrder, infStatus;
-  uint64_t infCalls = 0, infBlocks = 0, infBytes = 0, infBad = 0; double infKernelMs = 0; int infGrid = 0;
-  // mm_text_* (mm_text.hip), under inflateMu and on the inflate stream: the text buffer (dText, textLen bytes; dTextAlt takes the tail when
-  // the consumed bytes leave), per tile its summary and carry-in, the record table with the sequence-byte index at every record start,
-  // keep flags, packed start of every record, the totals block, scratch for a piece that is not staged
-  DevBuf dText, dTextAlt, dTextSum, dTextCarry, dTextRecs, dTextSeqStart, dTextKeep, dTextPackOff, dTextTotals, dTextNames, dTextWords;
-  size_t textLen = 0; bool textScanned = false; int textFormat = 0, textFinal = 0;
-  size_t textRecords = 0, textNameBytes = 0, textConsumed = 0;
-  hipEvent_t textEvA = nullptr, textEvB = nullptr, textDone = nullptr;
-  uint64_t textScans = 0, textRecordsTotal = 0, textBytesTotal = 0; double textScanMs = 0, textPackMs = 0;
+  Staging stage;
+  DeviceInput input;
   ReadBatch parked[MM_BATCH_SLOTS];                     // batches parked beside the resident one (mm_reads_exchange)
 
   // sketches: raw (a4) and after frequent-seed removal (a8)
@@ -265,7 +289,7 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   DevBuf dSketchTabs; int sketchTabsK = 0;        // strip-hasher tables for kmerSize sketchTabsK (built once, copied into LDS by every workgroup)
   // MM_OPT_SKETCH_LARGE: the two counts of k_sketch_large as of the last sketch launch -- copied to the page-locked hSkLarge behind the
   // kernel (the mapping pass resets the words they are counted in); mm_sketch_large_counts waits for skLargeDone when the copy is pending
-  unsigned long long* hSkLarge = nullptr; hipEvent_t skLargeDone = nullptr;
+  PinnedBuf hSkLarge; DevEvent skLargeDone;
   int skLargeState = 0; uint64_t skLargeFrags = 0, skLargeUncut = 0;   // MM_SKL_STATE_*
   DevBuf dQHash, dQStrand;                              // post-removal sketch (written only for fragments that lose a frequent seed)
   DevBuf dStats;                                        // mm_frag_stats[nFrags]
@@ -298,29 +322,28 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   DevBuf dCommCounts, dGathered; std::vector<size_t> gatherCounts, gatherDisp; size_t nGathered = 0; bool gathered = false;
   // overlapped exchange (mm_allgatherv_mappings_begin / _end): a snapshot of the records, a stream of its own, the host thread that
   // runs the exchange while the caller maps the next batch
-  DevBuf dGatherSrc; hipStream_t commStream = nullptr; std::thread gatherThread; int gatherRc = 0; std::string gatherErr;
+  DevBuf dGatherSrc; DevStream commStream; std::thread gatherThread; int gatherRc = 0; std::string gatherErr;
   DevBuf dL2Info, dL2Cnt, dL2Off, dL2Ops, dScanTmp, dL2Tmp, dL2Wide, dL2Exact, dL2Cells, dListB, dListC, dBigList, dMidList, dGrpList;     // L2 staging: per-candidate stream extents, op counts/offsets, located ops
   DevBuf dL2InitCells, dL2InitState;                                 // per candidate of a chunk: the SlideMapper state after the pre-load, as k_l2_locate leaves it for the sweeps
   DevBuf dL2Sort[4], dL2Order, dL2OrderPos;                          // candidates of a chunk in order of descending stream length (mm_order_desc)
   bool sketched = false, mapped = false;
-  unsigned long long* hPass = nullptr;                  // page-locked mirror of dCounters (MM_COUNTER_BYTES, word for word): the parts a pass reads back at its end
+  PinnedBuf hPass;                                      // page-locked mirror of dCounters (MM_COUNTER_BYTES, word for word): the parts a pass reads back at its end
   bool refGroupMonotone = true;                         // the index's refGroup array is non-decreasing (checked where it arrives: mm_flatten_device_index; mm_index_replicate carries it)
 
   // profiling
   bool profile = false;
   double kMs[MM_K_COUNT] = {0};
   uint64_t kLaunches[MM_K_COUNT] = {0};
-  hipEvent_t evA = nullptr, evB = nullptr;              // mm_bench_hash_only's own pair
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> evPool; size_t evUsed = 0;   // KernelTimer brackets recorded since the last mm_profile_collect
+  DevEvent evA, evB;                                    // mm_bench_hash_only's own pair
+  std::vector<std::pair<DevEvent, DevEvent>> evPool; size_t evUsed = 0;       // KernelTimer brackets recorded since the last mm_profile_collect
   std::vector<std::pair<int, size_t>> evPending;                              // (kernel, pool index)
 };
 
 const char* mm_inflate_take_error(const mm_ctx* c);     // mm_inflate.hip: the text of this thread's failed mm_inflate_blocks / mm_text_* on c, once; else null
-struct InflateErr { std::string err; };                 // what MM_HIP writes to on the reader thread's paths (never mm_ctx::err)
 void mm_inflate_keep_error(const mm_ctx* c, InflateErr& e, int rc);   // rc != MM_OK: e's text becomes this thread's for c; MM_OK: forgets it
 int mm_inflate_run(mm_ctx* c, InflateErr* e, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks, void* dst, size_t nDst, size_t* nBad, uint8_t* devOut);
-// the staging area of packed pieces (mm_api.hip; prefetchMu held): where a piece of nPackedBases goes -- *fits = false: no room under the
-// pieces on their way -- and its entry once its words are on their way there (copyDone recorded behind them)
+// the staging area of packed pieces (mm_api.hip; prefetchMu held): the area sized and stage.ring.next the place of a piece of nPackedBases
+// -- *fits = false: no room under the pieces on their way -- and its entry once its words are on their way there (copyDone recorded behind them)
 int mm_stage_place(mm_ctx* c, size_t nPackedBases, size_t reservePackedBases, bool* fits);
 void mm_stage_commit(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases);
 // the resident batch changed (an upload, an exchange): nothing sketched, mapped or gathered belongs to it
@@ -334,6 +357,21 @@ inline void mm_batch_changed(mm_ctx* c) { c->sketched = false; c->mapped = false
       return MM_ERR_DEVICE;                                                                      \
     }                                                                                            \
   } while (0)
+inline int DeviceInput::ready(int device, InflateErr* e) {
+  MM_HIP(e, hipSetDevice(device));
+  MM_HIP(e, inflateStream.ensure());
+  return MM_OK;
+}
+// an entry point of mm_inflate.hip / mm_text.hip: body(InflateErr*) runs under inflateMu, and its error text is kept for the calling thread
+template <class F>
+int mm_input_call(mm_ctx* c, F&& body) {
+  if (!c) return MM_ERR_ARG;
+  InflateErr e;
+  std::lock_guard<std::mutex> lock(c->input.inflateMu);
+  const int rc = body(&e);
+  mm_inflate_keep_error(c, e, rc);
+  return rc;
+}
 // a host synchronisation of a mapping pass: counted (mm_pass_syncs)
 #define MM_SYNC(c) do { MM_HIP(c, hipStreamSynchronize((c)->stream)); (c)->rep.nSyncs++; } while (0)
 
@@ -346,11 +384,11 @@ struct KernelTimer {
     if (!c->profile) return;
     if (c->evUsed == c->evPool.size()) {
       // the pool is recycled by mm_profile_collect (every profiled entry point that synchronises calls it); a caller that records
-      // thousands of brackets without one gets no more events than this, and a failing hipEventCreate switches the timers off
+      // thousands of brackets without one gets no more events than this, and a failing event creation switches the timers off
       if (c->evPool.size() >= 8192) return;
-      hipEvent_t a = nullptr, b = nullptr;
-      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { if (a) (void)hipEventDestroy(a); c->profile = false; return; }
-      c->evPool.emplace_back(a, b);
+      std::pair<DevEvent, DevEvent> pr;
+      if (pr.first.ensure() != hipSuccess || pr.second.ensure() != hipSuccess) { c->profile = false; return; }
+      c->evPool.push_back(std::move(pr));
     }
     idx = c->evUsed++;
     on = hipEventRecord(c->evPool[idx].first, c->stream) == hipSuccess;

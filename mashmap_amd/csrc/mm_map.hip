@@ -1736,9 +1736,10 @@ static int pass_lookup(mm_ctx* c, MapPass& p) {
     MM_HIP(c, hipMemcpyAsync(p.hc, cnt, sizeof p.hc, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipMemcpyAsync(&p.hMid, cnt + MM_PC_MID_LEN, 8, hipMemcpyDeviceToHost, c->stream));
     MM_HIP(c, hipMemcpyAsync(p.hcur, c->dL1Cursors.p, sizeof p.hcur, hipMemcpyDeviceToHost, c->stream));
-    MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_HARD_COPY, all + MM_CW_HARD_COPY, 8, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long* hPass = c->hPass.as<unsigned long long>();
+    MM_HIP(c, hipMemcpyAsync(hPass + MM_CW_HARD_COPY, all + MM_CW_HARD_COPY, 8, hipMemcpyDeviceToHost, c->stream));
     MM_SYNC(c);
-    c->rep.lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
+    c->rep.lastHard = (size_t)(hPass[MM_CW_HARD_COPY] & 0xffffffffull);
     if (p.hc[MM_PC_POINT_OVERFLOW]) { c->ptsCap = mm_pts_cap_grown(mm_scaled(c, (size_t)p.hc[MM_PC_POINT_CURSOR], 16)); continue; }
     if (p.hc[MM_PC_L1_OVERFLOW]) {                            // some region overflowed: size for the largest one seen
       unsigned long long mx = 0;
@@ -1871,10 +1872,11 @@ static int pass_l1_sweeps(mm_ctx* c, MapPass& p) {
     MM_HIP(c, hipMemcpyAsync(p.hc + MM_PC_L1_CAND, cnt + MM_PC_L1_CAND, 16, hipMemcpyDeviceToHost, c->stream));   // the cursor and its overflow flag
     // ... and, with them, the length of the list k_l1_stream left for k_l1_sweep (the 64-bit word that holds MM_SL_LITERAL)
     constexpr int litWord = MM_CW_SORT_LENS + MM_SL_LITERAL / 2;
-    MM_HIP(c, hipMemcpyAsync(c->hPass + litWord, c->dCounters.as<unsigned long long>() + litWord, 8, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long* hPass = c->hPass.as<unsigned long long>();
+    MM_HIP(c, hipMemcpyAsync(hPass + litWord, c->dCounters.as<unsigned long long>() + litWord, 8, hipMemcpyDeviceToHost, c->stream));
     MM_SYNC(c);
     // (set again by every attempt of this loop: the last one, whose candidates stand, is the one that counts)
-    p.nLit = p.windowed ? 0ull : stream ? (unsigned long long)((const unsigned int*)(c->hPass + MM_CW_SORT_LENS))[MM_SL_LITERAL] : (unsigned long long)nBig;
+    p.nLit = p.windowed ? 0ull : stream ? (unsigned long long)((const unsigned int*)(hPass + MM_CW_SORT_LENS))[MM_SL_LITERAL] : (unsigned long long)nBig;
     if (c->env.debug && stream && p.fl.skipPrefix) fprintf(stderr, "[mm] point path: of %d queued fragments the literal L1 kernel took %llu (reference groups on the wave kernel)\n", nBig, p.nLit);
     if (!p.hc[MM_PC_L1_OVERFLOW]) return MM_OK;
     // grow, keeping the fused candidates already in the buffer
@@ -1903,13 +1905,14 @@ static int pass_finish(mm_ctx* c, MapPass& p) {
   if (rc != MM_OK || !p.steady) return rc;
   // the pass is over: the parts of the counter block it has written come back, each to its place in the mirror
   const unsigned long long* all = c->dCounters.as<unsigned long long>();
-  MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_PASS, all + MM_CW_PASS, (size_t)MM_PC_READ * 8, hipMemcpyDeviceToHost, c->stream));
-  MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_MAP, all + MM_CW_MAP, (size_t)(MM_CW_MAP_END - MM_CW_MAP) * 8, hipMemcpyDeviceToHost, c->stream));
-  MM_HIP(c, hipMemcpyAsync(c->hPass + MM_CW_HARD_COPY, all + MM_CW_HARD_COPY, 8, hipMemcpyDeviceToHost, c->stream));
+  unsigned long long* hPass = c->hPass.as<unsigned long long>();
+  MM_HIP(c, hipMemcpyAsync(hPass + MM_CW_PASS, all + MM_CW_PASS, (size_t)MM_PC_READ * 8, hipMemcpyDeviceToHost, c->stream));
+  MM_HIP(c, hipMemcpyAsync(hPass + MM_CW_MAP, all + MM_CW_MAP, (size_t)(MM_CW_MAP_END - MM_CW_MAP) * 8, hipMemcpyDeviceToHost, c->stream));
+  MM_HIP(c, hipMemcpyAsync(hPass + MM_CW_HARD_COPY, all + MM_CW_HARD_COPY, 8, hipMemcpyDeviceToHost, c->stream));
   MM_SYNC(c);
-  const unsigned long long* h = c->hPass + MM_CW_PASS; const unsigned long long* hm = c->hPass + MM_CW_MAP;
+  const unsigned long long* h = hPass + MM_CW_PASS; const unsigned long long* hm = hPass + MM_CW_MAP;
   PassReport& r = c->rep;
-  r.lastHard = (size_t)(c->hPass[MM_CW_HARD_COPY] & 0xffffffffull);
+  r.lastHard = (size_t)(hPass[MM_CW_HARD_COPY] & 0xffffffffull);
   if (mm_pass_incomplete(h) || hm[MM_MC_OVERFLOW]) { r.redoCause = mm_redo_cause(h, hm); return MM_PASS_REDO; }   // some buffer was too small for this batch: the sized pass grows it
   r.nL1 = (size_t)h[MM_PC_L1_CAND]; r.nL2 = (size_t)h[MM_PC_L2_LOCI]; r.nMappings = c->haveReplayTables ? (size_t)hm[MM_MC_MAPPINGS] : 0;
   r.lastOps = (size_t)hm[MM_MC_L2_OPS]; r.lastBig = c->sized.seen.prevBig;        // (MM_PC_BIG_LEN holds MM_PC_L2_WIDE_LEN by now: the sized pass's figure stands in)
@@ -1945,7 +1948,7 @@ int mm_launch_map(mm_ctx* c) {
   MM_HIP(c, c->dStats.ensure(cF * sizeof(mm_frag_stats) + 64));
   MM_HIP(c, c->dPtOff.ensure(cF * 16 + 64)); MM_HIP(c, c->dL1Off.ensure(cF * 8 + 64)); MM_HIP(c, c->dPtKept.ensure(cF * 4 + 64));
   MM_HIP(c, c->dCounters.ensure(MM_COUNTER_BYTES));
-  if (!c->hPass) { MM_HIP(c, hipHostMalloc((void**)&c->hPass, MM_COUNTER_BYTES, hipHostMallocDefault)); }
+  MM_HIP(c, c->hPass.ensure(MM_COUNTER_BYTES));
   c->rep = PassReport{};
   if (nF == 0) return MM_OK;
   const bool neverSteady = mm_never_steady(c->opt, (c->P.flags & MM_FLAG_SKIP_PREFIX) != 0, c->windowed, s);

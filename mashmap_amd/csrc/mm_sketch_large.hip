@@ -154,7 +154,7 @@ int launch_sketch_large_k(mm_ctx* c) {
   // the mapping pass resets the block: the two counts go to a page-locked spot right behind the kernel; mm_sketch_large_counts waits for
   // the copy, nothing else does
   static_assert(MM_SKW_LARGE_UNCUT == MM_SKW_LARGE_FRAGS + 1, "the two counts are copied as one range");
-  MM_HIP(c, hipMemcpyAsync(c->hSkLarge, words + MM_SKW_LARGE_FRAGS, 16, hipMemcpyDeviceToHost, c->stream));
+  MM_HIP(c, hipMemcpyAsync(c->hSkLarge.p, words + MM_SKW_LARGE_FRAGS, 16, hipMemcpyDeviceToHost, c->stream));
   MM_HIP(c, hipEventRecord(c->skLargeDone, c->stream));
   c->skLargeState = MM_SKL_STATE_PENDING;
   return MM_OK;
@@ -165,8 +165,8 @@ int launch_sketch_large_k(mm_ctx* c) {
 // every resident fragment through k_sketch_large (mm_launch_sketch routes here under MM_OPT_SKETCH_LARGE when the sketch does not fit the LDS kernels)
 int mm_launch_sketch_large(mm_ctx* c) {
   if (c->nFrags == 0) return MM_OK;
-  if (!c->hSkLarge) MM_HIP(c, hipHostMalloc((void**)&c->hSkLarge, 16, hipHostMallocDefault));
-  if (!c->skLargeDone) MM_HIP(c, hipEventCreateWithFlags(&c->skLargeDone, hipEventDisableTiming));
+  MM_HIP(c, c->hSkLarge.ensure(16));
+  MM_HIP(c, c->skLargeDone.ensure(hipEventDisableTiming));
   switch (c->P.kmerSize) {
 #define MM_CASE(KK) case KK: return launch_sketch_large_k<KK>(c);
     MM_FOR_EACH_K(MM_CASE)
@@ -180,7 +180,8 @@ int mm_sketch_large_counts(mm_ctx* c, uint64_t* fragments, uint64_t* uncut) {
   if (c->skLargeState == MM_SKL_STATE_PENDING) {
     MM_HIP(c, hipSetDevice(c->device));
     MM_HIP(c, hipEventSynchronize(c->skLargeDone));
-    c->skLargeFrags = c->hSkLarge[0]; c->skLargeUncut = c->hSkLarge[1];
+    const unsigned long long* h = c->hSkLarge.as<unsigned long long>();
+    c->skLargeFrags = h[0]; c->skLargeUncut = h[1];
     c->skLargeState = MM_SKL_STATE_KNOWN;
   }
   if (fragments) *fragments = c->skLargeFrags;

@@ -290,142 +290,136 @@ __global__ __launch_bounds__(64 * MMT_WAVES) void k_text_pack(const uint8_t* __r
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// entry points.  Every one takes inflateMu and leaves its error text to the calling thread (mm_inflate_keep_error).
+// entry points.  Every one runs under DeviceInput::inflateMu and leaves its error text to the calling thread (mm_input_call).
 // ---------------------------------------------------------------------------------------------------------------------------------
-template <class F>
-static int text_call(mm_ctx* c, F&& f) {
-  if (!c) return MM_ERR_ARG;
-  InflateErr e;
-  std::lock_guard<std::mutex> lock(c->inflateMu);
-  const int rc = f(&e);
-  mm_inflate_keep_error(c, e, rc);
-  return rc;
-}
-
 static int text_stream(mm_ctx* c, InflateErr* e) {
-  MM_HIP(e, hipSetDevice(c->device));
-  if (!c->inflateStream) MM_HIP(e, hipStreamCreateWithFlags(&c->inflateStream, hipStreamNonBlocking));
-  if (!c->textEvA) MM_HIP(e, hipEventCreate(&c->textEvA));
-  if (!c->textEvB) MM_HIP(e, hipEventCreate(&c->textEvB));
-  if (!c->textDone) MM_HIP(e, hipEventCreateWithFlags(&c->textDone, hipEventDisableTiming));
+  DeviceInput::Text& T = c->input.text;
+  { const int rc = c->input.ready(c->device, e); if (rc != MM_OK) return rc; }
+  MM_HIP(e, T.textEvA.ensure());
+  MM_HIP(e, T.textEvB.ensure());
+  MM_HIP(e, T.textDone.ensure(hipEventDisableTiming));
   return MM_OK;
 }
 
 // room for `more` bytes behind the textLen the buffer holds, which stay
 static int text_room(mm_ctx* c, InflateErr* e, size_t more, const char* who) {
-  if (more > 0xffffffffull - c->textLen) { e->err = std::string(who) + ": the text buffer holds at most 2^32 - 1 bytes"; return MM_ERR_ARG; }
-  const size_t need = c->textLen + more + 64;
-  if (need <= c->dText.bytes) return MM_OK;
-  MM_HIP(e, c->dTextAlt.ensure(need));
-  if (c->textLen) MM_HIP(e, hipMemcpyAsync(c->dTextAlt.p, c->dText.p, c->textLen, hipMemcpyDeviceToDevice, c->inflateStream));
-  MM_HIP(e, hipStreamSynchronize(c->inflateStream));
-  std::swap(c->dText, c->dTextAlt);
+  DeviceInput::Text& T = c->input.text;
+  if (more > 0xffffffffull - T.textLen) { e->err = std::string(who) + ": the text buffer holds at most 2^32 - 1 bytes"; return MM_ERR_ARG; }
+  const size_t need = T.textLen + more + 64;
+  if (need <= T.dText.bytes) return MM_OK;
+  MM_HIP(e, T.dTextAlt.ensure(need));
+  if (T.textLen) MM_HIP(e, hipMemcpyAsync(T.dTextAlt.p, T.dText.p, T.textLen, hipMemcpyDeviceToDevice, c->input.inflateStream));
+  MM_HIP(e, hipStreamSynchronize(c->input.inflateStream));
+  std::swap(T.dText, T.dTextAlt);
   return MM_OK;
 }
 
-static float text_elapsed(mm_ctx* c) {
+static float text_elapsed(const DeviceInput::Text& T) {
   float ms = 0;
-  if (hipEventElapsedTime(&ms, c->textEvA, c->textEvB) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (hipEventElapsedTime(&ms, T.textEvA, T.textEvB) != hipSuccess) { (void)hipGetLastError(); return 0; }
   return ms;
 }
 
 static int text_scan(mm_ctx* c, InflateErr* e, int format, int final, size_t* nRecords, size_t* nNameBytes, size_t* consumed) {
+  DeviceInput::Text& T = c->input.text;
   if (format != MM_TEXT_FASTA && format != MM_TEXT_FASTQ) { e->err = "mm_text_scan: unknown format"; return MM_ERR_ARG; }
   { const int rc = text_stream(c, e); if (rc != MM_OK) return rc; }
   final = final != 0;
-  c->textScanned = false;
-  c->textFormat = format; c->textFinal = final; c->textRecords = 0; c->textNameBytes = 0; c->textConsumed = 0; c->textScanMs = 0;
-  if (c->textLen) {
-    hipStream_t st = c->inflateStream;
-    const uint64_t nBytes = c->textLen;
+  T.textScanned = false;
+  T.textFormat = format; T.textFinal = final; T.textRecords = 0; T.textNameBytes = 0; T.textConsumed = 0; T.textScanMs = 0;
+  if (T.textLen) {
+    hipStream_t st = c->input.inflateStream;
+    const uint64_t nBytes = T.textLen;
     const uint32_t nTiles = (uint32_t)((nBytes + MM_TEXT_TILE - 1) / MM_TEXT_TILE);
     const unsigned grid = (nTiles + MMT_WAVES - 1) / MMT_WAVES;
-    MM_HIP(e, c->dTextSum.ensure((size_t)nTiles * sizeof(MmTextSum)));
-    MM_HIP(e, c->dTextCarry.ensure(((size_t)nTiles + 1) * sizeof(MmTextCarry)));
-    MM_HIP(e, c->dTextTotals.ensure(MMT_T_WORDS * 8));
-    unsigned long long* totals = c->dTextTotals.as<unsigned long long>();
+    MM_HIP(e, T.dTextSum.ensure((size_t)nTiles * sizeof(MmTextSum)));
+    MM_HIP(e, T.dTextCarry.ensure(((size_t)nTiles + 1) * sizeof(MmTextCarry)));
+    MM_HIP(e, T.dTextTotals.ensure(MMT_T_WORDS * 8));
+    unsigned long long* totals = T.dTextTotals.as<unsigned long long>();
     unsigned long long h[MMT_T_WORDS] = {0};
     MM_HIP(e, hipMemsetAsync(totals, 0, MMT_T_WORDS * 8, st));
-    MM_HIP(e, hipEventRecord(c->textEvA, st));
-    hipLaunchKernelGGL(k_text_summarise, dim3(grid), dim3(64 * MMT_WAVES), 0, st, c->dText.as<uint8_t>(), nBytes, format, nTiles, c->dTextSum.as<MmTextSum>());
+    MM_HIP(e, hipEventRecord(T.textEvA, st));
+    hipLaunchKernelGGL(k_text_summarise, dim3(grid), dim3(64 * MMT_WAVES), 0, st, T.dText.as<uint8_t>(), nBytes, format, nTiles, T.dTextSum.as<MmTextSum>());
     MM_HIP(e, hipGetLastError());
-    hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(MMT_SCAN_THREADS), 0, st, c->dText.as<uint8_t>(), nBytes, format, final, nTiles, c->dTextSum.as<MmTextSum>(),
-                       c->dTextCarry.as<MmTextCarry>(), totals);
+    hipLaunchKernelGGL(k_text_scan, dim3(1), dim3(MMT_SCAN_THREADS), 0, st, T.dText.as<uint8_t>(), nBytes, format, final, nTiles, T.dTextSum.as<MmTextSum>(),
+                       T.dTextCarry.as<MmTextCarry>(), totals);
     MM_HIP(e, hipGetLastError());
-    MM_HIP(e, hipEventRecord(c->textEvB, st));
+    MM_HIP(e, hipEventRecord(T.textEvB, st));
     MM_HIP(e, hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, st));
     MM_HIP(e, hipStreamSynchronize(st));
-    double ms = text_elapsed(c);
+    double ms = text_elapsed(T);
     // the table: a row for every header line the carry counted and one more (the kernels check every row against it)
     const uint64_t rows = h[MMT_T_ROWS];
     if (h[MMT_T_RECORDS] >= rows || h[MMT_T_HEADERS] >= rows || rows > 0xffffffffull) { e->err = "mm_text_scan: inconsistent totals"; return MM_ERR_DEVICE; }
-    MM_HIP(e, c->dTextRecs.ensure((size_t)rows * sizeof(mm_text_record)));
-    MM_HIP(e, c->dTextSeqStart.ensure((size_t)rows * sizeof(uint32_t)));
-    MM_HIP(e, hipMemsetAsync(c->dTextRecs.p, 0, (size_t)rows * sizeof(mm_text_record), st));
-    MM_HIP(e, hipMemsetAsync(c->dTextSeqStart.p, 0, (size_t)rows * sizeof(uint32_t), st));
-    MM_HIP(e, hipEventRecord(c->textEvA, st));
-    hipLaunchKernelGGL(k_text_records, dim3(grid), dim3(64 * MMT_WAVES), 0, st, c->dText.as<uint8_t>(), nBytes, format, nTiles, c->dTextCarry.as<MmTextCarry>(),
-                       c->dTextRecs.as<mm_text_record>(), c->dTextSeqStart.as<uint32_t>(), (uint32_t)rows, totals);
+    MM_HIP(e, T.dTextRecs.ensure((size_t)rows * sizeof(mm_text_record)));
+    MM_HIP(e, T.dTextSeqStart.ensure((size_t)rows * sizeof(uint32_t)));
+    MM_HIP(e, hipMemsetAsync(T.dTextRecs.p, 0, (size_t)rows * sizeof(mm_text_record), st));
+    MM_HIP(e, hipMemsetAsync(T.dTextSeqStart.p, 0, (size_t)rows * sizeof(uint32_t), st));
+    MM_HIP(e, hipEventRecord(T.textEvA, st));
+    hipLaunchKernelGGL(k_text_records, dim3(grid), dim3(64 * MMT_WAVES), 0, st, T.dText.as<uint8_t>(), nBytes, format, nTiles, T.dTextCarry.as<MmTextCarry>(),
+                       T.dTextRecs.as<mm_text_record>(), T.dTextSeqStart.as<uint32_t>(), (uint32_t)rows, totals);
     MM_HIP(e, hipGetLastError());
-    hipLaunchKernelGGL(k_text_finish, dim3((unsigned)((rows + MMT_WAVES - 1) / MMT_WAVES)), dim3(64 * MMT_WAVES), 0, st, c->dText.as<uint8_t>(), nBytes,
-                       c->dTextRecs.as<mm_text_record>(), c->dTextSeqStart.as<uint32_t>(), (uint32_t)rows, totals);
+    hipLaunchKernelGGL(k_text_finish, dim3((unsigned)((rows + MMT_WAVES - 1) / MMT_WAVES)), dim3(64 * MMT_WAVES), 0, st, T.dText.as<uint8_t>(), nBytes,
+                       T.dTextRecs.as<mm_text_record>(), T.dTextSeqStart.as<uint32_t>(), (uint32_t)rows, totals);
     MM_HIP(e, hipGetLastError());
-    MM_HIP(e, hipEventRecord(c->textEvB, st));
+    MM_HIP(e, hipEventRecord(T.textEvB, st));
     MM_HIP(e, hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, st));
     MM_HIP(e, hipStreamSynchronize(st));
-    ms += text_elapsed(c);
+    ms += text_elapsed(T);
     if (h[MMT_T_CONSUMED] > nBytes) { e->err = "mm_text_scan: inconsistent totals"; return MM_ERR_DEVICE; }
-    c->textRecords = (size_t)h[MMT_T_RECORDS]; c->textNameBytes = (size_t)h[MMT_T_NAME_BYTES]; c->textConsumed = (size_t)h[MMT_T_CONSUMED];
-    c->textScanMs = ms;
+    T.textRecords = (size_t)h[MMT_T_RECORDS]; T.textNameBytes = (size_t)h[MMT_T_NAME_BYTES]; T.textConsumed = (size_t)h[MMT_T_CONSUMED];
+    T.textScanMs = ms;
   }
-  c->textScanned = true;
-  c->textScans++; c->textRecordsTotal += c->textRecords; c->textBytesTotal += c->textConsumed;
-  if (nRecords) *nRecords = c->textRecords;
-  if (nNameBytes) *nNameBytes = c->textNameBytes;
-  if (consumed) *consumed = c->textConsumed;
+  T.textScanned = true;
+  T.textScans++; T.textRecordsTotal += T.textRecords; T.textBytesTotal += T.textConsumed;
+  if (nRecords) *nRecords = T.textRecords;
+  if (nNameBytes) *nNameBytes = T.textNameBytes;
+  if (consumed) *consumed = T.textConsumed;
   return MM_OK;
 }
 
 static int text_records(mm_ctx* c, InflateErr* e, mm_text_record* recs, char* names) {
-  if (!c->textScanned) { e->err = "mm_text_records: no mm_text_scan since the text buffer last changed"; return MM_ERR_STATE; }
-  const size_t n = c->textRecords;
+  DeviceInput::Text& T = c->input.text;
+  if (!T.textScanned) { e->err = "mm_text_records: no mm_text_scan since the text buffer last changed"; return MM_ERR_STATE; }
+  const size_t n = T.textRecords;
   if (!n || (!recs && !names)) return MM_OK;
   { const int rc = text_stream(c, e); if (rc != MM_OK) return rc; }
-  hipStream_t st = c->inflateStream;
+  hipStream_t st = c->input.inflateStream;
   std::vector<mm_text_record> own;
   if (!recs) { own.resize(n); recs = own.data(); }
-  MM_HIP(e, hipMemcpyAsync(recs, c->dTextRecs.p, n * sizeof(mm_text_record), hipMemcpyDeviceToHost, st));
+  MM_HIP(e, hipMemcpyAsync(recs, T.dTextRecs.p, n * sizeof(mm_text_record), hipMemcpyDeviceToHost, st));
   MM_HIP(e, hipStreamSynchronize(st));
-  if (!names || !c->textNameBytes) return MM_OK;
+  if (!names || !T.textNameBytes) return MM_OK;
   std::vector<uint64_t> off(n);
   uint64_t at = 0;
   for (size_t r = 0; r < n; r++) { off[r] = at; at += recs[r].nameLen; }
-  if (at != c->textNameBytes) { e->err = "mm_text_records: inconsistent name lengths"; return MM_ERR_DEVICE; }
+  if (at != T.textNameBytes) { e->err = "mm_text_records: inconsistent name lengths"; return MM_ERR_DEVICE; }
   const size_t offBytes = (n * 8 + 63) / 64 * 64;
-  MM_HIP(e, c->dTextNames.ensure(offBytes + (size_t)at + 64));
-  MM_HIP(e, hipMemcpyAsync(c->dTextNames.p, off.data(), n * 8, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_text_names, dim3((unsigned)((n + MMT_WAVES - 1) / MMT_WAVES)), dim3(64 * MMT_WAVES), 0, st, c->dText.as<uint8_t>(), (uint64_t)c->textLen,
-                     c->dTextRecs.as<mm_text_record>(), (uint32_t)n, c->dTextNames.as<uint64_t>(), c->dTextNames.as<uint8_t>() + offBytes, at);
+  MM_HIP(e, T.dTextNames.ensure(offBytes + (size_t)at + 64));
+  MM_HIP(e, hipMemcpyAsync(T.dTextNames.p, off.data(), n * 8, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_text_names, dim3((unsigned)((n + MMT_WAVES - 1) / MMT_WAVES)), dim3(64 * MMT_WAVES), 0, st, T.dText.as<uint8_t>(), (uint64_t)T.textLen,
+                     T.dTextRecs.as<mm_text_record>(), (uint32_t)n, T.dTextNames.as<uint64_t>(), T.dTextNames.as<uint8_t>() + offBytes, at);
   MM_HIP(e, hipGetLastError());
-  MM_HIP(e, hipMemcpyAsync(names, c->dTextNames.as<char>() + offBytes, (size_t)at, hipMemcpyDeviceToHost, st));
+  MM_HIP(e, hipMemcpyAsync(names, T.dTextNames.as<char>() + offBytes, (size_t)at, hipMemcpyDeviceToHost, st));
   MM_HIP(e, hipStreamSynchronize(st));
   return MM_OK;
 }
 
 static int text_pack(mm_ctx* c, InflateErr* e, const uint8_t* keep, uint32_t* bases2, uint32_t* nmask, size_t capPackedBases, size_t reservePackedBases,
                      size_t* nPackedBases, int* staged) {
-  if (!c->textScanned) { e->err = "mm_text_pack: no mm_text_scan since the text buffer last changed"; return MM_ERR_STATE; }
+  DeviceInput::Text& T = c->input.text;
+  if (!T.textScanned) { e->err = "mm_text_pack: no mm_text_scan since the text buffer last changed"; return MM_ERR_STATE; }
   { const int rc = text_stream(c, e); if (rc != MM_OK) return rc; }
-  hipStream_t st = c->inflateStream;
-  const size_t nRec = c->textRecords;
+  hipStream_t st = c->input.inflateStream;
+  const size_t nRec = T.textRecords;
   uint64_t nPacked = 0;
-  c->textPackMs = 0;
+  T.textPackMs = 0;
   if (nRec) {
-    unsigned long long* totals = c->dTextTotals.as<unsigned long long>();
-    MM_HIP(e, c->dTextPackOff.ensure(nRec * sizeof(int64_t)));
-    if (keep) { MM_HIP(e, c->dTextKeep.ensure(nRec)); MM_HIP(e, hipMemcpyAsync(c->dTextKeep.p, keep, nRec, hipMemcpyHostToDevice, st)); }
-    const uint8_t* dKeep = keep ? c->dTextKeep.as<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(k_text_plan, dim3(1), dim3(MMT_SCAN_THREADS), 0, st, c->dTextRecs.as<mm_text_record>(), (uint32_t)nRec, dKeep, c->dTextPackOff.as<int64_t>(), totals);
+    unsigned long long* totals = T.dTextTotals.as<unsigned long long>();
+    MM_HIP(e, T.dTextPackOff.ensure(nRec * sizeof(int64_t)));
+    if (keep) { MM_HIP(e, T.dTextKeep.ensure(nRec)); MM_HIP(e, hipMemcpyAsync(T.dTextKeep.p, keep, nRec, hipMemcpyHostToDevice, st)); }
+    const uint8_t* dKeep = keep ? T.dTextKeep.as<uint8_t>() : nullptr;
+    hipLaunchKernelGGL(k_text_plan, dim3(1), dim3(MMT_SCAN_THREADS), 0, st, T.dTextRecs.as<mm_text_record>(), (uint32_t)nRec, dKeep, T.dTextPackOff.as<int64_t>(), totals);
     MM_HIP(e, hipGetLastError());
     unsigned long long h[2] = {0, 0};
     MM_HIP(e, hipMemcpyAsync(h, totals + MMT_T_PACKED, sizeof h, hipMemcpyDeviceToHost, st));
@@ -438,47 +432,48 @@ static int text_pack(mm_ctx* c, InflateErr* e, const uint8_t* keep, uint32_t* ba
   int isStaged = 0;
   if (nPacked) {
     // under prefetchMu until the words are where they go: the staging area is shared with the uploads of the context's own thread
-    std::lock_guard<std::mutex> prefetchLock(c->prefetchMu);
+    Staging& S = c->stage;
+    std::lock_guard<std::mutex> prefetchLock(S.prefetchMu);
     bool fits = false;
     { const int rc = mm_stage_place(c, (size_t)nPacked, reservePackedBases, &fits); if (rc != MM_OK) { e->err = c->err; return rc; } }
     char* dst;
-    if (fits) dst = (char*)c->dAsciiNext.p + c->stagedBytes;
-    else { MM_HIP(e, c->dTextWords.ensure((size_t)nPacked / 4 + (size_t)nPacked / 8 + 64)); dst = c->dTextWords.as<char>(); }
+    if (fits) dst = S.dAsciiNext.as<char>() + S.ring.next;
+    else { MM_HIP(e, T.dTextWords.ensure(StageRing::bytes((size_t)nPacked) + 64)); dst = T.dTextWords.as<char>(); }
     uint32_t* dB = (uint32_t*)dst; uint32_t* dM = (uint32_t*)(dst + nPacked / 4);
-    const uint64_t nBytes = c->textConsumed;                       // the complete records lie in front of `consumed`
+    const uint64_t nBytes = T.textConsumed;                       // the complete records lie in front of `consumed`
     const uint32_t nTiles = (uint32_t)((nBytes + MM_TEXT_TILE - 1) / MM_TEXT_TILE);
-    MM_HIP(e, hipMemsetAsync(dst, 0, (size_t)nPacked / 4 + (size_t)nPacked / 8, st));
-    MM_HIP(e, hipEventRecord(c->textEvA, st));
-    hipLaunchKernelGGL(k_text_pack, dim3((nTiles + MMT_WAVES - 1) / MMT_WAVES), dim3(64 * MMT_WAVES), 0, st, c->dText.as<uint8_t>(), nBytes, c->textFormat, nTiles,
-                       c->dTextCarry.as<MmTextCarry>(), (uint32_t)nRec, keep ? c->dTextKeep.as<uint8_t>() : nullptr, c->dTextPackOff.as<int64_t>(),
-                       c->dTextSeqStart.as<uint32_t>(), dB, dM, nPacked);
+    MM_HIP(e, hipMemsetAsync(dst, 0, StageRing::bytes((size_t)nPacked), st));
+    MM_HIP(e, hipEventRecord(T.textEvA, st));
+    hipLaunchKernelGGL(k_text_pack, dim3((nTiles + MMT_WAVES - 1) / MMT_WAVES), dim3(64 * MMT_WAVES), 0, st, T.dText.as<uint8_t>(), nBytes, T.textFormat, nTiles,
+                       T.dTextCarry.as<MmTextCarry>(), (uint32_t)nRec, keep ? T.dTextKeep.as<uint8_t>() : nullptr, T.dTextPackOff.as<int64_t>(),
+                       T.dTextSeqStart.as<uint32_t>(), dB, dM, nPacked);
     MM_HIP(e, hipGetLastError());
-    MM_HIP(e, hipEventRecord(c->textEvB, st));
+    MM_HIP(e, hipEventRecord(T.textEvB, st));
     if (fits) {
       // the upload waits for copyDone: recorded on the copy stream behind this kernel
-      MM_HIP(e, hipEventRecord(c->textDone, st));
-      MM_HIP(e, hipStreamWaitEvent(c->copyStream, c->textDone, 0));
-      MM_HIP(e, hipEventRecord(c->copyDone, c->copyStream));
+      MM_HIP(e, hipEventRecord(T.textDone, st));
+      MM_HIP(e, hipStreamWaitEvent(S.copyStream, T.textDone, 0));
+      MM_HIP(e, hipEventRecord(S.copyDone, S.copyStream));
     } else {
       MM_HIP(e, hipMemcpyAsync(bases2, dB, (size_t)nPacked / 4, hipMemcpyDeviceToHost, st));
       MM_HIP(e, hipMemcpyAsync(nmask, dM, (size_t)nPacked / 8, hipMemcpyDeviceToHost, st));
     }
     MM_HIP(e, hipStreamSynchronize(st));
     if (fits) { mm_stage_commit(c, bases2, nmask, (size_t)nPacked); isStaged = 1; }
-    c->textPackMs = text_elapsed(c);
+    T.textPackMs = text_elapsed(T);
   }
   // the consumed bytes leave: the tail goes to the other buffer, which becomes the text buffer
-  const size_t tail = c->textLen - c->textConsumed;
-  if (c->textConsumed) {
+  const size_t tail = T.textLen - T.textConsumed;
+  if (T.textConsumed) {
     if (tail) {
-      MM_HIP(e, c->dTextAlt.ensure(tail + 64));
-      MM_HIP(e, hipMemcpyAsync(c->dTextAlt.p, c->dText.as<char>() + c->textConsumed, tail, hipMemcpyDeviceToDevice, st));
+      MM_HIP(e, T.dTextAlt.ensure(tail + 64));
+      MM_HIP(e, hipMemcpyAsync(T.dTextAlt.p, T.dText.as<char>() + T.textConsumed, tail, hipMemcpyDeviceToDevice, st));
       MM_HIP(e, hipStreamSynchronize(st));
-      std::swap(c->dText, c->dTextAlt);
+      std::swap(T.dText, T.dTextAlt);
     }
-    c->textLen = tail;
+    T.textLen = tail;
   }
-  c->textScanned = false;
+  T.textScanned = false;
   if (nPackedBases) *nPackedBases = (size_t)nPacked;
   if (staged) *staged = isStaged;
   return MM_OK;
@@ -487,25 +482,27 @@ static int text_pack(mm_ctx* c, InflateErr* e, const uint8_t* keep, uint32_t* ba
 extern "C" {
 
 int mm_text_reset(mm_ctx* c) {
-  return text_call(c, [&](InflateErr*) -> int { c->textLen = 0; c->textScanned = false; return MM_OK; });
+  return mm_input_call(c, [&](InflateErr*) -> int { c->input.text.textLen = 0; c->input.text.textScanned = false; return MM_OK; });
 }
 
 int mm_text_append(mm_ctx* c, const void* bytes, size_t n, int onDevice) {
-  return text_call(c, [&](InflateErr* e) -> int {
+  return mm_input_call(c, [&](InflateErr* e) -> int {
+    DeviceInput::Text& T = c->input.text;
     if (n && !bytes) { e->err = "mm_text_append: null argument"; return MM_ERR_ARG; }
     if (!n) return MM_OK;
     { const int rc = text_stream(c, e); if (rc != MM_OK) return rc; }
     { const int rc = text_room(c, e, n, "mm_text_append"); if (rc != MM_OK) return rc; }
-    MM_HIP(e, hipMemcpyAsync(c->dText.as<char>() + c->textLen, bytes, n, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->inflateStream));
-    MM_HIP(e, hipStreamSynchronize(c->inflateStream));
-    c->textLen += n; c->textScanned = false;
+    MM_HIP(e, hipMemcpyAsync(T.dText.as<char>() + T.textLen, bytes, n, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->input.inflateStream));
+    MM_HIP(e, hipStreamSynchronize(c->input.inflateStream));
+    T.textLen += n; T.textScanned = false;
     return MM_OK;
   });
 }
 
 int mm_text_append_inflated(mm_ctx* c, const void* comp, size_t nComp, mm_inflate_block* blocks, size_t nBlocks, size_t* nBad) {
   if (nBad) *nBad = 0;
-  return text_call(c, [&](InflateErr* e) -> int {
+  return mm_input_call(c, [&](InflateErr* e) -> int {
+    DeviceInput::Text& T = c->input.text;
     if (nBlocks && !blocks) { e->err = "mm_text_append_inflated: null argument"; return MM_ERR_ARG; }
     uint64_t total = 0;
     for (size_t i = 0; i < nBlocks; i++) {
@@ -515,42 +512,42 @@ int mm_text_append_inflated(mm_ctx* c, const void* comp, size_t nComp, mm_inflat
     { const int rc = text_stream(c, e); if (rc != MM_OK) return rc; }
     { const int rc = text_room(c, e, (size_t)total, "mm_text_append_inflated"); if (rc != MM_OK) return rc; }
     size_t bad = 0;
-    const int rc = mm_inflate_run(c, e, comp, nComp, blocks, nBlocks, nullptr, ~(size_t)0, &bad, c->dText.as<uint8_t>() + c->textLen);
+    const int rc = mm_inflate_run(c, e, comp, nComp, blocks, nBlocks, nullptr, ~(size_t)0, &bad, T.dText.as<uint8_t>() + T.textLen);
     if (nBad) *nBad = bad;
     if (rc != MM_OK) return rc;
-    if (!bad && total) { c->textLen += (size_t)total; c->textScanned = false; }   // a refused block: the bytes behind textLen are nobody's
+    if (!bad && total) { T.textLen += (size_t)total; T.textScanned = false; }   // a refused block: the bytes behind textLen are nobody's
     return MM_OK;
   });
 }
 
 int mm_text_scan(mm_ctx* c, int format, int final, size_t* nRecords, size_t* nNameBytes, size_t* consumed) {
-  return text_call(c, [&](InflateErr* e) -> int { return text_scan(c, e, format, final, nRecords, nNameBytes, consumed); });
+  return mm_input_call(c, [&](InflateErr* e) -> int { return text_scan(c, e, format, final, nRecords, nNameBytes, consumed); });
 }
 
 int mm_text_records(mm_ctx* c, mm_text_record* recs, char* names) {
-  return text_call(c, [&](InflateErr* e) -> int { return text_records(c, e, recs, names); });
+  return mm_input_call(c, [&](InflateErr* e) -> int { return text_records(c, e, recs, names); });
 }
 
 int mm_text_pack(mm_ctx* c, const uint8_t* keep, uint32_t* bases2, uint32_t* nmask, size_t capPackedBases, size_t reservePackedBases, size_t* nPackedBases, int* staged) {
   if (nPackedBases) *nPackedBases = 0;
   if (staged) *staged = 0;
-  return text_call(c, [&](InflateErr* e) -> int { return text_pack(c, e, keep, bases2, nmask, capPackedBases, reservePackedBases, nPackedBases, staged); });
+  return mm_input_call(c, [&](InflateErr* e) -> int { return text_pack(c, e, keep, bases2, nmask, capPackedBases, reservePackedBases, nPackedBases, staged); });
 }
 
 int mm_text_counts(const mm_ctx* c, uint64_t* scans, uint64_t* records, uint64_t* bytes) {
   if (!c) return MM_ERR_ARG;
-  std::lock_guard<std::mutex> lock(c->inflateMu);
-  if (scans) *scans = c->textScans;
-  if (records) *records = c->textRecordsTotal;
-  if (bytes) *bytes = c->textBytesTotal;
+  std::lock_guard<std::mutex> lock(c->input.inflateMu);
+  if (scans) *scans = c->input.text.textScans;
+  if (records) *records = c->input.text.textRecordsTotal;
+  if (bytes) *bytes = c->input.text.textBytesTotal;
   return MM_OK;
 }
 
 int mm_text_kernel_ms(const mm_ctx* c, double* scanMs, double* packMs) {
   if (!c) return MM_ERR_ARG;
-  std::lock_guard<std::mutex> lock(c->inflateMu);
-  if (scanMs) *scanMs = c->textScanMs;
-  if (packMs) *packMs = c->textPackMs;
+  std::lock_guard<std::mutex> lock(c->input.inflateMu);
+  if (scanMs) *scanMs = c->input.text.textScanMs;
+  if (packMs) *packMs = c->input.text.textPackMs;
   return MM_OK;
 }
 

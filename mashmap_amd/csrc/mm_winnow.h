@@ -16,17 +16,12 @@ struct WinnowBuffers {       // grow-only device scratch shared by the contigs o
   // (a vector sized first is zero-filled first)
   // Two of them, taken in turns: the host thread that finishes contig i copies its records out of one while the device fills the other
   // with contig i+1's (the caller waits for the copy-out of contig i-2 before it hands a buffer to the device again).
-  void* hStage[2] = {nullptr, nullptr}; size_t hStageBytes[2] = {0, 0}; int turn = 0;
+  PinnedBuf hStage[2]; int turn = 0;
   void* host(size_t bytes) {                     // nullptr when page-locking fails: the caller copies into pageable memory as before
-    void*& h = hStage[turn]; size_t& hb = hStageBytes[turn];
-    if (bytes <= hb) return h;
-    if (h) { (void)hipHostFree(h); h = nullptr; hb = 0; }
-    const size_t cap = bytes + bytes / 8 + 4096;
-    if (hipHostMalloc(&h, cap, hipHostMallocDefault) != hipSuccess) { h = nullptr; (void)hipGetLastError(); return nullptr; }
-    hb = cap;
-    return h;
+    PinnedBuf& h = hStage[turn];
+    if (bytes > h.bytes) (void)h.ensure(bytes + bytes / 8 + 4096);   // (a failure leaves it empty)
+    return h.p;
   }
-  ~WinnowBuffers() { for (void* h : hStage) if (h) (void)hipHostFree(h); }   // the two page-locked areas; the device buffers free themselves
 };
 
 // records in the reference's emission order (wpos == WN_CARRY where the run started before its tile), per-tile record counts,
