@@ -267,6 +267,19 @@ k_sketch_all_hard(int nF, int32_t* __restrict__ hardList, uint32_t* __restrict__
 //   * SL positions per thread are chosen so that the threads fill whole waves (4 982 k-mers: 250 threads x 20 positions = 4 waves,
 //     one per SIMD, instead of 312 x 16 = 5 waves of which two share a SIMD).
 // A fragment that overflows any of it (queue, table, duplicate list) or keeps fewer than s distinct survivors goes to the hard list.
+//
+// The kernel is bound by VALU issue, not by waiting: at configs[1] (2 M fragments of 5 kbp, s = 130, k = 19) it issues vector instructions
+// at the rate of the hash-only yardstick (SQ_INSTS_VALU per launch / kernel time: profiles/r14_13_configs1_pmc_SQ_INSTS_VALU.csv,
+// r14_14_configs1_kernel_stats.csv),
+//     k_hash_only<19,20>     22.0 G wave-instructions   35.3 ms   0.62 G / ms
+//     k_sketch_fast<19,20>   26.3 G                     41.4 ms   0.64 G / ms        (k_l2_sweep 0.65, k_l2_locate 0.47, k_lookup_l1 0.41)
+// so only fewer or cheaper vector instructions shorten it; one instruction per position is 0.156 G per launch, about 0.25 ms.  Hence the
+// strip loop (onPos below) does per position only what decides whether the position is queued -- one v_min_u32 and one 32-bit compare on
+// the high words of the two hashes -- and leaves the rest to the 3.6 % that pass (behind a wave-uniform branch) or, once per queued
+// position, to the drain: which of the two hashes is the smaller, whether they tie, whether the position exists and its k-mer holds no N.
+// The loop issues 8.05 VALU instructions per position on top of the hash-only loop's 135.7, of which 2 are outside that branch
+// (profiles/sketch_opcode_histogram_hiword.txt; 12.6, all but the push outside a branch, with every test on 64 bits and per position:
+// profiles/r14_04_sketch_opcode_histogram.txt).
 // ---------------------------------------------------------------------------------------------
 #define MM_SKF_FLAG 0x80000000u
 struct SkFast : SkCut {
@@ -334,7 +347,10 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   if (hasN) mm_sk_stage(sM, nM, nmask, fr.base >> 5, (int)(fr.base & 31), tid, nthr);
   // threshold: the canonical hash is the smaller of two uniform 64-bit values, so P[h < T] ~ 2T / 2^64; the cut is placed where
   // `wantFast` (> s) survivors are expected.  Any T gives the exact sketch as long as >= s distinct hashes survive (checked below).
-  const uint64_t T = mm_sketch_fast_cut(wantFast, n);
+  // From k = 16 on the loop tests the high words alone (HIWORD, below), so the cut is rounded up to a multiple of 2^32 there -- the same
+  // value wherever wantFast / 2n >= 2^-9, the float's 24 bits then end above the low word (mm_sketch_dev.h).
+  constexpr bool HIWORD = K >= 16;
+  const uint64_t T = HIWORD ? mm_sketch_cut_hiword(mm_sketch_fast_cut(wantFast, n)) : mm_sketch_fast_cut(wantFast, n);
   const int nStrips = (n + SL - 1) / SL;
   tab.set_cut(T, (uint32_t)HT);
   for (int i = tid; i < NS; i += nthr) tab.key[i] = MM_HASH_MAX;
@@ -347,13 +363,16 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   const uint32_t qBase = (uint32_t)(tid >> 6) * (uint32_t)QC, qEnd = qBase + (uint32_t)QC;
   uint32_t qHead = qBase;                           // wave-uniform (only ballots feed it)
   const uint64_t allPassM = (T == MM_HASH_MAX) ? ~0ull : 0ull;     // wave-uniform
+  const uint32_t cutLast = mm_sketch_cut_last_hi(T), qLast = qEnd - 1u;   // HIWORD: the largest high word under the cut; the wave's last queue entry
+  uint64_t tie = 0;                                 // HIWORD: lanes that queued a position whose two high words are equal (wave-uniform)
   for (int strip = tid; strip < nStrips; strip += nthr) {
     const int b0 = strip * SL;                      // first base of the strip: the 48-base window is cut out of four LDS words
     const int wi = b0 >> 4, bsh = (b0 & 15) * 2;
-    // bit j: position b0 + j exists and its k-mer holds no N
+    // bit j: position b0 + j exists and its k-mer holds no N.  (HIWORD: the drain asks that of the few positions that reach it; positions
+    // past the end and k-mers with an N, which hash as if it were an A, are queued like any other and dropped there)
     const int rem = n - b0;
     uint32_t ok = rem >= SL ? (uint32_t)((1ull << SL) - 1ull) : ((1u << rem) - 1u);
-    if (hasN) {
+    if (!HIWORD && hasN) {
       const int mi = b0 >> 5, msh = b0 & 31;
       const uint64_t lo64 = (uint64_t)sM[mi] | ((uint64_t)sM[mi + 1] << 32);
       if constexpr (MMWideK<K>::value) {            // 16 + K - 1 > 64 mask bits: a 128-bit window
@@ -365,16 +384,42 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
         ok &= ~(uint32_t)mm_window_or<K>(m64);
       }
     }
+    const uint32_t pos2 = (uint32_t)b0 << 1;
     auto onPos = [&](int j, uint64_t hf, uint64_t hr) {
-      const int pos = b0 + j;
-      // the tests as lane masks in scalar registers (mm_device.h): nothing but the two selects of the minimum touches a vector register
-      // (the compiler's own `hf < hr ? hf : hr` is as fast at s = 130 and 0.5 ms per 2 M fragments slower at s = 310: profiles/r06b, r06c)
-      const uint64_t mLt = mm_mask_lt64(hf, hr);
-      const uint64_t h = mm_mask_select64(mLt, hf, hr);
-      const uint64_t m = mm_mask_nz32(ok & (1u << j)) & mm_mask_ne64(hf, hr) & (mm_mask_lt64(h, T) | allPassM);
-      const uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, qHead));
-      if (__builtin_amdgcn_inverse_ballot_w64(m) && idx < qEnd) { qH[idx] = h; qM[idx] = ((uint32_t)pos << 1) | (__builtin_amdgcn_inverse_ballot_w64(mLt) ? 1u : 0u); }
-      qHead += (uint32_t)__popcll(m);
+      if constexpr (HIWORD) {
+        // What every position pays: one v_min_u32 of the two high words and one 32-bit compare.  Only ~3.6 % of the positions pass, and
+        // what only they need is done behind a wave-uniform branch (taken when any of the 64 lanes passes) or left to the drain:
+        //   * the canonical hash is not selected: every passing lane stores hr, the lanes with hf.hi < hr.hi then store hf over it (a wave's
+        //     LDS writes land in program order), each store with its own constant strand bit and both at one address computation;
+        //   * equal high words (hf == hr -- a k-mer that is its own reverse complement, which the reference skips, commonFunc.hpp:237 --
+        //     or a 2^-32 coincidence) are not resolved on the low words: the wave remembers it and the fragment goes to the hard list;
+        //   * an entry beyond the wave's queue overwrites the queue's last one: the count behind the loop sends the fragment to the
+        //     hard list, nothing outside the queue is written.
+        const uint32_t fh = (uint32_t)(hf >> 32), rh = (uint32_t)(hr >> 32);
+        const uint64_t m = mm_mask_le32(mm_min_u32(fh, rh), cutLast);
+        if (m) {
+          const uint64_t mF = mm_mask_lt32(fh, rh);
+          tie |= mm_mask_eq32(fh, rh) & m;
+          uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, qHead));
+          idx = idx < qLast ? idx : qLast;
+          if (__builtin_amdgcn_inverse_ballot_w64(m)) {
+            qH[idx] = hr; qM[idx] = pos2 + (uint32_t)(2 * j);
+            if (__builtin_amdgcn_inverse_ballot_w64(mF)) { qH[idx] = hf; qM[idx] = pos2 + (uint32_t)(2 * j + 1); }
+          }
+          qHead += (uint32_t)__popcll(m);
+        }
+      } else {
+        // k-mers of up to 15 bases (many of them their own reverse complement, few distinct ones): every test on the full hashes, per position.
+        // The tests as lane masks in scalar registers (mm_device.h): nothing but the two selects of the minimum touches a vector register
+        // (the compiler's own `hf < hr ? hf : hr` is as fast at s = 130 and 0.5 ms per 2 M fragments slower at s = 310: profiles/r06b, r06c)
+        const int pos = b0 + j;
+        const uint64_t mLt = mm_mask_lt64(hf, hr);
+        const uint64_t h = mm_mask_select64(mLt, hf, hr);
+        const uint64_t m = mm_mask_nz32(ok & (1u << j)) & mm_mask_ne64(hf, hr) & (mm_mask_lt64(h, T) | allPassM);
+        const uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, qHead));
+        if (__builtin_amdgcn_inverse_ballot_w64(m) && idx < qEnd) { qH[idx] = h; qM[idx] = ((uint32_t)pos << 1) | (__builtin_amdgcn_inverse_ballot_w64(mLt) ? 1u : 0u); }
+        qHead += (uint32_t)__popcll(m);
+      }
     };
     if constexpr (MMWideK<K>::value) {              // k-mers of 33..64 bases: 4 or 5 words per strip (SL == 16: the strip starts on a word)
       uint32_t ww[MMWideK<K>::NW];
@@ -394,7 +439,8 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
   {
     // lanes that left the strip loop early (or never entered it) hold a stale count; lane 0 owns the smallest strip
     const uint32_t qCount = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qHead - qBase));
-    if (mm_lane() == 0) { qCnt[tid >> 6] = qCount; if (qCount > (uint32_t)QC) atomicOr(&tab.counters[MM_TC_OVERFLOW], 1u); }
+    const bool tied = mm_bcast64_readfirstlane(tie) != 0ull;   // equal high words on a queued position: the exact kernel looks at all 64 bits
+    if (mm_lane() == 0) { qCnt[tid >> 6] = qCount; if (qCount > (uint32_t)QC || tied) atomicOr(&tab.counters[MM_TC_OVERFLOW], 1u); }
   }
   __syncthreads();
   mark(2);                                          // waiting for the other waves' hash loops
@@ -404,6 +450,12 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
 #pragma unroll
     for (int w = 0; w < 16; w++) pre[w + 1] = pre[w] + (w < nWaves ? qCnt[w] : 0u);
     const uint32_t total = pre[16];
+    // HIWORD: the loop queued positions without asking whether they have a k-mer (mm_sk_drain_keep: inside the fragment, no N)
+    const uint32_t* const drainMask = hasN ? sM : nullptr;
+    auto drain = [&](uint32_t at) {
+      const uint32_t m = qM[at];
+      if (!HIWORD || mm_sk_drain_keep<K>(m >> 1, (uint32_t)n, drainMask)) tab.insert(qH[at], m);
+    };
     if (nWaves <= 4) {
       // the usual geometry (4 982 k-mers = 250 threads = 4 waves): three compares place an entry instead of the fifteen of the general form
       // below, which were a sixth of the instructions a survivor costs behind the hash loop
@@ -412,7 +464,7 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
         const uint32_t w = (g >= p1 ? 1u : 0u) + (g >= p2 ? 1u : 0u) + (g >= p3 ? 1u : 0u);
         const uint32_t start = g >= p3 ? p3 : (g >= p2 ? p2 : (g >= p1 ? p1 : 0u));
         const uint32_t at = w * (uint32_t)QC + (g - start);
-        tab.insert(qH[at], qM[at]);
+        drain(at);
       }
     } else
     for (uint32_t g = (uint32_t)tid; g < total; g += (uint32_t)nthr) {
@@ -420,7 +472,7 @@ mm_sketch_fast(unsigned char* smem, const int f, const uint4* __restrict__ gTabs
 #pragma unroll
       for (int x = 1; x < 16; x++) if (g >= pre[x]) { w = (uint32_t)x; start = pre[x]; }
       const uint32_t at = w * (uint32_t)QC + (g - start);
-      tab.insert(qH[at], qM[at]);
+      drain(at);
     }
   }
   __syncthreads();

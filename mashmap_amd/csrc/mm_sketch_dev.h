@@ -1,8 +1,42 @@
 // mashmap_amd/csrc/mm_sketch_dev.h -- the device steps that more than one sketch kernel takes (k_sketch_fast, k_hash_only, k_sketch_hard:
 // mm_sketch.hip; k_sketch_global, k_sketch_large; k_ref_hash: mm_index.hip), each stated once.  Everything here is inlined into its callers.
+//
+// The head of the file -- the fast kernel's cut as a high word and its drain's keep / drop decision -- is plain C++ and compiles for the host
+// too (tests/hostlogic/sketch_drain_check.cpp); everything behind it is for hipcc alone.
 #pragma once
-#include "mm_device.h"
 #include "mm_sketch_plan.h"
+
+// ---------------------------------------------------------------------------------------------
+// k_sketch_fast tests a position against its cut on the high words of the two hashes alone, so its cut is a multiple of 2^32: T rounded
+// up (any cut is exact as long as s distinct hashes survive it, and a larger one only lets more through), or no cut where that leaves the
+// 64 bits.  mm_sketch_fast_cut makes T from a float: 24 significant bits, so at T >= 2^55 (n <= 256 wantFast) the low word is zero already
+// and the value -- hence the fragments that go to the hard list -- is what it was.  A position passes when min(hf.hi, hr.hi) <=
+// mm_sketch_cut_last_hi(cut).
+// ---------------------------------------------------------------------------------------------
+MM_SK_HD uint64_t mm_sketch_cut_hiword(uint64_t T) {
+  if (T == MM_SK_HASH_MAX) return T;
+  const uint32_t hi = (uint32_t)(T >> 32) + ((uint32_t)T != 0u ? 1u : 0u);
+  return hi ? (uint64_t)hi << 32 : MM_SK_HASH_MAX;
+}
+MM_SK_HD uint32_t mm_sketch_cut_last_hi(uint64_t cut) { return cut == MM_SK_HASH_MAX ? 0xFFFFFFFFu : (uint32_t)(cut >> 32) - 1u; }
+
+// The fast kernel's hash loop queues every position under the cut, whether or not it has a k-mer; the drain sees each queued position once
+// and keeps it if it lies inside the fragment (pos < n = len - K + 1: the last strip runs past the end) and its k-mer holds no N.
+// maskWords: the fragment's N mask, bit i of word j = base 32 j + i is an N, with two words of run-off behind base len - 1; null when the
+// read holds no N.
+template <int K>
+MM_SK_HD bool mm_sk_drain_keep(uint32_t pos, uint32_t n, const uint32_t* maskWords) {
+  static_assert(K >= 1 && K <= 64, "a k-mer's mask bits span at most three words");
+  if (pos >= n) return false;
+  if (!maskWords) return true;
+  const uint32_t j = pos >> 5, sh = pos & 31u;
+  uint64_t m = ((uint64_t)maskWords[j] | ((uint64_t)maskWords[j + 1] << 32)) >> sh;      // mask bits of bases pos .. pos + 63 - sh
+  if (K > 33 && sh) m |= (uint64_t)maskWords[j + 2] << (64 - sh);                           // K + sh <= 64 otherwise
+  return (m & (K >= 64 ? ~0ull : ((1ull << (K & 63)) - 1ull))) == 0ull;
+}
+
+#ifdef __HIPCC__
+#include "mm_device.h"
 
 // ---------------------------------------------------------------------------------------------
 // The cut of an ordered LDS table (SkTable, SkFast: mm_sketch.hip).  The home slot is a monotone function of the hash: hashes below the
@@ -153,3 +187,4 @@ __device__ __forceinline__ bool mm_sk_emit_sorted(const SkEnt* e, int64_t N2, in
   if (tid == 0) skCount[f] = (uint32_t)(total < s ? total : s);
   return false;
 }
+#endif  // __HIPCC__
