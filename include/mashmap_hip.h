@@ -315,6 +315,8 @@ int mm_pass_redo_cause(const mm_ctx* ctx, uint64_t* cause);
  * more.  Either pointer may be NULL.  Purely additive: MM_ABI_VERSION stays 2.  In a pass that ran k_lookup_groups (MM_OPT_L1_GROUP_FUSED)
  * the HBM point path holds only what that kernel handed over: *queued equals offered - fused of mm_pass_l1_group_fused. */
 int mm_pass_l1_literal(const mm_ctx* ctx, uint64_t* queued, uint64_t* literal);
+/* *mid = fragments k_lookup_l1 passed to k_lookup_mid in the context's last SIZED pass, finished there or handed on to the HBM point path (0 where it did not run). */
+int mm_pass_l1_mid(const mm_ctx* ctx, uint64_t* mid);
 /* Which L2 kernel took the candidates of a batch with a read longer than segLength (MM_FLAG_NO_SPLIT, windowLen != 0), as of the context's
  * last SIZED pass: *candidates = L1 candidates the windowed L2 stage took, *literal = those of them the literal one-thread-per-candidate
  * kernel (k_l2_window) swept -- every one without MM_OPT_L2_WINDOW_WAVE, otherwise the ones the wave-per-candidate kernel hands over: more

@@ -164,6 +164,7 @@ def load():
         "mm_pass_redo_cause": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "mm_pass_l1_literal": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_l1_group_fused": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mm_pass_l1_mid": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "mm_pass_l2_window": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_pass_l2_large": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mm_sketch_large_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -219,7 +220,7 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_reads_upload_packed", "mm_reads_prefetch_packed", "mm_pack_read", "mm_pack_read_portable", "mm_reads_packed_download",
            "mm_index_layout_get", "mm_pass_stats", "mm_comm_info", "mm_pass_totals", "mm_reads_exchange", "mm_reads_upload_packed_parts",
            "mm_reads_prefetch_packed_append", "mm_reads_prefetch_drop", "mm_reads_prefetch_reserve", "mm_pass_redo_cause",
-           "mm_pass_l1_literal", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
+           "mm_pass_l1_literal", "mm_pass_l1_mid", "mm_pass_l2_window", "mm_pass_l1_group_fused", "mm_pass_l2_large",
            "mm_stat_identity_table", "mm_set_chain_tables", "mm_chain_reads", "mm_chain_counts", "mm_chain_download",
            "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts", "mm_device_bytes",
            "mm_sketch_large_counts", "mm_chain_group_counts", "mm_inflate_blocks", "mm_inflate_counts", "mm_inflate_kernel_ms",
@@ -500,6 +501,12 @@ class Context:
         q, l = C.c_uint64(), C.c_uint64()
         self._ck(self.lib.mm_pass_l1_literal(self.h, C.byref(q), C.byref(l)), "mm_pass_l1_literal")
         return int(q.value), int(l.value)
+
+    def pass_l1_mid(self):
+        """fragments of the last sized pass that k_lookup_l1 passed to k_lookup_mid (finished there or handed on to the HBM point path)"""
+        v = C.c_uint64()
+        self._ck(self.lib.mm_pass_l1_mid(self.h, C.byref(v)), "mm_pass_l1_mid")
+        return int(v.value)
 
     def pass_l1_group_fused(self):
         """(offered, fused) of the last sized pass: fragments the lookup kernel queued under MM_FLAG_SKIP_PREFIX, and those of them

@@ -580,6 +580,11 @@ int mm_pass_l1_literal(const mm_ctx* c, uint64_t* queued, uint64_t* literal) {
   return MM_OK;
 }
 
+int mm_pass_l1_mid(const mm_ctx* c, uint64_t* mid) {
+  if (mid) *mid = c->sized.seen.prevMid;
+  return MM_OK;
+}
+
 int mm_pass_l1_group_fused(const mm_ctx* c, uint64_t* offered, uint64_t* fused) {
   if (offered) *offered = c->sized.seen.grpOffered;
   if (fused) *fused = c->sized.seen.grpFused;

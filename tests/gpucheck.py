@@ -96,11 +96,12 @@ def steady_leg(ctx, first, rule):
 
 
 def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=U.FLAG_HG, delim="\0", kmerPct=0.001,
-                    seqCounterBase=0, check_points=True, verbose=True, mutate_index=None, device_index=False, stats_out=None):
+                    seqCounterBase=0, check_points=True, verbose=True, mutate_index=None, device_index=False, stats_out=None, pass_out=None):
     """contigs: [(name, uint8 array)], reads: [(name, uint8 array)].  Returns (nFragments, nMappedLoci).
     device_index: the context builds its own index from the contigs' bases (mm_index_build: a5-a7 on the device) instead of taking the
     oracle's -- every stage downstream is then checked against the oracle on top of the DEVICE-built index.
-    stats_out: a list that receives the per-fragment stats array (mm_frag_stats) of the compared pass."""
+    stats_out: a list that receives the per-fragment stats array (mm_frag_stats) of the compared pass.
+    pass_out: a dict that receives, of the first (sized, default-path) pass, "mid" = pass_l1_mid() and "literal" = pass_l1_literal()."""
     from mashmap_amd import capi
     h = oracle.session(contigs, k, L, s, pi, U.FILTER_MAP, flags, delim.encode() if delim != "\0" else b"\0", kmerPct, mutate_index=mutate_index)
     ix = oracle.export_index(h)
@@ -132,6 +133,7 @@ def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=
     # steady-state pass behind it --, then again with the point lists kept in HBM (sort + literal sweep kernels); all must reproduce
     # the reference, and agree with each other
     ctx.map()
+    if pass_out is not None: pass_out.update(mid=ctx.pass_l1_mid(), literal=ctx.pass_l1_literal())
     fast = pass_bytes(ctx)
     steady_leg(ctx, fast, must_be_steady(flags, s, L, reads, ctx.result_counts()[0]))
     ctx.keep_points(True)
