@@ -432,6 +432,54 @@ int mm_chain_group_counts(const mm_ctx* ctx, uint64_t* reads, uint64_t* runs);
 int mm_chain_download(mm_ctx* ctx, mm_chain_row* out, size_t cap, size_t* n);
 int mm_chain_leftover_download(mm_ctx* ctx, mm_mapping* out, size_t cap, size_t* n);
 int mm_chain_device(const mm_ctx* ctx, const mm_chain_row** dRows, size_t* nRows, const mm_mapping** dLeftover, size_t* nLeftover);
+/*
+ * The PAF lines of a pass on the device: what the host side's MapPost::finishRows + appendReadMappings make of the rows of
+ * mm_chain_reads -- filterFalseHighIdentity (computeMap.hpp:441), mappingBoundarySanityCheck (:1714) and the text of every line
+ * (:1758-1806), byte for byte.  The restatement is mashmap_amd/csrc/mm_paf_core.h (compiled for the host by
+ * tests/hostlogic/paf_check.cpp, which holds it against MapPost); DESIGN.md section 6 says why the bytes are the host's.
+ *
+ * mm_paf_params: legacy = Parameters::legacy_output (separator ' ', ends minus 1, last field nucIdentity * 100); aniPercentage =
+ * report_ANI_percentage; merge = mergeMappings (0 adds the jc:f: field); filterLengthMismatches with lenIdThreshold = the host's own
+ * std::min(0.7, std::pow(percentageIdentity, 3)); sparsityThreshold = sparsity_hash_threshold, which must be 2^64 - 1: sparsifyMappings
+ * hashes through std::hash<float> and is not restated (MM_ERR_ARG otherwise).
+ * mm_set_paf_tables uploads the block, the mapQ table and the contigs' names and lengths; it needs no index.  fakeMapQ is not computed
+ * on the device (log10f there is not the host's bit for bit): mapqThresholds are nMapq (1 .. MM_PAF_MAX_MAPQ) ascending floats with
+ * mapqThresholds[0] == 0 and the last <= 1, mapqText holds MM_PAF_MAPQ_TEXT bytes an entry, NUL-padded with at least one NUL: the text of
+ * fakeMapQ for every identity t in thresholds[i] <= t < thresholds[i + 1] (the last entry: up to 1).  The host library builds it from
+ * MapPost's own expression (mmh_paf_mapq_table).  refNames are the contigs' names end to end, refNameOff[i] .. refNameOff[i + 1] contig
+ * i's (non-decreasing, nContigs + 1 entries).
+ * mm_paf_rows formats the rows mm_chain_reads left resident for the mapped batch: nReads must be the batch's read count, read index =
+ * querySeqId - seqCounterBase, queryNames / queryNameOff as the reference's.  mm_paf_format does the same for rows the caller brings
+ * (host memory, read-major: querySeqId - firstSeqId in [0, nReads), non-decreasing), with readLens[nReads]; it needs neither an index nor
+ * a mapped batch.  Both run on the context's stream and wait once, for the counts, before the text is written.
+ * The output is the text of all reads in read order, lines in row order inside a read; off[r] .. off[r + 1] is read r's span (empty for a
+ * read without rows or whose rows were all dropped).  A read with a row that is NOT FORMATTABLE -- an identity outside [0, 1], or a
+ * floating-point field that is inf, NaN or, unless it is +-0, outside 2^-64 <= |v| < 2^64 -- is handed over as a whole: empty span,
+ * handed[r] = 1, and the caller finishes it from mm_chain_download's rows; nothing is ever written for a read in part.
+ * MM_ERR_STATE / MM_ERR_ARG with the reason in mm_last_error, before anything is launched: tables not set; mm_chain_reads has not run
+ * on the mapped batch (mm_paf_rows); nReads mismatch; name offsets not non-decreasing; more than 2^31 - 1 rows; a row of mm_paf_format
+ * whose refSeqId lies outside the contigs or whose querySeqId lies outside the reads or breaks read order ("corrupt row").  The rows of
+ * mm_paf_rows are on the device: the same test runs in the first kernel, which reads no name or length for such a row, and the call
+ * answers MM_ERR_STATE "corrupt row" behind its one wait, before any text is written.  An empty batch or one without rows is MM_OK
+ * with zero counts.  A new upload or map call invalidates the results.
+ * mm_paf_counts: reads with a non-empty span, lines and bytes of the text, rows the two filters dropped (over all rows, those of
+ * handed-over reads included), reads handed over.  mm_paf_download copies the text (*n = its bytes; MM_ERR_ARG when cap is smaller),
+ * mm_paf_offsets_download off[nReads + 1] and, when non-NULL, handed[nReads]; mm_paf_device gives the device addresses, valid until the
+ * next mm_paf_* or map call.  Any pointer of mm_paf_counts / mm_paf_device may be NULL.
+ * Purely additive: MM_ABI_VERSION stays 2.
+ */
+#define MM_PAF_MAPQ_TEXT 8
+#define MM_PAF_MAX_MAPQ 128
+typedef struct { int32_t legacy, aniPercentage, merge, filterLengthMismatches; double lenIdThreshold; uint64_t sparsityThreshold; } mm_paf_params;
+int mm_set_paf_tables(mm_ctx* ctx, const mm_paf_params* params, const float* mapqThresholds, const char* mapqText, size_t nMapq,
+                      const char* refNames, const uint64_t* refNameOff, const int32_t* refLens, size_t nContigs);
+int mm_paf_rows(mm_ctx* ctx, const char* queryNames, const uint64_t* queryNameOff, size_t nReads);
+int mm_paf_format(mm_ctx* ctx, const mm_chain_row* rows, size_t nRows, const int32_t* readLens, int32_t firstSeqId,
+                  const char* queryNames, const uint64_t* queryNameOff, size_t nReads);
+int mm_paf_counts(const mm_ctx* ctx, uint64_t* readsWithText, uint64_t* lines, uint64_t* bytes, uint64_t* dropped, uint64_t* handedReads);
+int mm_paf_download(mm_ctx* ctx, char* text, size_t cap, size_t* n);
+int mm_paf_offsets_download(mm_ctx* ctx, int64_t* off, uint8_t* handed);
+int mm_paf_device(const mm_ctx* ctx, const char** dText, size_t* n, const int64_t** dOff);
 /* post-removal sketches Q.minmerTableQuery: out[f*sketchSize + r] (valid r < stats[f].sketchSize) */
 int mm_query_sketch_download(mm_ctx* ctx, mm_minmer* out);
 /*

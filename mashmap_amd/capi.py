@@ -43,6 +43,13 @@ class ChainParams(C.Structure):
                 ("merge", C.c_int32), ("filter", C.c_int32), ("kmerComplexityThreshold", C.c_float), ("pad", C.c_int32)]
 
 
+class PafParams(C.Structure):
+    """mm_paf_params (include/mashmap_hip.h)"""
+    _fields_ = [("legacy", C.c_int32), ("aniPercentage", C.c_int32), ("merge", C.c_int32), ("filterLengthMismatches", C.c_int32),
+                ("lenIdThreshold", C.c_double), ("sparsityThreshold", C.c_uint64)]
+
+
+MM_PAF_MAPQ_TEXT, MM_PAF_MAX_MAPQ = 8, 128
 MM_CHAIN_MAX_RECORDS, MM_CHAIN_MAX_SKETCH, MM_CHAIN_MAX_GAP = 16, 2048, 1 << 25
 MM_CHAIN_LONG_MAX_RECORDS = 512      # with MM_OPT_CHAIN_LONG: what k_chain_reads_long takes
 MM_CHAIN_FILTER_NONE, MM_CHAIN_FILTER_QUERY = 0, 1
@@ -182,6 +189,13 @@ def load():
         "mm_chain_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_leftover_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "mm_chain_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
+        "mm_set_paf_tables": (C.c_int, [vp, C.POINTER(PafParams), vp, vp, sz, vp, vp, vp, sz]),
+        "mm_paf_rows": (C.c_int, [vp, vp, vp, sz]),
+        "mm_paf_format": (C.c_int, [vp, vp, sz, vp, i32, vp, vp, sz]),
+        "mm_paf_counts": (C.c_int, [vp] + [C.POINTER(C.c_uint64)] * 5),
+        "mm_paf_download": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
+        "mm_paf_offsets_download": (C.c_int, [vp, vp, vp]),
+        "mm_paf_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]),
         "mm_device_bytes": (sz, []),
         "mm_inflate_blocks": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, C.POINTER(sz)]),
         "mm_inflate_counts": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -225,7 +239,8 @@ EXPORTS = ["mm_abi_version", "mm_create", "mm_destroy", "mm_last_error", "mm_ind
            "mm_chain_leftover_download", "mm_chain_device", "mm_chain_long_counts", "mm_device_bytes",
            "mm_sketch_large_counts", "mm_chain_group_counts", "mm_inflate_blocks", "mm_inflate_counts", "mm_inflate_kernel_ms",
            "mm_text_reset", "mm_text_append", "mm_text_append_inflated", "mm_text_scan", "mm_text_records", "mm_text_pack", "mm_text_counts",
-           "mm_text_kernel_ms"]
+           "mm_text_kernel_ms", "mm_set_paf_tables", "mm_paf_rows", "mm_paf_format", "mm_paf_counts", "mm_paf_download",
+           "mm_paf_offsets_download", "mm_paf_device"]
 
 
 def device_bytes():
@@ -274,6 +289,26 @@ def stat_identity_table(sketchSize, k):
     if load().mm_stat_identity_table(sketchSize, k, _ptr(out)) != 0:
         raise MashmapError("mm_stat_identity_table failed")
     return out
+
+
+def paf_mapq_table():
+    """(thresholds float32[n], text bytes[n * 8]) of fakeMapQ over [0, 1], from MapPost's own expression in libmashmap_host.so
+    (mmh_paf_mapq_table): what mm_set_paf_tables takes.  log10f is the host's, never restated here"""
+    from . import shard
+    thr = np.zeros(MM_PAF_MAX_MAPQ, dtype=np.float32); txt = np.zeros(MM_PAF_MAX_MAPQ * MM_PAF_MAPQ_TEXT, dtype=np.uint8)
+    n = shard.host_lib().mmh_paf_mapq_table(_ptr(thr), _ptr(txt), MM_PAF_MAX_MAPQ)
+    if n < 1:
+        raise MashmapError("mmh_paf_mapq_table failed (%d)" % n)
+    return thr[:n].copy(), txt[:n * MM_PAF_MAPQ_TEXT].copy()
+
+
+def pack_names(names):
+    """(bytes end to end as uint8, offsets uint64[n + 1]) of a list of names (str or bytes): the form the mm_paf_* calls take names in"""
+    raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    off = np.zeros(len(raw) + 1, dtype=np.uint64)
+    if raw:
+        off[1:] = np.cumsum([len(b) for b in raw], dtype=np.uint64)
+    return np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8).copy(), off
 
 
 def pack_reads(reads, portable=False):
@@ -690,6 +725,58 @@ class Context:
         a, b, na, nb = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
         self._ck(self.lib.mm_chain_device(self.h, C.byref(a), C.byref(na), C.byref(b), C.byref(nb)), "mm_chain_device")
         return a.value, na.value, b.value, nb.value
+
+    # ---- the PAF lines on the device
+    def set_paf_tables(self, ref_names, ref_lens, legacy=False, aniPercentage=False, merge=True, filterLengthMismatches=False, lenIdThreshold=0.7,
+                       sparsityThreshold=(1 << 64) - 1, mapq=None):
+        """mm_set_paf_tables: the parameter block, the mapQ table (paf_mapq_table() unless given as (thresholds, text)) and the contigs'
+        names and lengths.  lenIdThreshold is the host's std::min(0.7, std::pow(percentageIdentity, 3))"""
+        thr, txt = paf_mapq_table() if mapq is None else mapq
+        thr = np.ascontiguousarray(thr, dtype=np.float32); txt = np.ascontiguousarray(txt, dtype=np.uint8)
+        names, off = pack_names(ref_names)
+        lens = np.ascontiguousarray(ref_lens, dtype=np.int32)
+        assert len(lens) == len(off) - 1
+        p = PafParams(1 if legacy else 0, 1 if aniPercentage else 0, 1 if merge else 0, 1 if filterLengthMismatches else 0, lenIdThreshold, sparsityThreshold)
+        self._ck(self.lib.mm_set_paf_tables(self.h, C.byref(p), _ptr(thr), _ptr(txt), len(thr), _ptr(names), _ptr(off), _ptr(lens), len(lens)), "mm_set_paf_tables")
+
+    def paf_rows(self, query_names):
+        """mm_paf_rows: the PAF lines of the rows chain_reads() left, for the mapped batch's reads (their names, in batch order)"""
+        names, off = pack_names(query_names)
+        self._ck(self.lib.mm_paf_rows(self.h, _ptr(names), _ptr(off), len(off) - 1), "mm_paf_rows")
+
+    def paf_format(self, rows, read_lens, query_names, firstSeqId=0):
+        """mm_paf_format: the PAF lines of rows the caller brings (CHAIN_ROW_DT, read-major)"""
+        rows = np.ascontiguousarray(rows, dtype=CHAIN_ROW_DT); lens = np.ascontiguousarray(read_lens, dtype=np.int32)
+        names, off = pack_names(query_names)
+        assert len(lens) == len(off) - 1
+        self._ck(self.lib.mm_paf_format(self.h, _ptr(rows), len(rows), _ptr(lens), firstSeqId, _ptr(names), _ptr(off), len(lens)), "mm_paf_format")
+
+    def paf_counts(self):
+        """dict(readsWithText, lines, bytes, dropped, handedReads) of the last paf_rows() / paf_format()"""
+        v = [C.c_uint64() for _ in range(5)]
+        self._ck(self.lib.mm_paf_counts(self.h, *[C.byref(x) for x in v]), "mm_paf_counts")
+        return dict(zip(("readsWithText", "lines", "bytes", "dropped", "handedReads"), (int(x.value) for x in v)))
+
+    def paf_text(self, slack=0, fill=0):
+        """the text as bytes; with slack, a uint8 array of bytes + slack filled with `fill` before the download (what lies behind the text
+        stays as it was)"""
+        n = self.paf_counts()["bytes"]
+        out = np.full(n + slack, fill, dtype=np.uint8); got = C.c_size_t()
+        self._ck(self.lib.mm_paf_download(self.h, _ptr(out), n, C.byref(got)), "mm_paf_download")
+        assert got.value == n
+        return out if slack else out.tobytes()
+
+    def paf_offsets(self, nReads):
+        """(off int64[nReads + 1], handed uint8[nReads]) of the last paf_rows() / paf_format() over nReads reads"""
+        off = np.zeros(nReads + 1, dtype=np.int64); handed = np.zeros(max(nReads, 1), dtype=np.uint8)
+        self._ck(self.lib.mm_paf_offsets_download(self.h, _ptr(off), _ptr(handed)), "mm_paf_offsets_download")
+        return off, handed[:nReads]
+
+    def paf_device(self):
+        """(device address of the text, its bytes, device address of the nReads + 1 offsets)"""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        self._ck(self.lib.mm_paf_device(self.h, C.byref(a), C.byref(n), C.byref(b)), "mm_paf_device")
+        return a.value, n.value, b.value
 
     def comm_init_rank(self, comm_id, rank, world):
         buf = (C.c_char * COMM_ID_BYTES).from_buffer_copy(bytes(comm_id))

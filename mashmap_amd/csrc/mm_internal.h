@@ -317,6 +317,16 @@ struct mm_ctx : ReadBatch {                             // the resident reads: t
   uint64_t chLongOffered = 0, chLongFinished = 0;
   uint64_t chGroupReads = 0, chGroupRuns = 0;           // mm_chain_group_counts: finished reads with more than one run of filterByGroup, and the runs of all of them
   int chainCUs = 0;                                     // compute units of the device (k_chain_reads_long's grid), asked for once
+  // the PAF lines on the device (mm_paf.hip): the tables of mm_set_paf_tables (parameter block, mapQ thresholds and texts, the contigs'
+  // names, name offsets and lengths); per call the reads' names and offsets, the rows and read lengths mm_paf_format brings; per row its
+  // line's length and offset, per read its flag and its offset; the text and the counts.  The results belong to the batch and the pass
+  // they were made in (pafGen, pafPass)
+  DevBuf dPafMapqT, dPafMapqText, dPafRefNames, dPafRefOff, dPafRefLens, dPafQNames, dPafQOff, dPafRows, dPafReadLens;
+  DevBuf dPafLen, dPafRowOff, dPafFlag, dPafOff, dPafText, dPafTotals;
+  mm_paf_params pafP{}; bool havePafTables = false; int32_t pafNMapq = 0; size_t pafNContigs = 0; uint64_t pafRefNameBytes = 0;
+  bool pafDone = false; uint64_t pafGen = 0, pafPass = 0; size_t pafReads = 0;
+  uint64_t pafBytes = 0, pafLines = 0, pafDropped = 0, pafReadsText = 0, pafHanded = 0;
+  uint64_t batchGen = 0;                                // counts the changes of the resident batch (mm_batch_changed)
   // multi-GPU exchange (mm_comm.hip)
   void* comm = nullptr; int commRank = 0, commWorld = 0; bool commCopy = false;   // commCopy: local group whose contexts share a device
   DevBuf dCommCounts, dGathered; std::vector<size_t> gatherCounts, gatherDisp; size_t nGathered = 0; bool gathered = false;
@@ -347,7 +357,7 @@ int mm_inflate_run(mm_ctx* c, InflateErr* e, const void* comp, size_t nComp, mm_
 int mm_stage_place(mm_ctx* c, size_t nPackedBases, size_t reservePackedBases, bool* fits);
 void mm_stage_commit(mm_ctx* c, const uint32_t* bases2, const uint32_t* nmask, size_t nPackedBases);
 // the resident batch changed (an upload, an exchange): nothing sketched, mapped or gathered belongs to it
-inline void mm_batch_changed(mm_ctx* c) { c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false; }
+inline void mm_batch_changed(mm_ctx* c) { c->sketched = false; c->mapped = false; c->fragTabStale = true; c->gathered = false; c->batchGen++; }
 
 #define MM_HIP(ctx, call)                                                                        \
   do {                                                                                           \

@@ -186,6 +186,58 @@ int64_t mmh_chain_rows_modes(int k, int segLength, int sketchSize, float pi, int
                     nReads, firstSeqCounter, maxRecords, out, cap, refGroup, split);
 }
 
+// fakeMapQ over [0, 1] as mm_set_paf_tables takes it, from MapPost's own expression (MapPost::mapqTable): thresholds[cap], text[cap * 8].
+// Returns the number of entries, or -1 when cap is too small.
+int mmh_paf_mapq_table(float* thresholds, char* text, int cap) {
+  std::vector<float> t; std::vector<char> x;
+  skch::MapPost::mapqTable(t, x);
+  if ((size_t)cap < t.size() || !thresholds || !text) return -1;
+  std::memcpy(thresholds, t.data(), t.size() * sizeof(float));
+  std::memcpy(text, x.data(), x.size());
+  return (int)t.size();
+}
+
+// What mm_paf_rows / mm_paf_format must write, from the host's own code: MapPost::finishRows + appendReadMappings of the given rows
+// (read-major, querySeqId - firstSeqId in [0, nReads)), read by read.  Names arrive as the device calls take them: bytes end to end and
+// n + 1 offsets.  text receives the first `cap` bytes, off[nReads + 1] every read's span, reported[nReads] (may be null) the number of
+// lines of every read.  Returns the bytes of the whole text, or -1 for a row outside the reads, the contigs or the sketch size (the
+// identity bound is cached per (sketchSize, conservedSketches) up to the parameter's sketch size).  One thread.
+int64_t mmh_paf_text(int k, int sketchSize, float pi, int legacy, int aniPercentage, int merge, int filterLengthMismatches, int nContigs,
+                     const int32_t* contigLens, const char* refNames, const uint64_t* refNameOff, const mm_chain_row* rows, size_t nRows,
+                     const int32_t* readLens, size_t nReads, int32_t firstSeqId, const char* queryNames, const uint64_t* queryNameOff, char* text,
+                     size_t cap, int64_t* off, int64_t* reported) {
+  skch::Parameters p;
+  p.kmerSize = k; p.sketchSize = sketchSize; p.percentageIdentity = pi; p.filterMode = skch::filter::MAP;
+  p.legacy_output = legacy != 0; p.report_ANI_percentage = aniPercentage != 0; p.mergeMappings = merge != 0; p.filterLengthMismatches = filterLengthMismatches != 0;
+  std::vector<skch::ContigInfo> meta((size_t)nContigs);
+  for (int i = 0; i < nContigs; i++) meta[i] = skch::ContigInfo{std::string(refNames + refNameOff[i], refNames + refNameOff[i + 1]), contigLens[i]};
+  std::vector<int> grp((size_t)nContigs, 0);
+  skch::MapPost post(p, meta, grp);
+  for (size_t i = 0; i < nRows; i++) {
+    const mm_chain_row& r = rows[i];
+    if ((size_t)(uint32_t)(r.querySeqId - firstSeqId) >= nReads || (uint32_t)r.refSeqId >= (uint32_t)nContigs || r.sketchSize < 1 || r.sketchSize > sketchSize ||
+        r.conservedSketches < 0 || r.conservedSketches > sketchSize || (i && rows[i - 1].querySeqId > r.querySeqId)) return -1;
+  }
+  std::string all;
+  skch::MappingResultsVector_t v;
+  size_t i = 0;
+  for (size_t r = 0; r < nReads; r++) {
+    off[r] = (int64_t)all.size();
+    size_t j = i;
+    while (j < nRows && (size_t)(rows[j].querySeqId - firstSeqId) == r) j++;
+    v.clear();
+    if (j > i) {
+      post.finishRows(rows + i, rows + j, readLens[r], v);
+      post.appendReadMappings(v, std::string(queryNames + queryNameOff[r], queryNames + queryNameOff[r + 1]), all);
+    }
+    if (reported) reported[r] = (int64_t)v.size();
+    i = j;
+  }
+  off[nReads] = (int64_t)all.size();
+  if (text && cap) std::memcpy(text, all.data(), std::min(cap, all.size()));
+  return (int64_t)all.size();
+}
+
 // slots of the all-gatherv of candidate mappings (mm_exchange_plan.h, what mm_comm.hip places its RCCL broadcasts by): disp[world + 1]
 uint64_t mmh_exchange_plan(const uint64_t* counts, int world, uint64_t* disp) { return mm_exchange_place(counts, world, disp); }
 

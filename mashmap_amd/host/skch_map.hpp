@@ -93,6 +93,12 @@ class Map {
   // value `all` it gets MM_OPT_CHAIN_LONG and MM_OPT_CHAIN_MODES, and the condition "split reads, no reference groups" falls away: the
   // stage then runs under -Y and --noSplit as well (the reference-axis filter of one-to-one stays on the host)
   bool deviceChain = false, deviceChainLong = false, deviceChainModes = false;
+  // MASHMAP_HIP_DEVICE_PAF: behind mm_chain_reads the device stage runs mm_paf_rows and brings back the PAF text of the reads the device
+  // finished, every read's span in it and the left-over records -- rows only when a read was handed over because one of its rows is not
+  // formattable; the post stage writes the spans and finishes the other reads as before.  Acts only where MASHMAP_HIP_DEVICE_CHAIN acts
+  // -- with this switch set that includes filter mode none --, and then only in a filter mode other than one-to-one (its output is deferred and needs the mappings), without a processMappingResults
+  // callback and without a sparsity threshold; anywhere else one line says why it is ignored
+  bool devicePaf = false;
   bool exchangeFellBack = false;                 // a default RCCL all-gatherv failed once: per-context downloads for the rest of the run
   skch::Time::time_point tStart = skch::Time::now();   // MASHMAP_HIP_TIMING lines carry the time since the Map was constructed
   // one write per diagnostic line: three stages log at once, and `std::cerr << a << b` from two threads interleaves inside a line
@@ -110,6 +116,10 @@ class Map {
     std::shared_ptr<PinnedRecs<mm_mapping>> recOwner; const mm_mapping* recs = nullptr; size_t nRecs = 0;
     // under MASHMAP_HIP_DEVICE_CHAIN: the rows of the reads mm_chain_reads finished (recs are then the handed-over reads' records only)
     std::shared_ptr<PinnedRecs<mm_chain_row>> rowOwner; const mm_chain_row* rows = nullptr; size_t nRows = 0;
+    // under MASHMAP_HIP_DEVICE_PAF: the text mm_paf_rows wrote for the pass, every read's span in it (off, nReads of the pass + 1) and
+    // the reads handed over for a row that is not formattable; this batch's reads start at pafFirst
+    struct PafPass { std::vector<char> text; std::vector<int64_t> off; std::vector<uint8_t> handed; };
+    std::shared_ptr<PafPass> paf; size_t pafFirst = 0;
     mutable std::vector<char> prefetched;        // per context: the batch's block is already on its way to that GPU (guarded by pfMu)
     size_t size() const { return in.names.size(); }
     size_t bases() const { return (size_t)in.totalBases(); }
@@ -142,7 +152,11 @@ class Map {
     }
     const char* chainEnv = getenv("MASHMAP_HIP_DEVICE_CHAIN");
     const bool chainAll = chainEnv && std::strcmp(chainEnv, "all") == 0;
-    if (chainEnv && ctxs.size() == 1 && (chainAll || (p.split && !p.skip_prefix)) && (p.filterMode == filter::MAP || p.filterMode == filter::ONETOONE) &&
+    // (filter mode none: mm_chain_reads takes it as MM_CHAIN_FILTER_NONE; the command line asks for the stage there only together with
+    // MASHMAP_HIP_DEVICE_PAF, so that a run with the chain switch alone does what it did)
+    const bool pafAsked = getenv("MASHMAP_HIP_DEVICE_PAF") != nullptr;
+    if (chainEnv && ctxs.size() == 1 && (chainAll || (p.split && !p.skip_prefix)) &&
+        (p.filterMode == filter::MAP || p.filterMode == filter::ONETOONE || (pafAsked && p.filterMode == filter::NONE)) &&
         p.sketchSize <= MM_CHAIN_MAX_SKETCH && p.chain_gap >= 0 && p.chain_gap <= MM_CHAIN_MAX_GAP) {
       const size_t stride = (size_t)p.sketchSize + 1;
       std::vector<float> identity(stride * stride);
@@ -159,7 +173,25 @@ class Map {
         deviceChainModes = true;
       }
     }
-    if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] integer tables ready" << (deviceChain ? " (chaining on the device)" : "") << at();
+    if (pafAsked) {
+      const char* why = nullptr;
+      if (!deviceChain) why = "MASHMAP_HIP_DEVICE_CHAIN is not set, or does not act in this run";
+      else if (p.filterMode == filter::ONETOONE) why = "filter mode one-to-one defers its output and needs the mappings";
+      else if (processMappingResults) why = "a processMappingResults callback needs the mappings";
+      else if (p.sparsity_hash_threshold != std::numeric_limits<uint64_t>::max()) why = "a sparsity threshold is set (sparsifyMappings stays on the host)";
+      if (why) LogLine() << "[mashmap_hip::skch::Map] MASHMAP_HIP_DEVICE_PAF ignored: " << why;
+      else {
+        std::vector<float> thresholds; std::vector<char> mapqText;
+        MapPost::mapqTable(thresholds, mapqText);
+        std::string names; std::vector<uint64_t> nameOff(1, 0); std::vector<int32_t> lens;
+        for (const auto& m : refsketch.metadata) { names += m.name; nameOff.push_back(names.size()); lens.push_back((int32_t)m.len); }
+        const mm_paf_params pp = post.pafParams();
+        if (mm_set_paf_tables(ctx, &pp, thresholds.data(), mapqText.data(), thresholds.size(), names.data(), nameOff.data(), lens.data(), lens.size()) != MM_OK) die("mm_set_paf_tables");
+        devicePaf = true;
+      }
+    }
+    if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] integer tables ready" << (deviceChain ? " (chaining on the device)" : "")
+                                                << (devicePaf ? " (PAF text on the device)" : "") << at();
     this->mapQuery();
     if (getenv("MASHMAP_HIP_TIMING")) LogLine() << "[mashmap_hip::timing] mapQuery done" << at();
     if (getenv("MASHMAP_HIP_TIMING")) {
@@ -452,7 +484,9 @@ class Map {
       releaseBuffers();
     }
     size_t n = 0;
-    uint64_t longOffered = 0, longFinished = 0, groupReads = 0, groupRuns = 0;
+    uint64_t longOffered = 0, longFinished = 0, groupReads = 0, groupRuns = 0, pafBytes = 0, pafHanded = 0;
+    size_t chainedRows = 0;
+    std::shared_ptr<typename Batch::PafPass> pafPass;
     const auto p2 = skch::Time::now();
     if (nCtx == 1 && deviceChain) {
       // rows of the reads the device finished + records of the reads it handed over, instead of every record
@@ -460,6 +494,21 @@ class Map {
       if (mm_chain_counts(ctx, nullptr, nullptr, &nRows, &n) != MM_OK) die("mm_chain_counts");
       if (deviceChainLong && mm_chain_long_counts(ctx, &longOffered, &longFinished) != MM_OK) die("mm_chain_long_counts");
       if (deviceChainModes && mm_chain_group_counts(ctx, &groupReads, &groupRuns) != MM_OK) die("mm_chain_group_counts");
+      if (devicePaf) {
+        // the text of the reads the device finished and every read's span; rows only for reads handed over for a row that is not formattable
+        std::string names; std::vector<uint64_t> nameOff(1, 0);
+        nameOff.reserve(nReads + 1);
+        for (const auto& b : grp) for (const auto& nm : b.in.names) { names += nm; nameOff.push_back(names.size()); }
+        if (mm_paf_rows(ctx, names.data(), nameOff.data(), nReads) != MM_OK) die("mm_paf_rows");
+        if (mm_paf_counts(ctx, nullptr, nullptr, &pafBytes, nullptr, &pafHanded) != MM_OK) die("mm_paf_counts");
+        pafPass = std::make_shared<typename Batch::PafPass>();
+        pafPass->text.resize((size_t)pafBytes); pafPass->off.resize(nReads + 1); pafPass->handed.resize(nReads + 1);
+        size_t got = 0;
+        if (mm_paf_download(ctx, pafPass->text.data(), pafPass->text.size(), &got) != MM_OK) die("mm_paf_download");
+        if (mm_paf_offsets_download(ctx, pafPass->off.data(), pafPass->handed.data()) != MM_OK) die("mm_paf_offsets_download");
+        chainedRows = nRows;
+        if (!pafHanded) nRows = 0;
+      }
       allRows->resize(nRows); all->resize(n);
       if (nRows && mm_chain_download(ctx, allRows->data(), nRows, &nRows) != MM_OK) die("mm_chain_download");
       if (n && mm_chain_leftover_download(ctx, all->data(), n, &n) != MM_OK) die("mm_chain_leftover_download");
@@ -502,6 +551,7 @@ class Map {
         while (rowAt < nRows && (*allRows)[rowAt].querySeqId < endId) rowAt++;
         grp[j].recOwner = all; grp[j].recs = all->data() + b0; grp[j].nRecs = at - b0;
         grp[j].rowOwner = allRows; grp[j].rows = allRows->data() + r0; grp[j].nRows = rowAt - r0;
+        grp[j].paf = pafPass; grp[j].pafFirst = first[j];
       }
       if (at != n || rowAt != nRows) { std::cerr << "[mashmap_hip::skch::Map] ERROR: candidate mappings of a pass are not in input order" << std::endl; exit(1); }
     }
@@ -510,7 +560,58 @@ class Map {
                           << std::chrono::duration<double>(skch::Time::now() - t0).count() << " s (upload " << phase[0] << ", kernels " << phase[1]
                           << ", download " << std::chrono::duration<double>(skch::Time::now() - p2).count() << ") [bases " << passBases << "] [batches " << nB << "]"
                           << (deviceChainLong ? " [" + std::to_string(longFinished) + " of " + std::to_string(longOffered) + " reads of more than 16 records chained on the device]" : std::string())
-                          << (deviceChainModes ? " [" + std::to_string(groupRuns) + " group runs filtered on the device, " + std::to_string(groupReads) + " reads with more than one]" : std::string()) << at();
+                          << (deviceChainModes ? " [" + std::to_string(groupRuns) + " group runs filtered on the device, " + std::to_string(groupReads) + " reads with more than one]" : std::string())
+                          << (devicePaf ? " [" + std::to_string(pafBytes) + " bytes of PAF text of " + std::to_string(chainedRows) + " chained rows written on the device, " + std::to_string(pafHanded) + " reads handed over]" : std::string()) << at();
+  }
+
+  // post stage under MASHMAP_HIP_DEVICE_PAF: the device's text holds the lines of every read it finished, in read order; a read with
+  // left-over records (handed over by mm_chain_reads) or handed over by mm_paf_rows has an empty span there and is finished here as
+  // before.  The spans between two such reads are consecutive bytes of the text: each maximal run is written with one call, the host's
+  // lines in between.  Filter mode is not one-to-one and there is no callback (the constructor checked), so nothing keeps the mappings.
+  void postStagePaf(Batch& batch, const std::vector<size_t>& recBegin, const std::vector<size_t>& rowBegin, seqno_t& totalReadsMapped, std::ofstream& outstrm,
+                    skch::Time::time_point t0, bool timing) {
+    const size_t nReads = batch.size();
+    const typename Batch::PafPass& P = *batch.paf;
+    const int64_t* off = P.off.data() + batch.pafFirst;
+    const uint8_t* handed = P.handed.data() + batch.pafFirst;
+    std::vector<size_t> hostReads;                         // the reads this stage finishes itself
+    for (size_t r = 0; r < nReads; r++)
+      if (recBegin[r] != recBegin[r + 1] || (handed[r] && batch.nRows && rowBegin[r] != rowBegin[r + 1])) hostReads.push_back(r);
+    std::vector<std::string> hostText(hostReads.size());
+    const unsigned nThreads = std::min((unsigned)std::max(1, param.threads), mmhost::availableCpus());
+    std::atomic<size_t> next(0);
+    auto work = [&]() {
+      MappingResultsVector_t one;
+      for (size_t i = next.fetch_add(1); i < hostReads.size(); i = next.fetch_add(1)) {
+        const size_t r = hostReads[i];
+        const offset_t len = (offset_t)(batch.in.offs[r + 1] - batch.in.offs[r]);
+        if (len < param.kmerSize) continue;
+        one.clear();
+        if (handed[r]) post.finishRows(batch.rows + rowBegin[r], batch.rows + rowBegin[r + 1], len, one);
+        else post.mapModuleFromRecords(batch.recs + recBegin[r], batch.recs + recBegin[r + 1], len, one);
+        post.appendReadMappings(one, batch.in.names[r], hostText[i]);
+      }
+    };
+    if (!hostReads.empty()) {
+      if (!postPool || postPool->size() != nThreads) postPool.reset(new mmhost::WorkerPool(nThreads));
+      postPool->run(nThreads, [&](unsigned) { work(); });
+    }
+    const auto t1 = skch::Time::now();
+    seqno_t mapped = 0;
+    for (size_t r = 0; r < nReads; r++) mapped += off[r + 1] > off[r] ? 1 : 0;             // the device's readsWithText, of this batch
+    int64_t runStart = off[0];
+    for (size_t i = 0; i < hostReads.size(); i++) {
+      if (hostText[i].empty()) continue;
+      mapped++;
+      const int64_t here = off[hostReads[i]];
+      if (here > runStart) outstrm.write(P.text.data() + runStart, (std::streamsize)(here - runStart));
+      outstrm.write(hostText[i].data(), (std::streamsize)hostText[i].size());
+      runStart = here;
+    }
+    if (off[nReads] > runStart) outstrm.write(P.text.data() + runStart, (std::streamsize)(off[nReads] - runStart));
+    totalReadsMapped += mapped;
+    if (timing) LogLine() << "[mashmap_hip::timing] post stage: chain + filter + format " << std::chrono::duration<double>(t1 - t0).count()
+                          << " s, output " << std::chrono::duration<double>(skch::Time::now() - t1).count() << " s" << at();
   }
 
   // post stage: per read, chaining + filters + PAF text on param.threads threads; then output in input order
@@ -536,6 +637,7 @@ class Map {
         rowBegin[r] = i;
       }
     }
+    if (batch.paf) { postStagePaf(batch, recBegin, rowBegin, totalReadsMapped, outstrm, t0, timing); return; }
     // per CHUNK of 64 consecutive reads, not per read: one text buffer, one result vector, one counter (a hundred thousand small
     // allocations and frees per batch on this thread cost as much as the stage's work)
     const bool reportNow = param.filterMode != filter::ONETOONE;

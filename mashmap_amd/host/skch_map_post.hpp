@@ -509,6 +509,48 @@ class MapPost {
     }
   }
 
+  // the mapping quality of a line (:1763), stated once for appendReadMappings and for the table the device formats it from
+  static float fakeMapQOf(float nucIdentity) { return nucIdentity == 1 ? 255 : std::round(-10.0 * std::log10(1 - (nucIdentity))); }
+
+  // fakeMapQOf over [0, 1] as the table mm_set_paf_tables takes (include/mashmap_hip.h): ascending thresholds, thresholds[0] == 0 and
+  // the last == 1, and per entry the to_chars text of the value on [thresholds[i], thresholds[i + 1]), MM_PAF_MAPQ_TEXT bytes,
+  // NUL-padded.  Each threshold is the first float at which the value changes, found by bisection over the floats' bit patterns (which
+  // order as the floats do, from 0 up): that assumes the value never returns to an earlier one as the identity grows, which
+  // tests/hostlogic/paf_check.cpp checks against fakeMapQOf itself around every threshold and at random.
+  static void mapqTable(std::vector<float>& thresholds, std::vector<char>& text) {
+    auto bitsOf = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    auto floatOf = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+    thresholds.clear(); text.clear();
+    const uint32_t one = bitsOf(1.0f);
+    for (uint32_t cur = 0;;) {
+      const uint32_t v = bitsOf(fakeMapQOf(floatOf(cur)));
+      char b[64] = {0};
+      const auto r = std::to_chars(b, b + sizeof b, floatOf(v), std::chars_format::general, 6);
+      thresholds.push_back(floatOf(cur));
+      text.insert(text.end(), MM_PAF_MAPQ_TEXT, '\0');
+      std::memcpy(text.data() + text.size() - MM_PAF_MAPQ_TEXT, b, std::min<size_t>((size_t)(r.ptr - b), MM_PAF_MAPQ_TEXT - 1));
+      if (cur == one) break;
+      uint32_t lo = cur, hi = one;               // the value at lo is v, at hi it is another (at 1 it is 255, which no identity below reaches)
+      while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (bitsOf(fakeMapQOf(floatOf(mid))) == v) lo = mid; else hi = mid;
+      }
+      cur = hi;
+    }
+  }
+
+  // the parameter block mm_set_paf_tables takes for these parameters (include/mashmap_hip.h: mm_paf_params)
+  mm_paf_params pafParams() const {
+    mm_paf_params c{};
+    c.legacy = param.legacy_output ? 1 : 0;
+    c.aniPercentage = param.report_ANI_percentage ? 1 : 0;
+    c.merge = param.mergeMappings ? 1 : 0;
+    c.filterLengthMismatches = param.filterLengthMismatches ? 1 : 0;
+    c.lenIdThreshold = std::min(0.7, std::pow(param.percentageIdentity, 3));      // filterFalseHighIdentity's own expression
+    c.sparsityThreshold = param.sparsity_hash_threshold;
+    return c;
+  }
+
   // The same text appended to a string, field by field with std::to_chars: a stream insertion of a float goes through the locale
   // machinery (~0.3 us each, three per line), and a million reads a second is what the post stage has to keep up with.  An unformatted
   // operator<< of a float / double / long double is printf's %g with precision 6, which is chars_format::general with precision 6.
@@ -519,7 +561,7 @@ class MapPost {
     const char sep = param.legacy_output ? ' ' : '\t';
     const int back = param.legacy_output ? 1 : 0;
     for (const auto& e : readMappings) {
-      const float fakeMapQ = e.nucIdentity == 1 ? 255 : std::round(-10.0 * std::log10(1 - (e.nucIdentity)));
+      const float fakeMapQ = fakeMapQOf(e.nucIdentity);
       out += param.filterMode == filter::ONETOONE ? (*qmetadata)[e.querySeqId].name : queryName;
       out += sep; num(e.queryLen); out += sep; num(e.queryStartPos); out += sep; num(e.queryEndPos - back);
       out += sep; out += e.strand == strnd::FWD ? '+' : '-';

@@ -40,6 +40,13 @@ def host_lib():
         lib.mmh_chain_rows_modes.argtypes = lib.mmh_chain_rows.argtypes + [C.c_void_p, C.c_int]
         lib.mmh_post_chained_modes.restype = C.c_int64
         lib.mmh_post_chained_modes.argtypes = lib.mmh_post_chained.argtypes + [C.c_void_p, C.c_int]
+        # the PAF text: the mapQ table mm_set_paf_tables takes, and the host's own text of given rows (what mm_paf_rows / mm_paf_format must write)
+        lib.mmh_paf_mapq_table.restype = C.c_int
+        lib.mmh_paf_mapq_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.mmh_paf_text.restype = C.c_int64
+        lib.mmh_paf_text.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_void_p]
         _host = lib
     return _host
 
