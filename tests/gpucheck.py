@@ -96,12 +96,15 @@ def steady_leg(ctx, first, rule):
 
 
 def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=U.FLAG_HG, delim="\0", kmerPct=0.001,
-                    seqCounterBase=0, check_points=True, verbose=True, mutate_index=None, device_index=False, stats_out=None, pass_out=None):
+                    seqCounterBase=0, check_points=True, verbose=True, mutate_index=None, device_index=False, stats_out=None, pass_out=None,
+                    maps_out=None):
     """contigs: [(name, uint8 array)], reads: [(name, uint8 array)].  Returns (nFragments, nMappedLoci).
     device_index: the context builds its own index from the contigs' bases (mm_index_build: a5-a7 on the device) instead of taking the
     oracle's -- every stage downstream is then checked against the oracle on top of the DEVICE-built index.
     stats_out: a list that receives the per-fragment stats array (mm_frag_stats) of the compared pass.
-    pass_out: a dict that receives, of the first (sized, default-path) pass, "mid" = pass_l1_mid() and "literal" = pass_l1_literal()."""
+    pass_out: a dict that receives, of the first (sized, default-path) pass, "mid" = pass_l1_mid() and "literal" = pass_l1_literal().
+    maps_out: a dict that receives, per fragment, the candidate mappings (k_l2_select's records) of the compared pass IN DEVICE ORDER, each as
+    (refSeqId, refStartPos, conservedSketches, strand) -- the comparison below sorts them."""
     from mashmap_amd import capi
     h = oracle.session(contigs, k, L, s, pi, U.FILTER_MAP, flags, delim.encode() if delim != "\0" else b"\0", kmerPct, mutate_index=mutate_index)
     ix = oracle.export_index(h)
@@ -153,6 +156,9 @@ def run_and_compare(oracle, contigs, reads, k=19, L=5000, s=130, pi=0.85, flags=
         while (int(frs[f_at]["readId"]), int(frs[f_at]["fragStart"])) != key:
             f_at += 1                                    # records follow the fragment order
         recs_by_f.setdefault(f_at, []).append(m)
+    if maps_out is not None:
+        maps_out.update({f: [(int(m["refSeqId"]), int(m["refStartPos"]), int(m["conservedSketches"]), int(m["strand"])) for m in recs_by_f.get(f, [])]
+                         for f in range(nF)})
     l1_by_f = {}
     for i, c in enumerate(l1):
         l1_by_f.setdefault(int(c["frag"]), []).append((i, c))

@@ -95,6 +95,79 @@ int hl_map_read(int k, int segLength, int sketchSize, float pi, int filterMode, 
   return (int)res.size();
 }
 
+// mmhost::replayTables as the tests read it: (sketchSize + 1)^2 entries per table, row Qs at Qs * (sketchSize + 1)
+void hl_replay_tables(int sketchSize, int k, float pi, int keepLow, uint8_t* accept, int16_t* minIsz) {
+  std::vector<uint8_t> a; std::vector<int16_t> m;
+  mmhost::replayTables(sketchSize, k, pi, skch::Parameters().ANIDiff, keepLow != 0, 4, a, m);
+  std::memcpy(accept, a.data(), a.size()); std::memcpy(minIsz, m.data(), m.size() * sizeof(int16_t));
+}
+
+// doL2Mapping's walk over ONE fragment, twice, on integers the caller supplies: candidate c has (candSeq[c], candIsz[c]) and the loci
+// [l2Off[c], l2Off[c + 1]) of l2Shared.  Each walk returns its pushes, in push order, as (candidate, locus) pairs of indices.
+//   a  MapPost::doL2MappingReplay -- std::make_heap / std::pop_heap and the reference's float expressions --, called once per reference
+//      group as MapPost::fragmentMappings calls it (whose final sort by position would lose the order): the reference of the tests
+//   b  mm_select_fragment (mm_select_core.h, mm_heap.h) over the rows of mmhost::replayTables: the code k_l2_select compiles
+// Returns 0, or -1 when an output does not hold its pushes.
+int hl_select_walk(int k, int sketchSize, float pi, int flags, int Qs, int nC, const int32_t* candSeq, const int32_t* candIsz,
+                   const int32_t* l2Off, const int32_t* l2Shared, int nContigs, const int32_t* groups,
+                   int32_t* outA, int32_t* nA, int32_t* outB, int32_t* nB, int cap) {
+  skch::Parameters p;
+  p.kmerSize = k; p.segLength = 1000; p.sketchSize = sketchSize; p.percentageIdentity = pi;
+  p.stage1_topANI_filter = (flags & HL_HG) != 0; p.skip_prefix = (flags & HL_SKIP_PREFIX) != 0; p.keep_low_pct_id = !(flags & HL_DROP_LOW_ID);
+  const int nL2 = l2Off[nC];
+  std::vector<skch::ContigInfo> meta;
+  for (int i = 0; i < nContigs; i++) meta.push_back(skch::ContigInfo{"c" + std::to_string(i), 1 << 30});
+  std::vector<int> grp;
+  if (groups) grp.assign(groups, groups + nContigs);
+  skch::MapPost post(p, meta, grp);
+  skch::DeviceResults D;
+  D.stats.assign(1, mm_frag_stats{}); D.stats[0].sketchSize = Qs; D.stats[0].rawSketchSize = Qs; D.stats[0].nL1 = nC;
+  D.l1.resize((size_t)nC); D.l2.resize((size_t)nL2); D.l2Begin.assign(l2Off, l2Off + nC + 1);
+  for (int c = 0; c < nC; c++) {
+    D.l1[c] = mm_l1_candidate{}; D.l1[c].seqId = candSeq[c]; D.l1[c].intersectionSize = candIsz[c];
+    for (int i = l2Off[c]; i < l2Off[c + 1]; i++) {                // the locus carries its own index as its position
+      D.l2[i] = mm_l2_locus{}; D.l2[i].cand = c; D.l2[i].seqId = candSeq[c]; D.l2[i].meanOptimalPos = i; D.l2[i].sharedSketchSize = l2Shared[i]; D.l2[i].strand = 1;
+    }
+  }
+  *nA = *nB = 0;
+  if (Qs <= 0 || nC <= 0) return 0;
+  // a
+  {
+    skch::MappingResultsVector_t pushed;
+    std::vector<size_t> cands;
+    const std::vector<int>& g = post.groups();
+    size_t gb = 0;
+    while (gb < (size_t)nC) {                                      // MapPost::fragmentMappings' group loop
+      size_t ge = (size_t)nC;
+      if (p.skip_prefix) { const int g0 = g[D.l1[gb].seqId]; ge = gb; while (ge < (size_t)nC && g[D.l1[ge].seqId] == g0) ge++; }
+      cands.resize(ge - gb);
+      for (size_t i = 0; i < cands.size(); i++) cands[i] = gb + i;
+      post.doL2MappingReplay(D, 0, cands, 1000, 0, 1.0f, pushed);
+      gb = ge;
+    }
+    if ((int)pushed.size() > cap) return -1;
+    for (const auto& e : pushed) { outA[2 * *nA] = D.l2[(size_t)e.refStartPos].cand; outA[2 * *nA + 1] = (int32_t)e.refStartPos; ++*nA; }
+  }
+  // b
+  {
+    static std::vector<uint8_t> accept; static std::vector<int16_t> minIsz; static int have[4] = {-1, -1, -1, -1}; static float havePi = -1;
+    if (have[0] != sketchSize || have[1] != k || have[2] != (int)p.keep_low_pct_id || havePi != pi) {
+      mmhost::replayTables(sketchSize, k, pi, p.ANIDiff, p.keep_low_pct_id, 4, accept, minIsz);
+      have[0] = sketchSize; have[1] = k; have[2] = (int)p.keep_low_pct_id; havePi = pi;
+    }
+    const size_t stride = (size_t)sketchSize + 1;
+    std::vector<int64_t> l2First((size_t)nC); std::vector<int32_t> l2Num((size_t)nC), heap((size_t)nC + 1);
+    for (int c = 0; c < nC; c++) { l2First[c] = l2Off[c]; l2Num[c] = l2Off[c + 1] - l2Off[c]; }
+    std::vector<int32_t> rg(post.groups().begin(), post.groups().end());
+    bool full = false;
+    mm_select_fragment(nC, D.l1.data(), heap.data(), l2First.data(), l2Num.data(), D.l2.data(), rg.data(), p.skip_prefix ? 1 : 0,
+                       p.stage1_topANI_filter ? 1 : 0, Qs, accept.data() + (size_t)Qs * stride, minIsz.data() + (size_t)Qs * stride,
+                       [&](const mm_l2_locus& L) { if (*nB >= cap) { full = true; return; } outB[2 * *nB] = L.cand; outB[2 * *nB + 1] = L.meanOptimalPos; ++*nB; });
+    if (full) return -1;
+  }
+  return 0;
+}
+
 // PAF / legacy text: MapPost::appendReadMappings (std::to_chars, what the pipeline uses) against the literal stream form
 // (reportReadMappingsStream = computeMap.hpp:1758-1806) on n random mappings in every output mode.  Returns the number of modes x
 // batches whose bytes differ.

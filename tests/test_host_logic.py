@@ -5,7 +5,6 @@ reference's own L1/L2 stages, or from the committed golden vectors -- and must r
 import ctypes as C
 import json
 import os
-import subprocess
 import tempfile
 
 import numpy as np
@@ -15,7 +14,6 @@ import mmutil as U
 from golden import cases as CS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HL_DIR = os.path.join(ROOT, "tests", "hostlogic")
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 FRAG_DT = np.dtype([("readId", "<i4"), ("fragStart", "<i4"), ("len", "<i4"), ("pad", "<i4")])
@@ -27,13 +25,8 @@ L2_DT = np.dtype([("frag", "<i4"), ("cand", "<i4"), ("seqId", "<i4"), ("meanOpti
 
 @pytest.fixture(scope="module")
 def hl():
-    so = os.path.join(HL_DIR, "libhostlogic.so")
-    src = os.path.join(HL_DIR, "hostlogic.cpp")
-    hdrs = [os.path.join(ROOT, "mashmap_amd", "host", f) for f in ("skch_map_post.hpp", "skch_types.hpp", "mm_stats.hpp")]
-    hdrs += [os.path.join(ROOT, "mashmap_amd", "csrc", f) for f in ("mm_select_core.h", "mm_heap.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in [src] + hdrs):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wno-sign-compare", "-o", so, src])
-    lib = C.CDLL(so)
+    import selplant
+    lib = selplant.hostlogic()                               # builds tests/hostlogic/libhostlogic.so when a source of it is newer
     lib.hl_map_read.restype = C.c_int
     return lib
 
